@@ -10,10 +10,17 @@ ranks come from the environment; invoked plainly, this process spawns the N
 ranks itself (fresh child processes, before anything touches the GPU) and
 relays rank 0's line.  Rank 0 generates the synthetic weights and broadcasts
 them over RCCL, then every rank runs its own independent trajectory (no
-per-step traffic, weak scaling).  Rank 0 prints ONE JSON line.  At N=1 the line
-also carries a per-kernel roofline (HIP-event census of one eager step scaled to
-the graph-replay step time) and the CPU baseline (the oracle restatement of the
-reference's eager path, timed on the host cores for a bounded sample).
+per-step traffic, weak scaling).  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set up, warm up, time
+the K steps, print.  With --full the N=1 line also carries a per-kernel roofline
+(HIP-event census of one eager step scaled to the graph-replay step time), the
+side measurements of extras() and the CPU baseline (the oracle restatement of
+the reference's eager path, timed on the host cores for a bounded sample).
+
+--dump-outputs DIR writes, right after the timed steps, what they handed back
+(the fp32 latent of every rank) as DIR/<name>.npy; the inputs are seeded, so two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -56,7 +63,10 @@ def parse_args():
     ap.add_argument("--mode", choices=["auto", "loop", "step", "eager"], default="auto")
     ap.add_argument("--dtype", choices=["bf16", "fp16", "fp32"], default="bf16",
                     help="compute / storage type of the timed run (same matrix-pipe rate; fp16 is the reference call site's own type)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements of the N=1 line (loop-graph replay when the "
+    ap.add_argument("--full", action="store_true", help="add the census roofline, the side measurements and the CPU baseline to the "
+                                                        "N=1 line (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what they computed to DIR/<name>.npy (fp32)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements of the N=1 line (loop-graph replay when the "
                                                              "timed mode is 'step', the other 16-bit type, strict fp32)")
     ap.add_argument("--fp8", action="store_true", help="transformer-block projections on the fp8 matrix pipe (BASELINE config #5 mode; "
                                                        "a separate line with dtype fp8, never the headline)")
@@ -65,8 +75,8 @@ def parse_args():
     ap.add_argument("--img2img", type=float, default=None, metavar="STRENGTH",
                     help="img2img start (the refiner's use): the trajectory starts at schedule entry n - int(n * STRENGTH) from init latent + noise; "
                          "the timed steps are denoise steps from there (step graph, wrapping round the schedule)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-census", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-census", action="store_true", help="with --full: skip the per-kernel census and roofline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a same-device rehearsal)")
     ap.add_argument("--same-device", action="store_true", help="rehearsal only: every rank uses cuda:0")
     return ap.parse_args()
@@ -409,6 +419,24 @@ def cpu_baseline(model, latent_hw, spec):
                       f"1 warm-up ({times[0]:.1f} s) + 2 timed ({times[1]:.1f}, {times[2]:.1f} s), median {dt:.1f} s per step"}
 
 
+DUMP_BYTES = 64 << 20      # all dumped arrays together
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES):
+    """Write `arrays` (name -> tensor) as float32 DIR/<name>.npy in NCHW order.  An array over its even share of `budget`
+    is replaced by a fixed sample of its elements (seed 0, ascending flat indices): the same positions in every run."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    share = budget // max(len(arrays), 1) // 4
+    for name, t in arrays.items():
+        a = t.detach().float().contiguous().cpu()
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a.numpy())
+
+
 def rccl_report(path):
     """What RCCL logged at communicator init (NCCL_DEBUG=INFO to a per-rank file): rank count and transports seen."""
     try:
@@ -520,6 +548,8 @@ def main():
         parallel.barrier()
         elapsed = parallel.max_over_ranks(elapsed, dev)
         finite = bool(torch.isfinite(loop.latent).all())
+        if args.dump_outputs:           # before anything below steps the loop again
+            dump_outputs(args.dump_outputs, {"latent" if rank == 0 else f"latent_rank{rank}": loop.latent}, DUMP_BYTES // world)
 
         ms_per_step = elapsed / args.steps * 1e3
         result = {
@@ -550,7 +580,7 @@ def main():
                 rccl_problem = rccl_self_check(result["rccl"], world, ranks_seen) if rank == 0 else None
                 if result["rccl"] is None or result["rccl"].get("nranks_logged") is None:
                     result["rccl_note"] = "no init record in RCCL's log (NCCL_DEBUG preset?): verified by the all-reduce witness only"
-        if rank == 0 and world == 1:
+        if rank == 0 and world == 1 and args.full:
             if not args.no_census:
                 fam, census_ms, marker_ms, glue_ms = census(loop)
                 n_launch = sum(f["launches"] for f in fam.values())

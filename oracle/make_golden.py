@@ -8,6 +8,7 @@ fixtures are data (inputs are regenerated from seeds; outputs are stored); no
 reference source is copied.
 
     python oracle/make_golden.py f1 f2          # seconds .. a minute
+    python oracle/make_golden.py f0_schema      # seconds  (the reference module's state-dict schema, leaf-module calls and rewrite counts)
     python oracle/make_golden.py f3_64          # ~4 min   (50 Euler steps, latent 64)
     python oracle/make_golden.py f3_128         # ~20 min  (50 Euler steps, latent 128)
     python oracle/make_golden.py f1_b4          # ~1 min   (BASELINE config #3 rows: batch 4, per-row distinct conditioning)
@@ -320,11 +321,31 @@ def f3_f64(ref, cfg: bool, hw=64):
     _REF_UNET = None            # the module is double now: later fixtures of this process build a fresh one
 
 
+def f0_schema(ref):
+    """What tests/test_dropin_reference.py checks against: the reference module's state-dict schema (name -> shape), its fx
+    trace's leaf-module calls in order (qualified name, class) and the rewrite counts the backend passes leave on it."""
+    from torch import fx
+    from stabletriton_amd.optimization import replace_backend
+    with torch.device("meta"):
+        m = ref.UNet2DConditionModel()
+    sd = m.state_dict()
+    traced = fx.symbolic_trace(m)
+    mods = dict(traced.named_modules())
+    leaves = [(n.target, type(mods[n.target]).__name__) for n in traced.graph.nodes if n.op == "call_module"]
+    stats = replace_backend(fx.symbolic_trace(m)).rewrite_stats
+    save("f0_reference_schema",
+         sd_keys=np.array(list(sd)), sd_shapes=np.array([",".join(str(d) for d in v.shape) for v in sd.values()]),
+         leaf_targets=np.array([t for t, _ in leaves]), leaf_classes=np.array([c for _, c in leaves]),
+         stat_names=np.array(sorted(stats)), stat_values=np.array([int(stats[k]) for k in sorted(stats)]))
+
+
 if __name__ == "__main__":
     torch.set_num_threads(os.cpu_count() or 8)
     ref = load_reference()
     for what in sys.argv[1:] or ["f1", "f2"]:
-        if what == "f1":
+        if what == "f0_schema":
+            f0_schema(ref)
+        elif what == "f1":
             f1(ref)
         elif what == "f2":
             f2(ref)

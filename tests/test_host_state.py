@@ -120,6 +120,29 @@ def test_bench_self_launch_relays_rank0_and_fails_loudly(capsys):
     assert "rank 2" in capsys.readouterr().err
 
 
+def test_bench_plain_run_leaves_the_side_measurements_out(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    args = bench.parse_args()
+    assert args.steps == 7 and args.warmup == 3 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == "out"
+
+
+def test_bench_dump_outputs_is_nchw_fp32_within_its_budget(tmp_path):
+    import numpy as np
+    x = torch.arange(2 * 4 * 8 * 8, dtype=torch.float64).reshape(2, 4, 8, 8).contiguous(memory_format=torch.channels_last)
+    bench.dump_outputs(str(tmp_path / "whole"), {"latent": x})
+    a = np.load(tmp_path / "whole" / "latent.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 4, 8, 8) and np.array_equal(a, x.numpy())
+    bench.dump_outputs(str(tmp_path / "s1"), {"latent": x, "eps": x}, budget=256)         # 128 bytes = 32 elements each
+    bench.dump_outputs(str(tmp_path / "s2"), {"latent": x, "eps": x}, budget=256)
+    s = np.load(tmp_path / "s1" / "latent.npy")
+    assert s.dtype == np.float32 and s.shape == (32,)
+    assert np.all(np.diff(s) > 0)                        # distinct elements in flat NCHW order (values = flat indices)
+    assert np.array_equal(s, np.load(tmp_path / "s2" / "latent.npy"))      # the same positions in every run
+
+
 def test_host_cores_is_bounded_by_this_process():
     n, desc = bench.host_cores()
     assert 1 <= n <= (os.cpu_count() or 1) and n <= len(os.sched_getaffinity(0))

@@ -5,19 +5,19 @@ R=${R:-r5}
 set -x
 mkdir -p gpurun_out/$R/final && cd $GRAFT_REPO_ROOT
 o=gpurun_out/$R/final
-python bench.py > $o/bench_default.json 2> $o/bench_default.err
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_driver_call.json 2>/dev/null
-python bench.py --steps 50 --warmup 50 --no-cpu-baseline --no-extras --dtype fp16 > $o/bench_fp16.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 2 > $o/bench_b2.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 2 --fp8 > $o/bench_b2_fp8.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 4 > $o/bench_b4.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 4 --dtype fp16 > $o/bench_b4_fp16.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 4 --fp8 > $o/bench_b4_fp8.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras --fp8 > $o/bench_b1_fp8.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --mode step --no-cpu-baseline --no-extras --dtype fp32 > $o/bench_strict_fp32.json 2>/dev/null
-python bench.py --steps 50 --warmup 10 --mode step --no-cpu-baseline --no-extras --dtype fp32 --batch 4 > $o/bench_strict_fp32_b4.json 2>/dev/null
-python bench.py --model refiner --img2img 0.3 --steps 30 --warmup 15 --no-cpu-baseline --no-extras > $o/bench_refiner_img2img.json 2>/dev/null
-python bench.py --model refiner --img2img 0.3 --steps 30 --warmup 15 --no-cpu-baseline --no-extras --fp8 > $o/bench_refiner_img2img_fp8.json 2>/dev/null
+python bench.py --full > $o/bench_default.json 2> $o/bench_default.err
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $o/bench_driver_call.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 50 --no-cpu-baseline --no-extras --dtype fp16 > $o/bench_fp16.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 2 > $o/bench_b2.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 2 --fp8 > $o/bench_b2_fp8.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 4 > $o/bench_b4.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 4 --dtype fp16 > $o/bench_b4_fp16.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras --batch 4 --fp8 > $o/bench_b4_fp8.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-extras --fp8 > $o/bench_b1_fp8.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --mode step --no-cpu-baseline --no-extras --dtype fp32 > $o/bench_strict_fp32.json 2>/dev/null
+python bench.py --full --steps 50 --warmup 10 --mode step --no-cpu-baseline --no-extras --dtype fp32 --batch 4 > $o/bench_strict_fp32_b4.json 2>/dev/null
+python bench.py --full --model refiner --img2img 0.3 --steps 30 --warmup 15 --no-cpu-baseline --no-extras > $o/bench_refiner_img2img.json 2>/dev/null
+python bench.py --full --model refiner --img2img 0.3 --steps 30 --warmup 15 --no-cpu-baseline --no-extras --fp8 > $o/bench_refiner_img2img_fp8.json 2>/dev/null
 python bench.py --gpus 2 --same-device --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $o/bench_2rank_gloo_same_device.json 2> $o/bench_2rank.err
 # the driver's own launcher for N > 1 (torch.distributed.run, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from its env; fresh children, nothing here has touched the GPU)
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --same-device > $o/bench_2rank_torchrun_same_device.json 2> $o/bench_2rank_torchrun.err
