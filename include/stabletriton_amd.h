@@ -46,14 +46,15 @@ enum {
     ST_EPI_ROWBIAS   = 16   /* + rowbias[batch(m)][n]     (time-embedding add)    */
 };
 
-int         st_abi_version(void);          /* bumps on any signature or contract change; this header is ABI 16
+int         st_abi_version(void);          /* bumps on any signature or contract change; this header is ABI 17
                                               (6: next-weights hint passed per call, st_timestep_sincos; 7: fp8 entry points; 8: GroupNorm partials from the
                                               producer; 9: st_ln_linear_xattn; 10: ST_F16 accepted by every entry point
                                               that takes a dtype, st_ln_linear_xattn takes a dtype; 11: fp8 plan with
                                               delayed per-tensor scaling - st_linear_emit8, st_linear_fp8x, st_fp8_update_scales; 12: readers of a channel
                                               concatenation that is never written - st_group_norm_from_stats_cat, st_conv1x1_cat; 13: ST_F32S split fp32 matrix operands, st_split_f32, st_arm_split_output, st_attention_split; 14: st_attention
                                               takes head_dim 16 / 32 / 128 beside 64; 15: st_timestep_features takes the host's table of the reference's own features for integer timesteps;
-                                              16: next_weights_bytes carries the geometry of a strided touch in bits 40-61) */
+                                              16: next_weights_bytes carries the geometry of a strided touch in bits 40-61;
+                                              17: st_cfg_euler_step, st_cfg_step_workspace_bytes) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -209,6 +210,22 @@ int st_euler_step(float* latent, const void* eps, void* next_in, const float* ds
                   const float* in_scale, const int* step, long n, int n_steps,
                   int dtype, void* stream);
 int st_step_advance(int* step, int n_steps, void* stream);
+
+/* Classifier-free guidance fused into the Euler update (restated diffusers StableDiffusionXLPipeline.__call__ and its
+ * rescale_noise_cfg, see csrc/runtime.hip; the reference leaves this to the third-party pipeline).  With i = *step:
+ *   latent: batch x per_sample fp32; eps, next_in: 2*batch x per_sample in `dtype`, rows 0..B-1 the negative conditioning,
+ *   rows B..2B-1 the positive one (cat([uncond, cond])); every sample one dense block (channels_last as well);
+ *   e = e_neg + guidance[i] * (e_pos - e_neg);
+ *   rescale != NULL: phi = rescale[i], per sample e = phi * e * std(e_pos) / std(e) + (1 - phi) * e  (std over the
+ *     sample, correction 1; two launches through `workspace`, st_cfg_step_workspace_bytes(batch, per_sample) bytes,
+ *     bitwise deterministic);
+ *   latent += e * dsigma[i];  both halves of next_in = latent * in_scale[min(i + 1, n_steps - 1)] (cast to `dtype`).
+ * guidance / rescale are device tables of n_steps floats, so new values need no new capture.  per_sample % 8 == 0,
+ * latent / eps / next_in / workspace 16-byte aligned.  workspace may be NULL without a rescale table. */
+size_t st_cfg_step_workspace_bytes(int batch, long per_sample);
+int st_cfg_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
+                      const float* guidance, const float* rescale, const int* step, int batch, long per_sample,
+                      int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

@@ -16,7 +16,7 @@ from .build import lib_path
 ST_F32, ST_BF16, ST_F16, ST_F32S = 0, 1, 2, 3
 ST_NCHW, ST_NHWC = 0, 1
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_RESIDUAL, EPI_ROWBIAS = 1, 2, 4, 8, 16
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 _p, _i, _l, _f, _z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
@@ -49,6 +49,8 @@ SIGNATURES = {
     "st_split_f32": (_i, [_p, _p, _l, _i, _l, _p]),
     "st_arm_split_output": (_i, [_p, _l, _i]),
     "st_attention_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _p]),
+    "st_cfg_step_workspace_bytes": (_z, [_i, _l]),
+    "st_cfg_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
 }
 
 _lib = None

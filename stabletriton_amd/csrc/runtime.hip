@@ -43,7 +43,7 @@ int st_check_launch(const char* what) {
 }
 
 extern "C" const char* st_last_error(void) { return g_err; }
-extern "C" int st_abi_version(void) { return 16; }
+extern "C" int st_abi_version(void) { return 17; }
 
 // ---- Euler-discrete update ---------------------------------------------------
 template <typename T>
@@ -76,6 +76,207 @@ extern "C" int st_euler_step(float* latent, const void* eps, void* next_in, cons
     else
         return st_fail("euler_step: unsupported dtype %d", dtype);
     return st_check_launch("euler_step");
+}
+
+// ---- classifier-free guidance + Euler update ----------------------------------------------------------------------------
+// Restated third-party arithmetic (the reference leaves it to its Diffusers pipeline, diffusers 0.21.2
+// StableDiffusionXLPipeline.__call__ and its `rescale_noise_cfg`), per sample b, i = *step, all in fp32:
+//   e   = e_neg + g[i] * (e_pos - e_neg)                      e_neg = eps row b, e_pos = eps row B + b (cat([uncond, cond]))
+//   e   = phi * (e * (std(e_pos) / std(e))) + (1 - phi) * e   only with a rescale table, phi = rescale[i]; std over the
+//                                                             sample's C*H*W values with correction 1 (torch.std), no guard
+//                                                             against std(e) == 0 (diffusers has none)
+//   latent += e * dsigma[i];  next_in rows b and B + b = latent * in_scale[min(i + 1, n - 1)]
+// Both kernels map one block to CFG_BLOCK_ELEMS consecutive values of one sample (blockIdx.y = sample), 8 per lane as 16-byte
+// vectors.  The std needs the whole sample before any value can be written, and the rescale path must replay bit for bit: no
+// atomics and no hand-off between blocks of one launch.  Launch 1 writes each block's fp64 (sum, sum of squares) of e_pos and e
+// to its own workspace slot; launch 2 has every block of a sample re-reduce that sample's slots in one fixed order (so all of
+// them compute the same ratio), then apply.  Without a rescale table launch 2 runs alone.
+constexpr int CFG_THREADS = 256, CFG_VEC = 8, CFG_BLOCK_ELEMS = CFG_THREADS * CFG_VEC;
+
+static inline long cfg_blocks_per_sample(long per_sample) { return (per_sample + CFG_BLOCK_ELEMS - 1) / CFG_BLOCK_ELEMS; }
+
+template <typename T>
+__device__ __forceinline__ void cfg_load8(const T* p, float (&v)[8]) {
+    if constexpr (sizeof(T) == 4) {
+        const Vec16<T> a = load16(p), b = load16(p + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { v[k] = a.get(k); v[4 + k] = b.get(k); }
+    } else {
+        const Vec16<T> a = load16(p);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = a.get(k);
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void cfg_store8(T* p, const float (&v)[8]) {
+    if constexpr (sizeof(T) == 4) {
+        Vec16<T> a, b;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { a.set(k, v[k]); b.set(k, v[4 + k]); }
+        store16(p, a);
+        store16(p + 4, b);
+    } else {
+        Vec16<T> a;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a.set(k, v[k]);
+        store16(p, a);
+    }
+}
+
+// the guided eps of 8 values at offset j of sample b (also returns e_pos for the statistics)
+template <typename T>
+__device__ __forceinline__ void cfg_guided8(const T* __restrict__ eps, int batch, int b, long per_sample, long j, float g,
+                                            float (&e)[8], float (&pos)[8]) {
+    float neg[8];
+    cfg_load8(eps + (long)b * per_sample + j, neg);
+    cfg_load8(eps + (long)(batch + b) * per_sample + j, pos);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e[k] = neg[k] + g * (pos[k] - neg[k]);
+}
+
+// launch 1 (rescale only): ws[(b * nblk + blk) * 4 + {0..3}] = fp64 (sum e_pos, sum e_pos^2, sum e, sum e^2) over the block's values
+template <typename T>
+__global__ __launch_bounds__(CFG_THREADS) void cfg_stats_kernel(const T* __restrict__ eps, const float* __restrict__ guidance,
+                                                                const int* __restrict__ step, int batch, long per_sample,
+                                                                double* __restrict__ ws) {
+    const int b = blockIdx.y;
+    const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    if (j < per_sample) {                        // per_sample % 8 == 0: a lane's 8 values are all inside or all outside
+        float e[8], pos[8];
+        cfg_guided8(eps, batch, b, per_sample, j, guidance[*step], e, pos);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const double p = pos[k], q = e[k];
+            acc[0] += p; acc[1] = fma(p, p, acc[1]);
+            acc[2] += q; acc[3] = fma(q, q, acc[3]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o, 64);
+    __shared__ double part[CFG_THREADS / 64][4];
+    const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+    if (lane == 0)
+        for (int k = 0; k < 4; ++k) part[wave][k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double s = part[0][threadIdx.x];
+        for (int w = 1; w < CFG_THREADS / 64; ++w) s += part[w][threadIdx.x];
+        ws[((long)b * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = s;
+    }
+}
+
+// launch 2: guidance (+ rescale with the sample's ratio) + Euler update + both halves of the next UNet input
+template <typename T, bool RESCALE>
+__global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
+                                                                const float* __restrict__ dsigma, const float* __restrict__ in_scale,
+                                                                const float* __restrict__ guidance, const float* __restrict__ rescale,
+                                                                const int* __restrict__ step, int batch, long per_sample, int n_steps,
+                                                                const double* __restrict__ ws) {
+    const int b = blockIdx.y, i = *step;
+    float ratio = 1.f, phi = 0.f;
+    if constexpr (RESCALE) {
+        // every block of sample b reduces the same slots in the same order: lane l takes slots l, l + 64, ..., then a fixed tree
+        __shared__ float ratio_s;
+        if (threadIdx.x < 64) {
+            const double* p = ws + (long)b * gridDim.x * 4;
+            double acc[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int s = threadIdx.x; s < (int)gridDim.x; s += 64)
+                for (int k = 0; k < 4; ++k) acc[k] += p[(long)s * 4 + k];
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o, 64);
+            if (threadIdx.x == 0) {
+                const double n = (double)per_sample;
+                const double var_pos = (acc[1] - acc[0] * (acc[0] / n)) / (n - 1.0);
+                const double var_e = (acc[3] - acc[2] * (acc[2] / n)) / (n - 1.0);
+                ratio_s = (float)(sqrt(var_pos) / sqrt(var_e));
+            }
+        }
+        __syncthreads();
+        ratio = ratio_s;
+        phi = rescale[i];
+    }
+    const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
+    if (j >= per_sample) return;
+    const float g = guidance[i], ds = dsigma[i];
+    const float sc = in_scale[i + 1 < n_steps ? i + 1 : n_steps - 1];
+    float e[8], pos[8], x[8];
+    cfg_guided8(eps, batch, b, per_sample, j, g, e, pos);
+    if constexpr (RESCALE) {
+        const float keep = 1.f - phi;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) e[k] = phi * (e[k] * ratio) + keep * e[k];      // phi = 0: 0 * r + 1 * e == e, the plain path's bits
+    }
+    float* lat = latent + (long)b * per_sample + j;
+    {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(lat), c = *reinterpret_cast<const f32x4*>(lat + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { x[k] = a[k]; x[4 + k] = c[k]; }
+    }
+    float y[8];
+    f32x4 a, c;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        x[k] = x[k] + e[k] * ds;
+        y[k] = x[k] * sc;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { a[k] = x[k]; c[k] = x[4 + k]; }
+    *reinterpret_cast<f32x4*>(lat) = a;
+    *reinterpret_cast<f32x4*>(lat + 4) = c;
+    cfg_store8(next_in + (long)b * per_sample + j, y);
+    cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+}
+
+extern "C" size_t st_cfg_step_workspace_bytes(int batch, long per_sample) {
+    if (batch <= 0 || per_sample <= 0) return 0;
+    return (size_t)batch * (size_t)cfg_blocks_per_sample(per_sample) * 4 * sizeof(double);
+}
+
+template <typename T>
+static int cfg_launch(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale, const float* guidance,
+                       const float* rescale, const int* step, int batch, long per_sample, int n_steps, double* ws, hipStream_t st) {
+    const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (rescale) {
+        hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
+        if (st_check_launch("cfg_euler_step (statistics)")) return 1;
+        hipLaunchKernelGGL((cfg_euler_kernel<T, true>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, dsigma,
+                           in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)ws);
+    } else {
+        hipLaunchKernelGGL((cfg_euler_kernel<T, false>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, dsigma,
+                           in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)nullptr);
+    }
+    return st_check_launch("cfg_euler_step");
+}
+
+extern "C" int st_cfg_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
+                                 const float* guidance, const float* rescale, const int* step, int batch, long per_sample,
+                                 int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(latent && eps && next_in && dsigma && in_scale && guidance && step, "cfg_euler_step: null pointer");
+    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "cfg_euler_step: bad sizes (batch %d, per_sample %ld, n_steps %d)",
+               batch, per_sample, n_steps);
+    ST_REQUIRE(per_sample % CFG_VEC == 0, "cfg_euler_step: per_sample %ld is not a multiple of %d (16-byte vectors)", per_sample, CFG_VEC);
+    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "cfg_euler_step: grid too large");
+    ST_REQUIRE((uintptr_t)latent % 16 == 0 && (uintptr_t)eps % 16 == 0 && (uintptr_t)next_in % 16 == 0,
+               "cfg_euler_step: latent, eps and next_in must be 16-byte aligned");
+    if (rescale) {
+        const size_t need = st_cfg_step_workspace_bytes(batch, per_sample);
+        ST_REQUIRE(workspace && workspace_bytes >= need, "cfg_euler_step: the rescale path needs a workspace of %zu bytes, got %zu",
+                   need, workspace ? workspace_bytes : (size_t)0);
+        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "cfg_euler_step: workspace must be 16-byte aligned");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double* ws = (double*)workspace;
+    if (dtype == ST_BF16)
+        return cfg_launch<bf16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
+    if (dtype == ST_F16)
+        return cfg_launch<f16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
+    if (dtype == ST_F32)
+        return cfg_launch<float>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
+    return st_fail("cfg_euler_step: unsupported dtype %d", dtype);
 }
 
 __global__ void step_advance_kernel(int* step, int n_steps) {

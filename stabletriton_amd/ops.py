@@ -1159,6 +1159,44 @@ def euler_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, d
                                _C.dtype_code(eps.dtype), _C.stream_ptr()), "euler_step")
 
 
+def cfg_workspace(latent: torch.Tensor) -> torch.Tensor:
+    """Scratch of st_cfg_euler_step's guidance-rescale path for this latent (allocate once; a captured graph keeps its address)."""
+    n = _C.load().st_cfg_step_workspace_bytes(latent.shape[0], latent[0].numel())
+    return torch.empty(n, dtype=torch.uint8, device=latent.device)
+
+
+def cfg_euler_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, dsigma: torch.Tensor, in_scale: torch.Tensor,
+                   guidance: torch.Tensor, step: torch.Tensor, rescale: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None) -> None:
+    """In place, classifier-free guidance + Euler update: latent (B, ...) fp32; eps and next_in (2B, ...), rows [negative | positive];
+    i = *step: e = e_neg + guidance[i] (e_pos - e_neg), rescaled by rescale[i] when given (diffusers' rescale_noise_cfg);
+    latent += e * dsigma[i]; both halves of next_in = latent * in_scale[i + 1]."""
+    _C.require_device(latent, eps, next_in, dsigma, in_scale, guidance, step, rescale, workspace)
+    lib = _C.load()
+    if latent.dtype != torch.float32 or eps.dtype != next_in.dtype:
+        raise BackendError("cfg_euler_step: latent must be fp32 and eps/next_in share a dtype")
+    if not (latent.is_contiguous() or latent.is_contiguous(memory_format=torch.channels_last)):
+        raise BackendError("cfg_euler_step: latent must be dense (contiguous or channels_last)")
+    b = latent.shape[0]
+    if eps.shape != next_in.shape or eps.shape[0] != 2 * b or eps.shape[1:] != latent.shape[1:]:
+        raise BackendError(f"cfg_euler_step: eps and next_in must be (2B, ...) = {(2 * b, *latent.shape[1:])} for a latent of "
+                           f"{tuple(latent.shape)}; got {tuple(eps.shape)} and {tuple(next_in.shape)}")
+    if not (latent.stride() == eps.stride() == next_in.stride()):
+        raise BackendError("cfg_euler_step: latent, eps and next_in must share one dense layout")
+    n = dsigma.numel()
+    for name, t in (("in_scale", in_scale), ("guidance", guidance), ("rescale", rescale)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise BackendError(f"cfg_euler_step: {name} must be a contiguous fp32 table of n_steps = {n} values")
+    if step.dtype != torch.int32:
+        raise BackendError("cfg_euler_step: step must be int32")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(lib.st_cfg_euler_step(latent.data_ptr(), eps.data_ptr(), next_in.data_ptr(), dsigma.data_ptr(), in_scale.data_ptr(),
+                                   guidance.data_ptr(), _ptr(rescale), step.data_ptr(), b, latent[0].numel(), n,
+                                   _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()), "cfg_euler_step")
+
+
 def step_advance(step: torch.Tensor, n_steps: int) -> None:
     _C.require_device(step)
     _C.check(_C.load().st_step_advance(step.data_ptr(), n_steps, _C.stream_ptr()), "step_advance")

@@ -9,10 +9,17 @@ step], all on the device, so the 50 steps can be captured back to back and a
 run is one graph launch.  `mode="step"` captures a single step driven by a
 device-side step counter instead (replayed n times), `mode="eager"` captures
 nothing (used for per-kernel timing and debugging).
+
+With `guidance_scale` the loop runs classifier-free guidance the way the reference's Diffusers call site does
+(diffusers' StableDiffusionXLPipeline: UNet batch 2B = [negative | positive] conditioning, one latent per image):
+the UNet input, text context and time tables get 2B rows, and the Euler update is `st_cfg_euler_step`, which
+combines the two halves, optionally applies guidance rescale, and writes both halves of the next input.  The
+guidance (and rescale) values live in device tables of n_steps floats: `set_guidance` changes them without a
+new capture.
 """
 from __future__ import annotations
 
-from typing import Callable, Dict, Optional
+from typing import Callable, Dict, Optional, Sequence, Union
 
 import torch
 
@@ -23,8 +30,12 @@ from .scheduler import EulerTables, euler_discrete_tables
 class DenoiseLoop:
     def __init__(self, unet: Callable, batch: int, latent_hw, dtype: torch.dtype, device,
                  tables: Optional[EulerTables] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
-                 tokens: int = 77, mode: str = "loop", n_time_ids: int = 6):
+                 tokens: int = 77, mode: str = "loop", n_time_ids: int = 6,
+                 guidance_scale: Optional[Union[float, Sequence[float]]] = None,
+                 guidance_rescale: Optional[Union[float, Sequence[float]]] = None):
         assert mode in ("loop", "step", "eager")
+        if guidance_rescale is not None and guidance_scale is None:
+            raise ValueError("guidance_rescale needs guidance_scale")
         self.unet, self.mode, self.dtype = unet, mode, dtype
         self.device = torch.device(device)
         self.tables = tables or euler_discrete_tables(50)
@@ -34,16 +45,26 @@ class DenoiseLoop:
         # `latent_hw`: one side of a square latent, or (height, width) - SDXL's aspect buckets (1216 x 832 px = 152 x 104);
         # both sides multiples of 4: the UNet halves the latent twice (Downsample2D, unet_pt.py:246-256) and doubles it back
         lh, lw = (int(latent_hw[0]), int(latent_hw[1])) if isinstance(latent_hw, (tuple, list)) else (int(latent_hw), int(latent_hw))
+        self.batch = batch
+        rows = 2 * batch if guidance_scale is not None else batch       # guidance: the UNet sees [negative | positive]
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
-        self.x_in = torch.zeros((batch, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
-        self.ehs = torch.zeros((batch, tokens, cross_dim), dtype=dtype, device=dev)
-        self.text_embeds = torch.zeros((batch, pooled_dim), dtype=dtype, device=dev)
-        self.time_ids = torch.zeros((batch, n_time_ids), dtype=dtype, device=dev)
+        self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
+        self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
+        self.text_embeds = torch.zeros((rows, pooled_dim), dtype=dtype, device=dev)
+        self.time_ids = torch.zeros((rows, n_time_ids), dtype=dtype, device=dev)
         self.timesteps = torch.tensor(self.tables.timesteps, dtype=torch.float32, device=dev)
         self.dsigma = torch.tensor(self.tables.dsigma(), dtype=torch.float32, device=dev)
         self.in_scale = torch.tensor(self.tables.in_scale(), dtype=torch.float32, device=dev)
         self.step_ids = torch.arange(n, dtype=torch.int32, device=dev)      # constants for the unrolled loop
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)           # counter for mode="step"
+        # guidance: static per-step tables and the rescale path's scratch, read by address from the captured graph
+        self.guidance = self.rescale = self.cfg_workspace = None
+        if guidance_scale is not None:
+            self.guidance = torch.zeros(n, dtype=torch.float32, device=dev)
+            if guidance_rescale is not None:
+                self.rescale = torch.zeros(n, dtype=torch.float32, device=dev)
+                self.cfg_workspace = ops.cfg_workspace(self.latent)
+            self.set_guidance(guidance_scale, guidance_rescale)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -56,10 +77,51 @@ class DenoiseLoop:
         self.time_tables = None
 
     # ---- inputs --------------------------------------------------------------------------
-    def set_conditioning(self, encoder_hidden_states, text_embeds, time_ids) -> None:
-        self.ehs.copy_(encoder_hidden_states)
-        self.text_embeds.copy_(text_embeds)
-        self.time_ids.copy_(time_ids)
+    def set_guidance(self, scale: Union[float, Sequence[float]], rescale: Optional[Union[float, Sequence[float]]] = None) -> None:
+        """Guidance scale (and guidance rescale, diffusers' `guidance_rescale`) per step: a float, or a sequence of n_steps floats.
+        Written into the device tables in place: the next run uses them without a new capture.  `rescale=None` leaves the
+        rescale table as it is."""
+        if self.guidance is None:
+            raise ValueError("set_guidance: this loop was built without guidance_scale")
+        if rescale is not None and self.rescale is None:
+            raise ValueError("set_guidance: this loop was built without guidance_rescale")
+        g = self._step_table(scale, "scale")
+        r = self._step_table(rescale, "rescale") if rescale is not None else None
+        self.guidance.copy_(g)
+        if r is not None:
+            self.rescale.copy_(r)
+
+    def _step_table(self, v, what: str) -> torch.Tensor:
+        try:
+            vals = [float(x) for x in v]
+        except TypeError:                                  # a scalar (float, numpy scalar, 0-d tensor)
+            vals = [float(v)] * self.n_steps
+        if len(vals) != self.n_steps:
+            raise ValueError(f"set_guidance: {what} takes a float or {self.n_steps} values (one per step), got {len(vals)}")
+        return torch.tensor(vals, dtype=torch.float32)
+
+    def set_conditioning(self, encoder_hidden_states, text_embeds, time_ids, negative_encoder_hidden_states=None,
+                         negative_text_embeds=None, negative_time_ids=None) -> None:
+        """Prompt conditioning, B rows each.  With guidance the negative prompt's rows go first; a missing negative text
+        state or pooled embedding is zeros (SDXL's force_zeros_for_empty_prompt), missing negative time ids copy the
+        positive ones."""
+        negatives = (negative_encoder_hidden_states, negative_text_embeds, negative_time_ids)
+        if self.guidance is None:
+            if any(t is not None for t in negatives):
+                raise ValueError("set_conditioning: negative conditioning needs a loop built with guidance_scale")
+            self.ehs.copy_(encoder_hidden_states)
+            self.text_embeds.copy_(text_embeds)
+            self.time_ids.copy_(time_ids)
+        else:
+            b = self.batch
+            for buf, pos, neg in ((self.ehs, encoder_hidden_states, negative_encoder_hidden_states),
+                                  (self.text_embeds, text_embeds, negative_text_embeds),
+                                  (self.time_ids, time_ids, time_ids if negative_time_ids is None else negative_time_ids)):
+                buf[b:].copy_(pos)
+                if neg is None:
+                    buf[:b].zero_()
+                else:
+                    buf[:b].copy_(neg)
         self.refresh_weights()
         if self._split:
             with torch.no_grad():
@@ -94,7 +156,7 @@ class DenoiseLoop:
     def set_noise(self, latent_unit: torch.Tensor) -> None:
         """latent_unit ~ N(0,1); scaled by the scheduler's init sigma (fp32 state)."""
         self.latent.copy_(latent_unit.to(self.device, torch.float32) * self.tables.init_noise_sigma)
-        self.x_in.copy_(self.latent * float(self.tables.in_scale()[0]))
+        self._write_input(float(self.tables.in_scale()[0]))
         self.step.zero_()
         self._recalibrate(0)
 
@@ -111,10 +173,18 @@ class DenoiseLoop:
         sigma = float(self.tables.sigmas[t_start])
         lat = init_latent.to(self.device, torch.float32) + noise_unit.to(self.device, torch.float32) * sigma
         self.latent.copy_(lat)
-        self.x_in.copy_(self.latent * float(self.tables.in_scale()[t_start]))
+        self._write_input(float(self.tables.in_scale()[t_start]))
         self.step.fill_(t_start)
         self._recalibrate(t_start)
         return n - t_start
+
+    def _write_input(self, scale: float) -> None:
+        if self.guidance is None:
+            self.x_in.copy_(self.latent * scale)
+            return
+        v = self.latent * scale
+        self.x_in[:self.batch].copy_(v)
+        self.x_in[self.batch:].copy_(v)
 
     def _recalibrate(self, i: int) -> None:
         """fp8 plan only: a trajectory starts from scales measured on its own first evaluation (not on the last step of
@@ -141,15 +211,22 @@ class DenoiseLoop:
     def _step_const(self, i: int) -> None:
         row = tuple(tbl[i] for tbl in self.time_tables) if self._tsplit else None      # static views: no launch
         eps = self._unet(self.timesteps[i], row)
-        ops.euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.step_ids[i:i + 1])
+        self._update(eps, self.step_ids[i:i + 1])
 
     def _step_counted(self) -> None:
         idx = self.step.long()
         t = self.timesteps.index_select(0, idx)[0]
         row = tuple(tbl.index_select(0, idx)[0] for tbl in self.time_tables) if self._tsplit else None
         eps = self._unet(t, row)
-        ops.euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.step)
+        self._update(eps, self.step)
         ops.step_advance(self.step, self.n_steps)
+
+    def _update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
+        if self.guidance is None:
+            ops.euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, step)
+        else:
+            ops.cfg_euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.guidance, step, self.rescale,
+                               self.cfg_workspace)
 
     # ---- capture / run -------------------------------------------------------------------
     def capture(self, warmup: int = 1) -> None:
