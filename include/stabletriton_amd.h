@@ -54,7 +54,8 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               concatenation that is never written - st_group_norm_from_stats_cat, st_conv1x1_cat; 13: ST_F32S split fp32 matrix operands, st_split_f32, st_arm_split_output, st_attention_split; 14: st_attention
                                               takes head_dim 16 / 32 / 128 beside 64; 15: st_timestep_features takes the host's table of the reference's own features for integer timesteps;
                                               16: next_weights_bytes carries the geometry of a strided touch in bits 40-61;
-                                              17: st_cfg_euler_step, st_cfg_step_workspace_bytes) */
+                                              17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, added
+                                              without a bump: a new entry point, no existing signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -226,6 +227,23 @@ size_t st_cfg_step_workspace_bytes(int batch, long per_sample);
 int st_cfg_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
                       const float* guidance, const float* rescale, const int* step, int batch, long per_sample,
                       int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* DPM-Solver++(2M) update (data prediction, second-order multistep; stabletriton_amd/scheduler.py states the arithmetic),
+ * optionally with the classifier-free guidance of st_cfg_euler_step.  With i = *step and coef row i = [sigma, a, b, k]
+ * (n_steps rows of 4 floats, DPMSolverTables.coefficients()):
+ *   e: eps row b of sample b (guidance == NULL: eps and next_in have `batch` rows), or the guided (+ rescaled) eps of st_cfg_euler_step
+ *      (guidance != NULL: eps and next_in have 2*batch rows [negative | positive]; rescale needs guidance and uses the same
+ *      workspace, st_cfg_step_workspace_bytes(batch, per_sample) bytes);
+ *   d = latent - sigma * e;
+ *   latent = a * latent + b * ((1 + k) * d - k * history) when i != *start and k != 0, else a * latent + b * d, and then
+ *     history is not read at all (the first step after a start, the last step);
+ *   history = d;  next_in (both halves when guided) = latent * in_scale[min(i + 1, n_steps - 1)] (cast to `dtype`).
+ * latent and history: batch x per_sample fp32, every sample one dense block (channels_last as well).  per_sample % 8 == 0;
+ * latent / eps / next_in / history / workspace 16-byte aligned.  coef, in_scale, guidance, rescale are device tables, step
+ * and start device ints, so a captured graph reads them by address.  No atomics: bitwise deterministic. */
+int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                    const float* guidance, const float* rescale, const int* step, const int* start, int batch, long per_sample,
+                    int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

@@ -51,6 +51,7 @@ SIGNATURES = {
     "st_attention_split": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _p]),
     "st_cfg_step_workspace_bytes": (_z, [_i, _l]),
     "st_cfg_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
+    "st_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
 }
 
 _lib = None

@@ -168,6 +168,29 @@ __global__ __launch_bounds__(CFG_THREADS) void cfg_stats_kernel(const T* __restr
     }
 }
 
+// launch 2's std(e_pos) / std(e) of sample b, the same value in every block of the sample: every block reduces the same slots
+// in the same order (lane l takes slots l, l + 64, ..., then a fixed tree).  Called by every thread of the block (a barrier).
+__device__ __forceinline__ float cfg_rescale_ratio(const double* __restrict__ ws, int b, long per_sample) {
+    __shared__ float ratio_s;
+    if (threadIdx.x < 64) {
+        const double* p = ws + (long)b * gridDim.x * 4;
+        double acc[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int s = threadIdx.x; s < (int)gridDim.x; s += 64)
+            for (int k = 0; k < 4; ++k) acc[k] += p[(long)s * 4 + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o, 64);
+        if (threadIdx.x == 0) {
+            const double n = (double)per_sample;
+            const double var_pos = (acc[1] - acc[0] * (acc[0] / n)) / (n - 1.0);
+            const double var_e = (acc[3] - acc[2] * (acc[2] / n)) / (n - 1.0);
+            ratio_s = (float)(sqrt(var_pos) / sqrt(var_e));
+        }
+    }
+    __syncthreads();
+    return ratio_s;
+}
+
 // launch 2: guidance (+ rescale with the sample's ratio) + Euler update + both halves of the next UNet input
 template <typename T, bool RESCALE>
 __global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
@@ -178,25 +201,7 @@ __global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restric
     const int b = blockIdx.y, i = *step;
     float ratio = 1.f, phi = 0.f;
     if constexpr (RESCALE) {
-        // every block of sample b reduces the same slots in the same order: lane l takes slots l, l + 64, ..., then a fixed tree
-        __shared__ float ratio_s;
-        if (threadIdx.x < 64) {
-            const double* p = ws + (long)b * gridDim.x * 4;
-            double acc[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int s = threadIdx.x; s < (int)gridDim.x; s += 64)
-                for (int k = 0; k < 4; ++k) acc[k] += p[(long)s * 4 + k];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_down(acc[k], o, 64);
-            if (threadIdx.x == 0) {
-                const double n = (double)per_sample;
-                const double var_pos = (acc[1] - acc[0] * (acc[0] / n)) / (n - 1.0);
-                const double var_e = (acc[3] - acc[2] * (acc[2] / n)) / (n - 1.0);
-                ratio_s = (float)(sqrt(var_pos) / sqrt(var_e));
-            }
-        }
-        __syncthreads();
-        ratio = ratio_s;
+        ratio = cfg_rescale_ratio(ws, b, per_sample);
         phi = rescale[i];
     }
     const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
@@ -277,6 +282,117 @@ extern "C" int st_cfg_euler_step(float* latent, const void* eps, void* next_in, 
     if (dtype == ST_F32)
         return cfg_launch<float>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
     return st_fail("cfg_euler_step: unsupported dtype %d", dtype);
+}
+
+// ---- DPM-Solver++(2M) update (scheduler.py docstring; k-diffusion's sample_dpmpp_2m in sigma form) ----------------------
+// Per sample b, i = *step, coef row i = [sigma, a, bb, k], all in fp32:
+//   e = eps row b (unguided), or the guided (+ rescaled) eps of st_cfg_euler_step from rows b and B + b
+//   d = x - sigma * e
+//   x = a * x + bb * ((1 + k) * d - k * d_prev)   second order, d_prev = history; only when i != *start and k != 0
+//   x = a * x + bb * d                            first order: history is not read (a branch, so stale or NaN values
+//                                                 never reach the output)
+//   history = d;  next_in row b (and B + b when guided) = x * in_scale[min(i + 1, n - 1)]
+// The block mapping, the 16-byte vectors and the rescale statistics (cfg_stats_kernel, launch 1) are the CFG kernel's.
+template <typename T, bool GUIDED, bool RESCALE>
+__global__ __launch_bounds__(CFG_THREADS) void dpmpp2m_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
+                                                              float* __restrict__ history, const float* __restrict__ coef,
+                                                              const float* __restrict__ in_scale, const float* __restrict__ guidance,
+                                                              const float* __restrict__ rescale, const int* __restrict__ step,
+                                                              const int* __restrict__ start, int batch, long per_sample, int n_steps,
+                                                              const double* __restrict__ ws) {
+    const int b = blockIdx.y, i = *step;
+    float ratio = 1.f, phi = 0.f;
+    if constexpr (RESCALE) {
+        ratio = cfg_rescale_ratio(ws, b, per_sample);
+        phi = rescale[i];
+    }
+    const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
+    if (j >= per_sample) return;
+    const float sigma = coef[4 * i], a = coef[4 * i + 1], bb = coef[4 * i + 2], k = coef[4 * i + 3];
+    const bool second = i != *start && k != 0.f;
+    const float sc = in_scale[i + 1 < n_steps ? i + 1 : n_steps - 1];
+    float e[8];
+    if constexpr (GUIDED) {
+        float pos[8];
+        cfg_guided8(eps, batch, b, per_sample, j, guidance[i], e, pos);
+        if constexpr (RESCALE) {
+            const float keep = 1.f - phi;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) e[q] = phi * (e[q] * ratio) + keep * e[q];   // phi = 0: the plain path's bits
+        }
+    } else {
+        cfg_load8(eps + (long)b * per_sample + j, e);
+    }
+    float* lat = latent + (long)b * per_sample + j;
+    float* hist = history + (long)b * per_sample + j;
+    float x[8], d[8], y[8];
+    cfg_load8(lat, x);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) d[q] = x[q] - sigma * e[q];
+    if (second) {
+        float prev[8];
+        cfg_load8(hist, prev);
+        const float kp = 1.f + k;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = a * x[q] + bb * (kp * d[q] - k * prev[q]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = a * x[q] + bb * d[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) y[q] = x[q] * sc;
+    cfg_store8(hist, d);
+    cfg_store8(lat, x);
+    cfg_store8(next_in + (long)b * per_sample + j, y);
+    if constexpr (GUIDED) cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+}
+
+template <typename T>
+static int dpm_launch(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                      const float* guidance, const float* rescale, const int* step, const int* start, int batch, long per_sample,
+                      int n_steps, double* ws, hipStream_t st) {
+    const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (rescale) {
+        hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
+        if (st_check_launch("dpmpp2m_step (statistics)")) return 1;
+        hipLaunchKernelGGL((dpmpp2m_kernel<T, true, true>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                           coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)ws);
+    } else if (guidance) {
+        hipLaunchKernelGGL((dpmpp2m_kernel<T, true, false>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                           coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)nullptr);
+    } else {
+        hipLaunchKernelGGL((dpmpp2m_kernel<T, false, false>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                           coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)nullptr);
+    }
+    return st_check_launch("dpmpp2m_step");
+}
+
+extern "C" int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                               const float* guidance, const float* rescale, const int* step, const int* start, int batch,
+                               long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start, "dpmpp2m_step: null pointer");
+    ST_REQUIRE(!rescale || guidance, "dpmpp2m_step: a rescale table needs a guidance table");
+    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "dpmpp2m_step: bad sizes (batch %d, per_sample %ld, n_steps %d)",
+               batch, per_sample, n_steps);
+    ST_REQUIRE(per_sample % CFG_VEC == 0, "dpmpp2m_step: per_sample %ld is not a multiple of %d (16-byte vectors)", per_sample, CFG_VEC);
+    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "dpmpp2m_step: grid too large");
+    ST_REQUIRE((uintptr_t)latent % 16 == 0 && (uintptr_t)eps % 16 == 0 && (uintptr_t)next_in % 16 == 0 && (uintptr_t)history % 16 == 0,
+               "dpmpp2m_step: latent, eps, next_in and history must be 16-byte aligned");
+    if (rescale) {
+        const size_t need = st_cfg_step_workspace_bytes(batch, per_sample);
+        ST_REQUIRE(workspace && workspace_bytes >= need, "dpmpp2m_step: the rescale path needs a workspace of %zu bytes, got %zu",
+                   need, workspace ? workspace_bytes : (size_t)0);
+        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "dpmpp2m_step: workspace must be 16-byte aligned");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double* ws = (double*)workspace;
+    if (dtype == ST_BF16)
+        return dpm_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
+    if (dtype == ST_F16)
+        return dpm_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
+    if (dtype == ST_F32)
+        return dpm_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
+    return st_fail("dpmpp2m_step: unsupported dtype %d", dtype);
 }
 
 __global__ void step_advance_kernel(int* step, int n_steps) {

@@ -1197,6 +1197,48 @@ def cfg_euler_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tenso
                                    _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()), "cfg_euler_step")
 
 
+def dpmpp2m_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, history: torch.Tensor, coef: torch.Tensor,
+                 in_scale: torch.Tensor, step: torch.Tensor, start: torch.Tensor, guidance: Optional[torch.Tensor] = None,
+                 rescale: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """In place, the DPM-Solver++(2M) update (scheduler.py): latent and history (B, ...) fp32; i = *step, coef row i =
+    [sigma, a, b, k]: d = latent - sigma e; latent = a latent + b ((1 + k) d - k history), first order (history unread) when
+    i == *start or k == 0; history = d; next_in = latent * in_scale[i + 1].  Without guidance eps and next_in have B rows and
+    e = eps; with it they have 2B rows [negative | positive] and e is cfg_euler_step's guided (+ rescaled) eps."""
+    _C.require_device(latent, eps, next_in, history, coef, in_scale, step, start, guidance, rescale, workspace)
+    lib = _C.load()
+    if latent.dtype != torch.float32 or history.dtype != torch.float32 or eps.dtype != next_in.dtype:
+        raise BackendError("dpmpp2m_step: latent and history must be fp32 and eps/next_in share a dtype")
+    if not (latent.is_contiguous() or latent.is_contiguous(memory_format=torch.channels_last)):
+        raise BackendError("dpmpp2m_step: latent must be dense (contiguous or channels_last)")
+    if rescale is not None and guidance is None:
+        raise BackendError("dpmpp2m_step: rescale needs guidance")
+    b = latent.shape[0]
+    rows = 2 * b if guidance is not None else b
+    if history.shape != latent.shape:
+        raise BackendError(f"dpmpp2m_step: history must match the latent {tuple(latent.shape)}; got {tuple(history.shape)}")
+    if eps.shape != next_in.shape or eps.shape[0] != rows or eps.shape[1:] != latent.shape[1:]:
+        what = "(2B, ...)" if guidance is not None else "(B, ...)"
+        raise BackendError(f"dpmpp2m_step: eps and next_in must be {what} = {(rows, *latent.shape[1:])} for a latent of "
+                           f"{tuple(latent.shape)}; got {tuple(eps.shape)} and {tuple(next_in.shape)}")
+    if not (latent.stride() == history.stride() == eps.stride() == next_in.stride()):
+        raise BackendError("dpmpp2m_step: latent, history, eps and next_in must share one dense layout")
+    n = in_scale.numel()
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 4) or not coef.is_contiguous():
+        raise BackendError(f"dpmpp2m_step: coef must be a contiguous fp32 (n_steps, 4) = ({n}, 4) table")
+    for name, t in (("in_scale", in_scale), ("guidance", guidance), ("rescale", rescale)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise BackendError(f"dpmpp2m_step: {name} must be a contiguous fp32 table of n_steps = {n} values")
+    if step.dtype != torch.int32 or start.dtype != torch.int32:
+        raise BackendError("dpmpp2m_step: step and start must be int32")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(lib.st_dpmpp2m_step(latent.data_ptr(), eps.data_ptr(), next_in.data_ptr(), history.data_ptr(), coef.data_ptr(),
+                                 in_scale.data_ptr(), _ptr(guidance), _ptr(rescale), step.data_ptr(), start.data_ptr(), b,
+                                 latent[0].numel(), n, _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()),
+             "dpmpp2m_step")
+
+
 def step_advance(step: torch.Tensor, n_steps: int) -> None:
     _C.require_device(step)
     _C.check(_C.load().st_step_advance(step.data_ptr(), n_steps, _C.stream_ptr()), "step_advance")

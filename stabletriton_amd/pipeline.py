@@ -16,6 +16,12 @@ the UNet input, text context and time tables get 2B rows, and the Euler update i
 combines the two halves, optionally applies guidance rescale, and writes both halves of the next input.  The
 guidance (and rescale) values live in device tables of n_steps floats: `set_guidance` changes them without a
 new capture.
+
+With `DPMSolverTables` (scheduler.dpmpp_2m_tables) the update is DPM-Solver++(2M), `st_dpmpp2m_step`, guided or not.  The
+solver carries the previous step's prediction of the clean latent in a static fp32 `history` buffer, and a device int
+`start` marks the step a trajectory starts from (0 after set_noise, t_start after set_image): that step is first-order and
+does not read the history.  Both, with the coefficient table, are read by address from the captured graph.  The solver
+follows from the type of the tables; Euler tables keep the Euler update and its buffers.
 """
 from __future__ import annotations
 
@@ -24,12 +30,12 @@ from typing import Callable, Dict, Optional, Sequence, Union
 import torch
 
 from . import ops
-from .scheduler import EulerTables, euler_discrete_tables
+from .scheduler import DPMSolverTables, EulerTables, euler_discrete_tables
 
 
 class DenoiseLoop:
     def __init__(self, unet: Callable, batch: int, latent_hw, dtype: torch.dtype, device,
-                 tables: Optional[EulerTables] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
+                 tables: Optional[Union[EulerTables, DPMSolverTables]] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
                  tokens: int = 77, mode: str = "loop", n_time_ids: int = 6,
                  guidance_scale: Optional[Union[float, Sequence[float]]] = None,
                  guidance_rescale: Optional[Union[float, Sequence[float]]] = None):
@@ -53,7 +59,15 @@ class DenoiseLoop:
         self.text_embeds = torch.zeros((rows, pooled_dim), dtype=dtype, device=dev)
         self.time_ids = torch.zeros((rows, n_time_ids), dtype=dtype, device=dev)
         self.timesteps = torch.tensor(self.tables.timesteps, dtype=torch.float32, device=dev)
-        self.dsigma = torch.tensor(self.tables.dsigma(), dtype=torch.float32, device=dev)
+        # the update's tables: Euler reads dsigma; DPM-Solver++(2M) its coefficient rows, the previous step's clean-latent
+        # prediction (history) and the trajectory's start step
+        self.dsigma = self.coef = self.history = self.start = None
+        if isinstance(self.tables, DPMSolverTables):
+            self.coef = torch.tensor(self.tables.coefficients(), dtype=torch.float32, device=dev)
+            self.history = torch.zeros_like(self.latent)
+            self.start = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            self.dsigma = torch.tensor(self.tables.dsigma(), dtype=torch.float32, device=dev)
         self.in_scale = torch.tensor(self.tables.in_scale(), dtype=torch.float32, device=dev)
         self.step_ids = torch.arange(n, dtype=torch.int32, device=dev)      # constants for the unrolled loop
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)           # counter for mode="step"
@@ -158,6 +172,8 @@ class DenoiseLoop:
         self.latent.copy_(latent_unit.to(self.device, torch.float32) * self.tables.init_noise_sigma)
         self._write_input(float(self.tables.in_scale()[0]))
         self.step.zero_()
+        if self.start is not None:
+            self.start.zero_()
         self._recalibrate(0)
 
     def set_image(self, init_latent: torch.Tensor, noise_unit: torch.Tensor, strength: float) -> int:
@@ -175,6 +191,8 @@ class DenoiseLoop:
         self.latent.copy_(lat)
         self._write_input(float(self.tables.in_scale()[t_start]))
         self.step.fill_(t_start)
+        if self.start is not None:
+            self.start.fill_(t_start)
         self._recalibrate(t_start)
         return n - t_start
 
@@ -222,7 +240,10 @@ class DenoiseLoop:
         ops.step_advance(self.step, self.n_steps)
 
     def _update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
-        if self.guidance is None:
+        if self.coef is not None:
+            ops.dpmpp2m_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.guidance,
+                             self.rescale, self.cfg_workspace)
+        elif self.guidance is None:
             ops.euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, step)
         else:
             ops.cfg_euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.guidance, step, self.rescale,
@@ -232,7 +253,7 @@ class DenoiseLoop:
     def capture(self, warmup: int = 1) -> None:
         if self.mode == "eager" or self.graph is not None:
             return
-        keep = (self.latent.clone(), self.x_in.clone(), self.step.clone())
+        keep = (self.latent.clone(), self.x_in.clone(), self.step.clone(), None if self.history is None else self.history.clone())
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
@@ -240,7 +261,7 @@ class DenoiseLoop:
                 self._step_counted() if self.mode == "step" else self._step_const(0)
         torch.cuda.current_stream(self.device).wait_stream(side)
         torch.cuda.synchronize(self.device)
-        self.latent.copy_(keep[0]); self.x_in.copy_(keep[1]); self.step.copy_(keep[2])
+        self._restore(keep)
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
@@ -252,10 +273,15 @@ class DenoiseLoop:
                     self._step_const(i)
                 self._captured_steps = self.n_steps
         self.graph = g
-        self.latent.copy_(keep[0]); self.x_in.copy_(keep[1]); self.step.copy_(keep[2])
+        self._restore(keep)
         # (fp8 plan: the warm-up evaluation above measured the scales its own way; start them over exactly as set_noise /
         #  set_image do, so the first trajectory after a capture equals every later one)
         self._recalibrate(int(keep[2].item()) % self.n_steps)
+
+    def _restore(self, keep) -> None:
+        self.latent.copy_(keep[0]); self.x_in.copy_(keep[1]); self.step.copy_(keep[2])
+        if keep[3] is not None:
+            self.history.copy_(keep[3])
 
     def run_steps(self, k: int) -> None:
         """Advance exactly k denoise steps from the current state (asynchronous)."""
