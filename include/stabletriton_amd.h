@@ -54,8 +54,9 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               concatenation that is never written - st_group_norm_from_stats_cat, st_conv1x1_cat; 13: ST_F32S split fp32 matrix operands, st_split_f32, st_arm_split_output, st_attention_split; 14: st_attention
                                               takes head_dim 16 / 32 / 128 beside 64; 15: st_timestep_features takes the host's table of the reference's own features for integer timesteps;
                                               16: next_weights_bytes carries the geometry of a strided touch in bits 40-61;
-                                              17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, added
-                                              without a bump: a new entry point, no existing signature or contract changed) */
+                                              17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, and then
+                                              st_sde_step and st_philox_normal, added without a bump: new entry points, no existing
+                                              signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -244,6 +245,25 @@ int st_cfg_euler_step(float* latent, const void* eps, void* next_in, const float
 int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
                     const float* guidance, const float* rescale, const int* step, const int* start, int batch, long per_sample,
                     int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Counter-based Gaussian noise (Philox4x32-10 + Box-Muller; stabletriton_amd/rng.py states the stream and restates it in
+ * float64): out[b][j] = the stream of seed seeds[b] at counter word `counter`, element j, for j < per_sample (memory order,
+ * one dense block per sample).  A pure function of (seed, counter, j): nothing is stored or advanced, so a captured graph
+ * replays the same values.  seeds: a device table of `batch` 64-bit seeds; out 16-byte aligned; per_sample % 4 == 0 and at
+ * most 4 * 2^32.  This project's own stream: it does not reproduce torch's generator. */
+int st_philox_normal(float* out, const unsigned long long* seeds, int batch, long per_sample, unsigned counter, void* stream);
+
+/* Stochastic update: Euler ancestral and DPM++ 2M SDE in one row form (stabletriton_amd/scheduler.py, SDETables).  The
+ * arguments of st_dpmpp2m_step plus `seeds` (a device table of `batch` 64-bit seeds, one per latent sample, also when
+ * guided), and coef rows of 5 floats [sigma, a, b, k, c] (SDETables.coefficients()).  With i = *step:
+ *   e, d, latent and history exactly as st_dpmpp2m_step (first order when i == *start or k == 0: history unread);
+ *   then, only when c != 0, latent += c * z with z the st_philox_normal stream of seeds[b] at counter word i + 1;
+ *   next_in (both halves when guided) = latent * in_scale[min(i + 1, n_steps - 1)] (cast to `dtype`).
+ * A row with c == 0 (the last step; eta = 0) draws nothing and gives st_dpmpp2m_step's bits.  per_sample % 8 == 0 and at
+ * most 4 * 2^32; latent / eps / next_in / history / workspace 16-byte aligned.  No atomics: bitwise deterministic. */
+int st_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                const float* guidance, const float* rescale, const int* step, const int* start, const unsigned long long* seeds,
+                int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

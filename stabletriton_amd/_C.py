@@ -52,6 +52,8 @@ SIGNATURES = {
     "st_cfg_step_workspace_bytes": (_z, [_i, _l]),
     "st_cfg_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
+    "st_philox_normal": (_i, [_p, _p, _i, _l, C.c_uint, _p]),
+    "st_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
 }
 
 _lib = None

@@ -1,6 +1,7 @@
 // Error plumbing, ABI version, and the small device-side pieces of the denoise
 // loop (Euler update, step counter, sinusoidal timestep features).
 #include "common.h"
+#include "philox.h"
 
 static thread_local char g_err[512] = "";
 
@@ -393,6 +394,162 @@ extern "C" int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, fl
     if (dtype == ST_F32)
         return dpm_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
     return st_fail("dpmpp2m_step: unsupported dtype %d", dtype);
+}
+
+// ---- stochastic samplers: Euler ancestral, DPM++ 2M SDE (scheduler.py docstring), with counter-based noise (philox.h) ------
+// The DPM++(2M) update plus one noise column.  Per sample b, i = *step, coef row i = [sigma, a, bb, k, c], all in fp32:
+//   e, d = x - sigma * e and x = a * x + bb * (...) exactly as dpmpp2m_kernel (same first-order branch on *start and k)
+//   x += c * z    only when c != 0 (a branch: the last step and eta = 0 never run the generator, and then every bit is
+//                 dpmpp2m_kernel's); z = the stream of seeds[b] at counter word i + 1, element j of the sample
+//   history = d;  next_in row b (and B + b when guided) = x * in_scale[min(i + 1, n - 1)]
+// With guidance the noise belongs to latent sample b (B seeds), not to the 2B UNet rows.  A lane's 8 values start at a
+// multiple of 8: exactly the two Philox calls q = j / 4 and j / 4 + 1.
+template <typename T, bool GUIDED, bool RESCALE>
+__global__ __launch_bounds__(CFG_THREADS) void sde_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
+                                                          float* __restrict__ history, const float* __restrict__ coef,
+                                                          const float* __restrict__ in_scale, const float* __restrict__ guidance,
+                                                          const float* __restrict__ rescale, const int* __restrict__ step,
+                                                          const int* __restrict__ start, const unsigned long long* __restrict__ seeds,
+                                                          int batch, long per_sample, int n_steps, const double* __restrict__ ws) {
+    const int b = blockIdx.y, i = *step;
+    float ratio = 1.f, phi = 0.f;
+    if constexpr (RESCALE) {
+        ratio = cfg_rescale_ratio(ws, b, per_sample);
+        phi = rescale[i];
+    }
+    const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
+    if (j >= per_sample) return;
+    const float sigma = coef[5 * i], a = coef[5 * i + 1], bb = coef[5 * i + 2], k = coef[5 * i + 3], c = coef[5 * i + 4];
+    const bool second = i != *start && k != 0.f;
+    const float sc = in_scale[i + 1 < n_steps ? i + 1 : n_steps - 1];
+    float e[8];
+    if constexpr (GUIDED) {
+        float pos[8];
+        cfg_guided8(eps, batch, b, per_sample, j, guidance[i], e, pos);
+        if constexpr (RESCALE) {
+            const float keep = 1.f - phi;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) e[q] = phi * (e[q] * ratio) + keep * e[q];   // phi = 0: the plain path's bits
+        }
+    } else {
+        cfg_load8(eps + (long)b * per_sample + j, e);
+    }
+    float* lat = latent + (long)b * per_sample + j;
+    float* hist = history + (long)b * per_sample + j;
+    float x[8], d[8], y[8], z[8];
+    cfg_load8(lat, x);
+    const bool noisy = c != 0.f;
+    if (noisy) {                 // drawn before the loaded values are first used: the loads above are in flight meanwhile
+        const PhiloxKey key = philox_key(seeds[b]);
+        const unsigned q0 = (unsigned)(j >> 2), ctr = (unsigned)(i + 1);
+        philox_normal4(key, q0, ctr, z);
+        philox_normal4(key, q0 + 1u, ctr, z + 4);
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) d[q] = x[q] - sigma * e[q];
+    if (second) {
+        float prev[8];
+        cfg_load8(hist, prev);
+        const float kp = 1.f + k;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = a * x[q] + bb * (kp * d[q] - k * prev[q]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = a * x[q] + bb * d[q];
+    }
+    if (noisy) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) x[q] = x[q] + c * z[q];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) y[q] = x[q] * sc;
+    cfg_store8(hist, d);
+    cfg_store8(lat, x);
+    cfg_store8(next_in + (long)b * per_sample + j, y);
+    if constexpr (GUIDED) cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+}
+
+template <typename T>
+static int sde_launch(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                      const float* guidance, const float* rescale, const int* step, const int* start,
+                      const unsigned long long* seeds, int batch, long per_sample, int n_steps, double* ws, hipStream_t st) {
+    const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (rescale) {
+        hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
+        if (st_check_launch("sde_step (statistics)")) return 1;
+        hipLaunchKernelGGL((sde_kernel<T, true, true>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                           coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)ws);
+    } else if (guidance) {
+        hipLaunchKernelGGL((sde_kernel<T, true, false>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                           coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)nullptr);
+    } else {
+        hipLaunchKernelGGL((sde_kernel<T, false, false>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                           coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)nullptr);
+    }
+    return st_check_launch("sde_step");
+}
+
+// the generator's counter word is 32 bits: a sample holds at most 4 * 2^32 values
+constexpr long PHILOX_MAX_PER_SAMPLE = 4L << 32;
+
+extern "C" int st_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                           const float* guidance, const float* rescale, const int* step, const int* start,
+                           const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start && seeds, "sde_step: null pointer");
+    ST_REQUIRE(!rescale || guidance, "sde_step: a rescale table needs a guidance table");
+    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "sde_step: bad sizes (batch %d, per_sample %ld, n_steps %d)",
+               batch, per_sample, n_steps);
+    ST_REQUIRE(per_sample % CFG_VEC == 0, "sde_step: per_sample %ld is not a multiple of %d (16-byte vectors)", per_sample, CFG_VEC);
+    ST_REQUIRE(per_sample <= PHILOX_MAX_PER_SAMPLE, "sde_step: per_sample %ld exceeds the generator's %ld values per sample",
+               per_sample, PHILOX_MAX_PER_SAMPLE);
+    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "sde_step: grid too large");
+    ST_REQUIRE((uintptr_t)latent % 16 == 0 && (uintptr_t)eps % 16 == 0 && (uintptr_t)next_in % 16 == 0 && (uintptr_t)history % 16 == 0,
+               "sde_step: latent, eps, next_in and history must be 16-byte aligned");
+    ST_REQUIRE((uintptr_t)seeds % 8 == 0, "sde_step: seeds must be 8-byte aligned");
+    if (rescale) {
+        const size_t need = st_cfg_step_workspace_bytes(batch, per_sample);
+        ST_REQUIRE(workspace && workspace_bytes >= need, "sde_step: the rescale path needs a workspace of %zu bytes, got %zu",
+                   need, workspace ? workspace_bytes : (size_t)0);
+        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "sde_step: workspace must be 16-byte aligned");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    double* ws = (double*)workspace;
+    if (dtype == ST_BF16)
+        return sde_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, ws, st);
+    if (dtype == ST_F16)
+        return sde_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, ws, st);
+    if (dtype == ST_F32)
+        return sde_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, ws, st);
+    return st_fail("sde_step: unsupported dtype %d", dtype);
+}
+
+// out[b][4q .. 4q + 3] = the stream of seeds[b] at counter word ctr, one Philox call (16-byte store) per lane
+__global__ __launch_bounds__(256) void philox_normal_kernel(float* __restrict__ out, const unsigned long long* __restrict__ seeds,
+                                                            long per_sample, unsigned ctr) {
+    const int b = blockIdx.y;
+    const long q = (long)blockIdx.x * 256 + threadIdx.x;
+    if (4 * q >= per_sample) return;
+    float z[4];
+    philox_normal4(philox_key(seeds[b]), (unsigned)q, ctr, z);
+    f32x4 v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = z[k];
+    *reinterpret_cast<f32x4*>(out + (long)b * per_sample + 4 * q) = v;
+}
+
+extern "C" int st_philox_normal(float* out, const unsigned long long* seeds, int batch, long per_sample, unsigned counter, void* stream) {
+    ST_REQUIRE(out && seeds, "philox_normal: null pointer");
+    ST_REQUIRE(batch > 0 && per_sample > 0, "philox_normal: bad sizes (batch %d, per_sample %ld)", batch, per_sample);
+    ST_REQUIRE(per_sample % 4 == 0, "philox_normal: per_sample %ld is not a multiple of 4 (one Philox call per 4 values)", per_sample);
+    ST_REQUIRE(per_sample <= PHILOX_MAX_PER_SAMPLE, "philox_normal: per_sample %ld exceeds the generator's %ld values per sample",
+               per_sample, PHILOX_MAX_PER_SAMPLE);
+    ST_REQUIRE(batch <= 65535 && (per_sample / 4 + 255) / 256 <= 0x7fffffffL, "philox_normal: grid too large");
+    ST_REQUIRE((uintptr_t)out % 16 == 0, "philox_normal: out must be 16-byte aligned");
+    ST_REQUIRE((uintptr_t)seeds % 8 == 0, "philox_normal: seeds must be 8-byte aligned");
+    const dim3 grid((unsigned)((per_sample / 4 + 255) / 256), (unsigned)batch);
+    hipLaunchKernelGGL(philox_normal_kernel, grid, dim3(256), 0, (hipStream_t)stream, out, seeds, per_sample, counter);
+    return st_check_launch("philox_normal");
 }
 
 __global__ void step_advance_kernel(int* step, int n_steps) {

@@ -1239,6 +1239,71 @@ def dpmpp2m_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor,
              "dpmpp2m_step")
 
 
+def _check_seeds(seeds: torch.Tensor, b: int, what: str) -> None:
+    if seeds.dtype != torch.int64 or seeds.dim() != 1 or seeds.numel() != b or not seeds.is_contiguous():
+        raise BackendError(f"{what}: seeds must be a contiguous int64 device table of B = {b} seeds; got "
+                           f"{seeds.dtype} {tuple(seeds.shape)}")
+
+
+def philox_normal(out: torch.Tensor, seeds: torch.Tensor, counter: int) -> None:
+    """In place: out (B, ...) fp32, dense, gets per sample b the counter-based N(0, 1) stream of seeds[b] (int64, the
+    seed's 64 bits) at counter word `counter`, in memory order within the sample (rng.py states it and restates it)."""
+    _C.require_device(out, seeds)
+    if out.dtype != torch.float32:
+        raise BackendError("philox_normal: out must be fp32")
+    if not (out.is_contiguous() or out.is_contiguous(memory_format=torch.channels_last)):
+        raise BackendError("philox_normal: out must be dense (contiguous or channels_last)")
+    b = out.shape[0]
+    _check_seeds(seeds, b, "philox_normal")
+    if not 0 <= int(counter) <= 0xFFFFFFFF:
+        raise BackendError(f"philox_normal: counter {counter} is not a 32-bit word")
+    _C.check(_C.load().st_philox_normal(out.data_ptr(), seeds.data_ptr(), b, out[0].numel(), int(counter), _C.stream_ptr()),
+             "philox_normal")
+
+
+def sde_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, history: torch.Tensor, coef: torch.Tensor,
+             in_scale: torch.Tensor, step: torch.Tensor, start: torch.Tensor, seeds: torch.Tensor,
+             guidance: Optional[torch.Tensor] = None, rescale: Optional[torch.Tensor] = None,
+             workspace: Optional[torch.Tensor] = None) -> None:
+    """In place, the stochastic update (Euler ancestral, DPM++ 2M SDE; scheduler.py): dpmpp2m_step with coef rows
+    [sigma, a, b, k, c] and, when c != 0, + c z, z the philox_normal stream of seeds[b] at counter word *step + 1.
+    seeds: int64 (B,) on the device, one per latent sample (also when guided)."""
+    _C.require_device(latent, eps, next_in, history, coef, in_scale, step, start, seeds, guidance, rescale, workspace)
+    lib = _C.load()
+    if latent.dtype != torch.float32 or history.dtype != torch.float32 or eps.dtype != next_in.dtype:
+        raise BackendError("sde_step: latent and history must be fp32 and eps/next_in share a dtype")
+    if not (latent.is_contiguous() or latent.is_contiguous(memory_format=torch.channels_last)):
+        raise BackendError("sde_step: latent must be dense (contiguous or channels_last)")
+    if rescale is not None and guidance is None:
+        raise BackendError("sde_step: rescale needs guidance")
+    b = latent.shape[0]
+    rows = 2 * b if guidance is not None else b
+    if history.shape != latent.shape:
+        raise BackendError(f"sde_step: history must match the latent {tuple(latent.shape)}; got {tuple(history.shape)}")
+    if eps.shape != next_in.shape or eps.shape[0] != rows or eps.shape[1:] != latent.shape[1:]:
+        what = "(2B, ...)" if guidance is not None else "(B, ...)"
+        raise BackendError(f"sde_step: eps and next_in must be {what} = {(rows, *latent.shape[1:])} for a latent of "
+                           f"{tuple(latent.shape)}; got {tuple(eps.shape)} and {tuple(next_in.shape)}")
+    if not (latent.stride() == history.stride() == eps.stride() == next_in.stride()):
+        raise BackendError("sde_step: latent, history, eps and next_in must share one dense layout")
+    n = in_scale.numel()
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 5) or not coef.is_contiguous():
+        raise BackendError(f"sde_step: coef must be a contiguous fp32 (n_steps, 5) = ({n}, 5) table")
+    for name, t in (("in_scale", in_scale), ("guidance", guidance), ("rescale", rescale)):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise BackendError(f"sde_step: {name} must be a contiguous fp32 table of n_steps = {n} values")
+    if step.dtype != torch.int32 or start.dtype != torch.int32:
+        raise BackendError("sde_step: step and start must be int32")
+    _check_seeds(seeds, b, "sde_step")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(lib.st_sde_step(latent.data_ptr(), eps.data_ptr(), next_in.data_ptr(), history.data_ptr(), coef.data_ptr(),
+                             in_scale.data_ptr(), _ptr(guidance), _ptr(rescale), step.data_ptr(), start.data_ptr(),
+                             seeds.data_ptr(), b, latent[0].numel(), n, _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes,
+                             _C.stream_ptr()), "sde_step")
+
+
 def step_advance(step: torch.Tensor, n_steps: int) -> None:
     _C.require_device(step)
     _C.check(_C.load().st_step_advance(step.data_ptr(), n_steps, _C.stream_ptr()), "step_advance")

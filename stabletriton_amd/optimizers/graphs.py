@@ -12,7 +12,9 @@ static device buffers on every call.
 """
 from __future__ import annotations
 
+import contextlib
 import functools
+import gc
 import logging
 import threading
 from typing import Any, Callable
@@ -23,6 +25,22 @@ logger = logging.getLogger(__name__)
 
 _pools = {}
 _pools_lock = threading.Lock()
+
+
+@contextlib.contextmanager
+def no_gc_during_capture():
+    """Keep Python's cyclic garbage collector out of a stream capture.  A dead reference cycle that holds GPU objects (an
+    earlier graph, its buffers) is freed when the collector happens to run, and its HIP calls are not allowed while the
+    stream captures: collected inside a capture, they abort the process.  Collect before the capture, and hold the
+    collector off until it ends (torch.cuda.graph no longer collects by itself)."""
+    gc.collect()
+    enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if enabled:
+            gc.enable()
 
 
 def _pool_for(device_index: int):
@@ -101,7 +119,7 @@ class GraphedCallable:
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, pool=_pool_for(dev.index)):
+            with no_gc_during_capture(), torch.cuda.graph(self.graph, pool=_pool_for(dev.index)):
                 self.static_out = fn(*self.static_in[0], **self.static_in[1])
 
     def __call__(self, *args, **kwargs):

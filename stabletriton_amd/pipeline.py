@@ -22,20 +22,29 @@ solver carries the previous step's prediction of the clean latent in a static fp
 `start` marks the step a trajectory starts from (0 after set_noise, t_start after set_image): that step is first-order and
 does not read the history.  Both, with the coefficient table, are read by address from the captured graph.  The solver
 follows from the type of the tables; Euler tables keep the Euler update and its buffers.
+
+With `SDETables` (scheduler.euler_ancestral_tables, dpmpp_2m_sde_tables) the update is `st_sde_step`: the DPM++ row plus
+fresh Gaussian noise on every step, drawn inside the kernel from a counter-based generator (rng.py) keyed by a device
+table of B 64-bit seeds and the step's schedule index.  Nothing is advanced between steps, so modes loop, step and eager
+draw the same noise and every replay repeats its bits.  `set_seed` writes the seeds in place (no new capture).  A seed
+also starts any sampler without a host tensor: `denoise(seed=s)` takes the initial noise from the same generator
+(counter word 0).  Euler and DPM++ loops allocate the seed table only when a seed is used, and their graph never reads it.
 """
 from __future__ import annotations
 
+import numbers
 from typing import Callable, Dict, Optional, Sequence, Union
 
 import torch
 
 from . import ops
-from .scheduler import DPMSolverTables, EulerTables, euler_discrete_tables
+from .optimizers.graphs import no_gc_during_capture
+from .scheduler import DPMSolverTables, EulerTables, SDETables, euler_discrete_tables
 
 
 class DenoiseLoop:
     def __init__(self, unet: Callable, batch: int, latent_hw, dtype: torch.dtype, device,
-                 tables: Optional[Union[EulerTables, DPMSolverTables]] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
+                 tables: Optional[Union[EulerTables, DPMSolverTables, SDETables]] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
                  tokens: int = 77, mode: str = "loop", n_time_ids: int = 6,
                  guidance_scale: Optional[Union[float, Sequence[float]]] = None,
                  guidance_rescale: Optional[Union[float, Sequence[float]]] = None):
@@ -60,9 +69,15 @@ class DenoiseLoop:
         self.time_ids = torch.zeros((rows, n_time_ids), dtype=dtype, device=dev)
         self.timesteps = torch.tensor(self.tables.timesteps, dtype=torch.float32, device=dev)
         # the update's tables: Euler reads dsigma; DPM-Solver++(2M) its coefficient rows, the previous step's clean-latent
-        # prediction (history) and the trajectory's start step
-        self.dsigma = self.coef = self.history = self.start = None
-        if isinstance(self.tables, DPMSolverTables):
+        # prediction (history) and the trajectory's start step; the stochastic samplers the same with a noise column and a
+        # device table of one 64-bit seed per sample (int64 holding the seed's bits)
+        self.dsigma = self.coef = self.history = self.start = self.seeds = None
+        if isinstance(self.tables, SDETables):
+            self.coef = torch.tensor(self.tables.coefficients(), dtype=torch.float32, device=dev)
+            self.history = torch.zeros_like(self.latent)
+            self.start = torch.zeros(1, dtype=torch.int32, device=dev)
+            self.seeds = torch.zeros(batch, dtype=torch.int64, device=dev)
+        elif isinstance(self.tables, DPMSolverTables):
             self.coef = torch.tensor(self.tables.coefficients(), dtype=torch.float32, device=dev)
             self.history = torch.zeros_like(self.latent)
             self.start = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -167,8 +182,46 @@ class DenoiseLoop:
         ectx = getattr(self.unet, "exec_context", None)
         return ectx.refresh_derived(full=True) if ectx is not None else 0
 
-    def set_noise(self, latent_unit: torch.Tensor) -> None:
-        """latent_unit ~ N(0,1); scaled by the scheduler's init sigma (fp32 state)."""
+    def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
+        """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
+        s + B - 1 (mod 2^64).  Written into the device table in place: a captured graph reads it by address."""
+        def integer(v) -> bool:
+            return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+
+        if integer(seed):
+            s0 = int(seed)
+            vals = [(s0 + b) % (1 << 64) if 0 <= s0 < 1 << 64 else s0 for b in range(self.batch)]
+        else:
+            try:
+                vals = list(seed)
+            except TypeError:
+                raise ValueError(f"set_seed: takes one int or B = {self.batch} ints, got {seed!r}") from None
+            if not all(integer(v) for v in vals):
+                raise ValueError(f"set_seed: seeds are integers, got {vals!r}")
+            vals = [int(v) for v in vals]
+        if len(vals) != self.batch:
+            raise ValueError(f"set_seed: takes one int or B = {self.batch} ints, got {len(vals)}")
+        if any(v < 0 or v >= 1 << 64 for v in vals):
+            raise ValueError("set_seed: seeds are 64-bit unsigned integers, in [0, 2^64)")
+        bits = torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
+        if self.seeds is None:                             # Euler / DPM++: only the initial noise reads the seeds
+            self.seeds = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
+        self.seeds.copy_(bits)
+
+    def _seeded_unit(self, counter: int) -> torch.Tensor:
+        z = torch.empty_like(self.latent)
+        ops.philox_normal(z, self.seeds, counter)
+        return z
+
+    def set_noise(self, latent_unit: Optional[torch.Tensor] = None, seed: Optional[Union[int, Sequence[int]]] = None) -> None:
+        """latent_unit ~ N(0,1); scaled by the scheduler's init sigma (fp32 state).  With `seed` the seeds are set first
+        (set_seed), and without latent_unit the unit noise is the generator's stream at counter word 0."""
+        if seed is not None:
+            self.set_seed(seed)
+        if latent_unit is None:
+            if seed is None:
+                raise ValueError("set_noise: pass latent_unit, seed, or both")
+            latent_unit = self._seeded_unit(0)
         self.latent.copy_(latent_unit.to(self.device, torch.float32) * self.tables.init_noise_sigma)
         self._write_input(float(self.tables.in_scale()[0]))
         self.step.zero_()
@@ -176,16 +229,24 @@ class DenoiseLoop:
             self.start.zero_()
         self._recalibrate(0)
 
-    def set_image(self, init_latent: torch.Tensor, noise_unit: torch.Tensor, strength: float) -> int:
+    def set_image(self, init_latent: torch.Tensor, noise_unit: Optional[torch.Tensor], strength: float,
+                  seed: Optional[Union[int, Sequence[int]]] = None) -> int:
         """img2img start (the refiner's use, BASELINE config #5; restated diffusers img2img: `get_timesteps` +
         `scheduler.add_noise`): skip the first n - int(n * strength) schedule entries, start from
-        init_latent + noise * sigma[t_start].  Returns the number of steps left to run (`run_steps(k)`, mode step / eager)."""
+        init_latent + noise * sigma[t_start].  Returns the number of steps left to run (`run_steps(k)`, mode step / eager).
+        With `seed` the seeds are set first, and noise_unit=None takes the generator's stream at counter word 0."""
         if self.mode == "loop":
             raise ValueError("set_image needs mode='step' or 'eager': the captured full-trajectory loop cannot start mid-schedule")
         n = self.n_steps
         t_start = max(n - min(int(n * strength), n), 0)
         if t_start >= n:
             raise ValueError(f"strength {strength} leaves no denoise step of the {n}-step schedule (int(n * strength) == 0)")
+        if seed is not None:
+            self.set_seed(seed)
+        if noise_unit is None:
+            if seed is None:
+                raise ValueError("set_image: pass noise_unit, seed, or both")
+            noise_unit = self._seeded_unit(0)
         sigma = float(self.tables.sigmas[t_start])
         lat = init_latent.to(self.device, torch.float32) + noise_unit.to(self.device, torch.float32) * sigma
         self.latent.copy_(lat)
@@ -240,7 +301,10 @@ class DenoiseLoop:
         ops.step_advance(self.step, self.n_steps)
 
     def _update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
-        if self.coef is not None:
+        if isinstance(self.tables, SDETables):
+            ops.sde_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+                         self.guidance, self.rescale, self.cfg_workspace)
+        elif self.coef is not None:
             ops.dpmpp2m_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.guidance,
                              self.rescale, self.cfg_workspace)
         elif self.guidance is None:
@@ -264,7 +328,7 @@ class DenoiseLoop:
         self._restore(keep)
         torch.cuda.synchronize(self.device)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with no_gc_during_capture(), torch.cuda.graph(g):
             if self.mode == "step":
                 self._step_counted()
                 self._captured_steps = 1
@@ -301,8 +365,9 @@ class DenoiseLoop:
             for _ in range(k):
                 self.graph.replay()
 
-    def denoise(self, latent_unit: torch.Tensor) -> torch.Tensor:
-        """Full trajectory: unit noise in, final fp32 latent (NCHW contiguous) out."""
-        self.set_noise(latent_unit)
+    def denoise(self, latent_unit: Optional[torch.Tensor] = None,
+                seed: Optional[Union[int, Sequence[int]]] = None) -> torch.Tensor:
+        """Full trajectory: unit noise (or a seed, set_noise) in, final fp32 latent (NCHW contiguous) out."""
+        self.set_noise(latent_unit, seed)
         self.run_steps(self.n_steps)
         return self.latent.contiguous(memory_format=torch.contiguous_format).clone()

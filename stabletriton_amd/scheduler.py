@@ -1,4 +1,5 @@
-"""Sampling tables for the denoise loop: Euler-discrete and DPM-Solver++(2M), with optional Karras sigmas.
+"""Sampling tables for the denoise loop: Euler-discrete, DPM-Solver++(2M), and the stochastic Euler ancestral and
+DPM++ 2M SDE, with optional Karras sigmas.
 
 The reference does not contain a scheduler: its 50-step loop is the
 third-party Diffusers SDXL pipeline (diffusers==0.21.2, requirements.txt:1;
@@ -23,6 +24,19 @@ lambda_i = -log sigma_i, h_i = lambda_{i+1} - lambda_i and e the (guided) eps of
     x_{i+1} = a_i x_i + b_i ((1 + k_i) d_i - k_i d_{i-1})
 A step is first-order when it is the first after the trajectory's start (step 0, or an img2img start) or the last one.
 The UNet input is x in_scale, as for Euler.  The loop keeps d_{i-1} in an fp32 history buffer between steps.
+
+Stochastic samplers (SDETables): the DPM++ row plus fresh Gaussian noise z_i on every step, one row form for both,
+    x_{i+1} = a_i x_i + b_i ((1 + k_i) d_i - k_i d_{i-1}) + c_i z_i          z_i ~ N(0, 1) per element
+with s = sigma_i, s' = sigma_{i+1}, eta (0: no noise) and s_noise (noise multiplier):
+  Euler ancestral (k-diffusion's `sample_euler_ancestral`, diffusers' EulerAncestralDiscreteScheduler):
+    sigma_up = min(s', eta sqrt(s'^2 (s^2 - s'^2) / s^2)),  sigma_down = sqrt(s'^2 - sigma_up^2)
+    a = sigma_down / s,  b = 1 - a,  k = 0,  c = s_noise sigma_up          i.e. x + (sigma_down - s) e + sigma_up z
+  DPM++ 2M SDE, midpoint (k-diffusion's `sample_dpmpp_2m_sde`, diffusers' algorithm_type="sde-dpmsolver++"):
+    a = (s'/s) exp(-eta h),  b = -expm1(-(1 + eta) h),  k = 1/(2 r) as for DPM++(2M) (0 on a first-order step),
+    c = s_noise s' sqrt(-expm1(-2 eta h))
+  Last row (s' = 0), both: [s, 0, 1, 0, 0], so x = d and no noise is drawn.
+With eta = 0 the DPM++ 2M SDE rows are the DPM++(2M) rows, bit for bit, with c = 0.  The noise z_i is the counter-based
+stream of rng.py at counter word i + 1 (i the absolute schedule index), keyed by the sample's seed.
 
 Diffusers versions discretise the timesteps differently: 0.21.2, which the reference pins, rounds t and ends the Karras
 schedule at sigma(t=0).  Parity with any diffusers version stays unpinned, as it already is for Euler.
@@ -81,6 +95,50 @@ class DPMSolverTables(_SigmaTables):
         return rows.astype(np.float32)
 
 
+@dataclass(frozen=True)
+class SDETables(_SigmaTables):
+    """Tables of a stochastic sampler: `sampler` is "euler_ancestral" or "dpmpp_2m_sde" (module docstring)."""
+    sampler: str = "dpmpp_2m_sde"
+    eta: float = 1.0
+    s_noise: float = 1.0
+
+    def __post_init__(self):
+        if self.sampler not in ("euler_ancestral", "dpmpp_2m_sde"):
+            raise ValueError(f"SDETables: unknown sampler {self.sampler!r} (euler_ancestral or dpmpp_2m_sde)")
+        if not self.eta >= 0.0 or not self.s_noise >= 0.0:
+            raise ValueError(f"SDETables: eta ({self.eta}) and s_noise ({self.s_noise}) must be >= 0")
+
+    def coefficients(self) -> np.ndarray:
+        """(n, 5) float32, one row [sigma_i, a_i, b_i, k_i, c_i] per step (module docstring), computed in float64 from the
+        stored sigmas.  The last row is [sigma, 0, 1, 0, 0]."""
+        s = self.sigmas.astype(np.float64)
+        n = self.n_steps
+        eta, s_noise = float(self.eta), float(self.s_noise)
+        rows = np.zeros((n, 5), dtype=np.float64)
+        lam = -np.log(s[:-1])                       # the expressions of DPMSolverTables.coefficients(): eta = 0 gives its bits
+        for i in range(n):
+            rows[i, 0] = s[i]
+            if i == n - 1 or s[i + 1] == 0.0:
+                rows[i, 1], rows[i, 2] = 0.0, 1.0
+                continue
+            if self.sampler == "euler_ancestral":
+                sc, sn = s[i], s[i + 1]
+                up = min(sn, eta * np.sqrt(sn * sn * (sc * sc - sn * sn) / (sc * sc)))
+                down = np.sqrt(sn * sn - up * up)
+                rows[i, 1] = down / sc
+                rows[i, 2] = 1.0 - rows[i, 1]
+                rows[i, 4] = s_noise * up
+                continue
+            h = lam[i + 1] - lam[i]
+            rows[i, 1] = s[i + 1] / s[i] * np.exp(-eta * h)
+            rows[i, 2] = -np.expm1(-(1.0 + eta) * h)
+            if i > 0:
+                r = (lam[i] - lam[i - 1]) / h
+                rows[i, 3] = 1.0 / (2.0 * r)
+            rows[i, 4] = s_noise * s[i + 1] * np.sqrt(-np.expm1(-2.0 * eta * h))
+        return rows.astype(np.float32)
+
+
 def training_sigmas(n_train: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012) -> np.ndarray:
     """float64 sigma of every training timestep t = 0 .. n_train - 1 (scaled-linear betas), increasing in t."""
     betas = np.linspace(beta_start ** 0.5, beta_end ** 0.5, n_train, dtype=np.float64) ** 2
@@ -123,3 +181,19 @@ def dpmpp_2m_tables(n_steps: int = 25, n_train: int = 1000, beta_start: float = 
     """DPM-Solver++(2M) tables: the timesteps, sigmas and init sigma of `euler_discrete_tables` with the same arguments."""
     e = euler_discrete_tables(n_steps, n_train, beta_start, beta_end, steps_offset, karras)
     return DPMSolverTables(e.timesteps, e.sigmas, e.init_noise_sigma)
+
+
+def euler_ancestral_tables(n_steps: int = 50, n_train: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                           steps_offset: int = 1, eta: float = 1.0, s_noise: float = 1.0, karras: bool = False) -> SDETables:
+    """Euler ancestral ("Euler a") tables: the timesteps, sigmas and init sigma of `euler_discrete_tables` with the same
+    arguments."""
+    e = euler_discrete_tables(n_steps, n_train, beta_start, beta_end, steps_offset, karras)
+    return SDETables(e.timesteps, e.sigmas, e.init_noise_sigma, "euler_ancestral", float(eta), float(s_noise))
+
+
+def dpmpp_2m_sde_tables(n_steps: int = 25, n_train: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                        steps_offset: int = 1, eta: float = 1.0, s_noise: float = 1.0, karras: bool = False) -> SDETables:
+    """DPM++ 2M SDE (midpoint) tables: the timesteps, sigmas and init sigma of `euler_discrete_tables` with the same
+    arguments."""
+    e = euler_discrete_tables(n_steps, n_train, beta_start, beta_end, steps_offset, karras)
+    return SDETables(e.timesteps, e.sigmas, e.init_noise_sigma, "dpmpp_2m_sde", float(eta), float(s_noise))

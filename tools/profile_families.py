@@ -39,8 +39,10 @@ def family(name: str):
         return "layer_norm"
     if "geglu_kernel" in name:
         return "geglu"
-    if ("euler_kernel" in name or "cfg_stats_kernel" in name or "dpmpp2m_kernel" in name or "step_advance" in name
-            or "timestep" in name):      # (cfg_euler_kernel: guided loop; dpmpp2m_kernel: the DPM-Solver++(2M) update)
+    if ("euler_kernel" in name or "cfg_stats_kernel" in name or "dpmpp2m_kernel" in name or "sde_kernel" in name
+            or "philox" in name or "step_advance" in name or "timestep" in name):
+        # (cfg_euler_kernel: guided loop; dpmpp2m_kernel: the DPM-Solver++(2M) update; sde_kernel: Euler ancestral and
+        #  DPM++ 2M SDE; philox_normal_kernel: a seeded start)
         return "loop"
     if "split_rows_kernel" in name:                # strict mode: the few matrix operands no producer could leave as a split image
         return "split_f32"
