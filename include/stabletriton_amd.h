@@ -55,8 +55,8 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               takes head_dim 16 / 32 / 128 beside 64; 15: st_timestep_features takes the host's table of the reference's own features for integer timesteps;
                                               16: next_weights_bytes carries the geometry of a strided touch in bits 40-61;
                                               17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, and then
-                                              st_sde_step and st_philox_normal, added without a bump: new entry points, no existing
-                                              signature or contract changed) */
+                                              st_sde_step and st_philox_normal, and then st_lora_merge, added without a bump: new entry
+                                              points, no existing signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -264,6 +264,27 @@ int st_philox_normal(float* out, const unsigned long long* seeds, int batch, lon
 int st_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
                 const float* guidance, const float* rescale, const int* step, const int* start, const unsigned long long* seeds,
                 int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+
+/* LoRA merge: one grouped launch rebuilds every adapted weight from its base snapshot (stabletriton_amd/lora.py owns the
+ * tables).  For every target t, elementwise over its row-major (N_t, K_t) weight of `dtype`:
+ *   W_t[n][k] = round( fp32(Base_t[n][k]) + sum_j scales[slot_j] * sum_r Up_tj[n][r] * DownT_tj[k][r] ),  fp32 throughout,
+ * written in place (W keeps its address).  All tables are on the device:
+ *   targets:  n_targets rows of 6 int64  [W, Base, N, K, first segment, segments]   (Base never aliases W);
+ *   segments: n_segments rows of 4 int64 [Up, DownT, padded rank rp, scale slot]: Up is (N, rp) and DownT - the down factor
+ *             TRANSPOSED - (K, rp), both row-major in `dtype`, 16-byte aligned, the ranks zero-padded to rp, a multiple of
+ *             32 (16-bit dtypes: one MFMA k) or of 4 (ST_F32), at most ST_LORA_MAX_RANK; alpha / rank is folded into Up
+ *             by the caller;
+ *             max_rank is the largest rp in the table (it sizes the kernel's LDS images; a larger segment is skipped);
+ *   tiles:    n_tiles rows of 2 int32 [target, tile]: one workgroup each, tile = row_tile * ceil(K / ST_LORA_TILE_K) +
+ *             column_tile over ST_LORA_TILE_N x ST_LORA_TILE_K tiles; a target is rebuilt where its tiles are listed;
+ *   scales:   n_scales floats, one slot per loaded adapter: changing a scale is a copy into this table and one launch.
+ * A segment whose scale is 0 is skipped, and a weight with no non-zero scale receives its base's bits.  16-byte accesses
+ * where K is a multiple of 16 bytes of elements and W / Base are 16-byte aligned, elementwise otherwise; N and K need not be
+ * tile multiples.  No atomics, nothing split over the rank: bitwise deterministic.  The tables' contents are the caller's
+ * contract (they cannot be checked from the host). */
+enum { ST_LORA_TILE_N = 64, ST_LORA_TILE_K = 128, ST_LORA_MAX_RANK = 128 };
+int st_lora_merge(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
+                  const int* tiles, long n_tiles, const float* scales, int n_scales, int dtype, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

@@ -61,6 +61,25 @@ class _HoistedUNet(nn.Module):
         self._ctx_copy.clear()
         return self.compiled.exec_context.refresh_derived(full=True)
 
+    # ---- LoRA adapters (lora.py): merged in place; the captured graphs stay, the hoisted K/V are projected again -------
+    def _lora_set(self):
+        from . import lora
+        return lora.attach(self.compiled)
+
+    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True):
+        """Merge a LoRA state dict (PEFT / diffusers / kohya keys) into the compiled UNet; returns the keys not applied."""
+        left = self._lora_set().load(name, state_dict, scale, strict)
+        self.refresh_weights()
+        return left
+
+    def set_lora_scale(self, name: str, scale: float) -> None:
+        self._lora_set().set_scale(name, scale)
+        self.refresh_weights()
+
+    def unload_lora(self, name: str) -> None:
+        self._lora_set().unload(name)
+        self.refresh_weights()
+
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
         version it had then.  A different object of the same shape (ComfyUI re-concatenates cond | uncond on every call) is
@@ -159,13 +178,23 @@ class DiffusersUNet(_HoistedUNet):
         for name, val in (("class_labels", class_labels), ("timestep_cond", timestep_cond), ("attention_mask", attention_mask)):
             if val is not None:
                 raise NotImplementedError(f"{name} is not part of the SDXL-base UNet path")
-        if cross_attention_kwargs:
-            # a pipeline with merged LoRA weights still passes {"scale": s}: scale 1 changes nothing once the weights are merged
-            # (`refresh_weights()` after the merge); anything else would need attention processors the compiled graph has not
+        loras = self.compiled.__dict__.get("_lora_set")
+        if loras is not None and loras.names():
+            # adapters loaded through load_lora: {"scale": s} is diffusers' global multiplier over all of them (1 when the
+            # pipeline passes none); a new value merges again, the same value costs nothing
+            kw = dict(cross_attention_kwargs or {})
+            scale = float(kw.pop("scale", 1.0))
+            if kw:
+                raise NotImplementedError(f"cross_attention_kwargs {sorted(kw)} (attention processors) are not supported")
+            if loras.set_global_scale(scale):
+                self.refresh_weights()
+        elif cross_attention_kwargs:
+            # a pipeline with merged LoRA weights still passes {"scale": s}: scale 1 changes nothing once the weights are merged;
+            # anything else would need attention processors the compiled graph has not
             extra = {k: v for k, v in cross_attention_kwargs.items() if not (k == "scale" and float(v) == 1.0)}
             if extra:
                 raise NotImplementedError(f"cross_attention_kwargs {sorted(extra)} (attention processors / a LoRA scale other than 1) are not "
-                                          "supported: merge the LoRA weights in place at the scale wanted and call refresh_weights()")
+                                          "supported: load the adapter with load_lora(name, state_dict, scale) and the scale is honoured")
         cd = self.compute_dtype
         cond = {"text_embeds": added_cond_kwargs["text_embeds"].to(cd), "time_ids": added_cond_kwargs["time_ids"].to(cd)}
         out = self._run(sample, timestep, encoder_hidden_states, cond)

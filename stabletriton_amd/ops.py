@@ -1307,3 +1307,79 @@ def sde_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, his
 def step_advance(step: torch.Tensor, n_steps: int) -> None:
     _C.require_device(step)
     _C.check(_C.load().st_step_advance(step.data_ptr(), n_steps, _C.stream_ptr()), "step_advance")
+
+
+# ---- LoRA merge (csrc/lora.hip): device tables for ONE grouped launch over every adapted weight ---------------------------
+LORA_MAX_RANK = 128
+
+
+def lora_rank_multiple(dtype: torch.dtype) -> int:
+    """Ranks are zero-padded (exactly) to the matrix instruction's k for 16-bit models, to a 16-byte vector for fp32."""
+    return 4 if dtype == torch.float32 else 32
+
+
+class LoraPlan:
+    """Descriptor table, segment table and flat tile list of one set of targets, on the device.  Built once per load / unload;
+    a scale change reuses it.  Holds every tensor the tables point at."""
+
+    def __init__(self, targets, segments, tiles, n_targets, n_segments, n_tiles, n_slots, max_rank, dtype, keep):
+        self.targets, self.segments, self.tiles = targets, segments, tiles
+        self.n_targets, self.n_segments, self.n_tiles, self.n_slots, self.max_rank = n_targets, n_segments, n_tiles, n_slots, max_rank
+        self.dtype, self.keep = dtype, keep
+
+
+def lora_plan(entries) -> LoraPlan:
+    """`entries`: one (weight, base, [(up, down_t, slot), ...]) per target.  weight / base: (N, K) contiguous, same dtype,
+    distinct storage; up: (N, rp), down_t: (K, rp) - the down factor transposed - contiguous in the weight's dtype with rp a
+    multiple of lora_rank_multiple(dtype) (zero padding).  A target with no factors is restored to its base by the launch."""
+    if not entries:
+        raise BackendError("lora_plan: no targets")
+    w0 = entries[0][0]
+    dtype, device = w0.dtype, w0.device
+    _C.dtype_code(dtype)
+    mult = lora_rank_multiple(dtype)
+    trows, srows, counts, keep, slots = [], [], [], [], 0
+    for w, base, factors in entries:
+        _C.require_device(w, base)
+        if w.dim() != 2 or not w.is_contiguous() or w.dtype != dtype or w.device != device:
+            raise BackendError(f"lora_plan: every weight must be a contiguous 2-D {dtype} tensor on {device}")
+        if base.shape != w.shape or base.dtype != dtype or base.device != device or not base.is_contiguous():
+            raise BackendError(f"lora_plan: a base must match its weight {tuple(w.shape)} {dtype}; got {tuple(base.shape)} {base.dtype}")
+        if base.data_ptr() == w.data_ptr():
+            raise BackendError("lora_plan: a base snapshot aliases its weight")
+        n, k = w.shape
+        trows.append([w.data_ptr(), base.data_ptr(), n, k, len(srows), len(factors)])
+        for up, down_t, slot in factors:
+            _C.require_device(up, down_t)
+            rp = up.shape[-1]
+            if (tuple(up.shape) != (n, rp) or tuple(down_t.shape) != (k, rp) or rp == 0 or rp % mult or up.dtype != dtype
+                    or down_t.dtype != dtype or not up.is_contiguous() or not down_t.is_contiguous()
+                    or up.data_ptr() % 16 or down_t.data_ptr() % 16 or up.device != device or down_t.device != device):
+                raise BackendError(f"lora_plan: factors of a {(n, k)} weight must be up ({n}, rp) and down_t ({k}, rp), contiguous "
+                                   f"{dtype}, rp a multiple of {mult}; got {tuple(up.shape)} {up.dtype} and {tuple(down_t.shape)} {down_t.dtype}")
+            if rp > LORA_MAX_RANK or slot < 0:
+                raise BackendError(f"lora_plan: padded rank {rp} (at most {LORA_MAX_RANK}) / scale slot {slot}")
+            srows.append([up.data_ptr(), down_t.data_ptr(), rp, slot])
+            slots = max(slots, slot + 1)
+            keep += [up, down_t]
+        counts.append(-(-n // _C.LORA_TILE_N) * -(-k // _C.LORA_TILE_K))
+        keep += [w, base]
+    cnt = torch.tensor(counts, dtype=torch.int64)
+    first = torch.cumsum(cnt, 0) - cnt
+    tgt = torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int64), cnt)
+    tiles = torch.stack([tgt, torch.arange(int(cnt.sum()), dtype=torch.int64) - first[tgt]], dim=1).to(torch.int32).contiguous()
+    segments = torch.tensor(srows, dtype=torch.int64).reshape(-1, 4).to(device) if srows else None
+    return LoraPlan(torch.tensor(trows, dtype=torch.int64).to(device), segments, tiles.to(device), len(trows), len(srows),
+                    tiles.shape[0], slots, max((r[2] for r in srows), default=0), dtype, keep)
+
+
+def lora_merge(plan: LoraPlan, scales: torch.Tensor) -> None:
+    """Rebuild every target of `plan` from its base: W = round(base + sum_j scales[slot_j] * up_j @ down_j), one launch.
+    Writes through raw pointers: the caller bumps the version counters of the rewritten parameters."""
+    _C.require_device(scales)
+    if scales.dtype != torch.float32 or not scales.is_contiguous() or scales.numel() < max(plan.n_slots, 1) or scales.device != plan.targets.device:
+        raise BackendError(f"lora_merge: scales must be a contiguous fp32 device table of at least {max(plan.n_slots, 1)} slots")
+    _C.check(_C.load().st_lora_merge(plan.targets.data_ptr(), plan.n_targets, _ptr(plan.segments), plan.n_segments, plan.max_rank,
+                                     plan.tiles.data_ptr(),
+                                     plan.n_tiles, scales.data_ptr(), scales.numel(), _C.dtype_code(plan.dtype), _C.stream_ptr()),
+             "lora_merge")

@@ -29,6 +29,10 @@ table of B 64-bit seeds and the step's schedule index.  Nothing is advanced betw
 draw the same noise and every replay repeats its bits.  `set_seed` writes the seeds in place (no new capture).  A seed
 also starts any sampler without a host tensor: `denoise(seed=s)` takes the initial noise from the same generator
 (counter word 0).  Euler and DPM++ loops allocate the seed table only when a seed is used, and their graph never reads it.
+
+LoRA adapters (`load_lora`, `set_lora_scale`, `unload_lora`; lora.py) are merged into the UNet's Linear weights in place by
+one grouped kernel launch.  The weights keep their addresses, so the captured graph stays; the loop re-derives, in place,
+what it had computed from them: derived weights, the hoisted text-context K/V and the time tables.
 """
 from __future__ import annotations
 
@@ -104,6 +108,7 @@ class DenoiseLoop:
         # schedule entry and the added conditioning: one table row per step, filled in set_conditioning
         self._tsplit = self._split and hasattr(unet, "precompute_time")
         self.time_tables = None
+        self._conditioned = False        # set_conditioning has filled the static conditioning buffers
 
     # ---- inputs --------------------------------------------------------------------------
     def set_guidance(self, scale: Union[float, Sequence[float]], rescale: Optional[Union[float, Sequence[float]]] = None) -> None:
@@ -151,6 +156,13 @@ class DenoiseLoop:
                     buf[:b].zero_()
                 else:
                     buf[:b].copy_(neg)
+        self._conditioned = True
+        self._rederive_conditioning()
+
+    def _rederive_conditioning(self) -> None:
+        """Everything the loop computes once per prompt from the weights and its own static `ehs`, `text_embeds` and
+        `time_ids` buffers, (re)computed IN PLACE: derived weights, the hoisted text-context K/V, the time tables.  Runs
+        after new conditioning and after a weight change (LoRA load / scale / unload); never needs a new capture."""
         self.refresh_weights()
         if self._split:
             with torch.no_grad():
@@ -181,6 +193,41 @@ class DenoiseLoop:
         weights between two runs of the same prompt."""
         ectx = getattr(self.unet, "exec_context", None)
         return ectx.refresh_derived(full=True) if ectx is not None else 0
+
+    # ---- LoRA adapters (lora.py): merged into the UNet's weights in place, no new capture ------------------------------
+    def _lora_set(self):
+        from . import lora
+        if not isinstance(self.unet, torch.nn.Module):
+            raise TypeError("LoRA adapters need the loop's unet to be a module (the result of optimize_model)")
+        return lora.attach(self.unet)
+
+    def _weights_changed(self) -> None:
+        """After a merge: the weights kept their addresses, so the captured graph stays; what was computed FROM them is
+        recomputed in place - derived weights always, the hoisted text K/V and the time tables once conditioning is set -
+        and under the fp8 plan the delayed scales are measured again, as at a trajectory start (set_noise)."""
+        if self._conditioned:
+            self._rederive_conditioning()
+            if getattr(self.unet, "fp8_plan", False):
+                self._recalibrate(int(self.step.item()) % self.n_steps)
+        else:
+            self.refresh_weights()
+
+    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True):
+        """Merge a LoRA state dict (PEFT / diffusers / kohya keys, lora.parse_lora_state_dict) into the UNet at `scale`.
+        Returns the keys that were not applied.  A loop that shares its UNet with another owner shares the adapters; the
+        other owner re-derives its own per-prompt state (its next set_conditioning does)."""
+        left = self._lora_set().load(name, state_dict, scale, strict)
+        self._weights_changed()
+        return left
+
+    def set_lora_scale(self, name: str, scale: float) -> None:
+        self._lora_set().set_scale(name, scale)
+        self._weights_changed()
+
+    def unload_lora(self, name: str) -> None:
+        """Remove an adapter; with none left every weight has its original bits again."""
+        self._lora_set().unload(name)
+        self._weights_changed()
 
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
