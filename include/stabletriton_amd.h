@@ -55,7 +55,8 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               takes head_dim 16 / 32 / 128 beside 64; 15: st_timestep_features takes the host's table of the reference's own features for integer timesteps;
                                               16: next_weights_bytes carries the geometry of a strided touch in bits 40-61;
                                               17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, and then
-                                              st_sde_step and st_philox_normal, and then st_lora_merge, added without a bump: new entry
+                                              st_sde_step and st_philox_normal, and then st_lora_merge, and then
+                                              st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, added without a bump: new entry
                                               points, no existing signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
@@ -373,6 +374,25 @@ int st_attention_split(const void* q, const void* ks, const void* vs, void* out,
  * kernels/timestep.py:13-45): x is fp32 of shape (..., half), n elements in all;
  *   sin_out[i] = sin(x[i] * f_j), cos_out[i] = cos(x[i] * f_j), j = i % half, f_j = exp(-ln(1e4) * j / half). */
 int st_timestep_sincos(const float* x, float* sin_out, float* cos_out, long n, int half, void* stream);
+
+/* FreeU at one decoder skip connection (csrc/freeu.hip; no reference counterpart: diffusers' enable_freeu / ComfyUI's FreeU nodes).
+ * h (N, H, W, C_h) is the running activation, skip (N, H, W, C_skip) the encoder tensor it is concatenated with; NHWC, dense,
+ * 16-byte aligned, channel counts multiples of 16 bytes, H and W >= 2.  params is a DEVICE row of five floats
+ * (b1, s1, b2, s2, version), read when the kernels run: slot 0 takes (b1, s1), slot 1 (b2, s2).  Out of place:
+ *   skip_out = skip with its four lowest spatial frequencies (bins {0, -1} x {0, -1}) scaled by s - the published
+ *              fourier_filter(threshold = 1) - as a rank-7 update from seven moments per plane, no FFT;
+ *   h_out    = h with channels [0, C_h / 2) times b (version 1) or times (b - 1) * mu_hat + 1 (version 2: mu = mean over all
+ *              channels, mu_hat = (mu - min) / (max - min) over the sample's H x W map, 0 where the map is constant).
+ * fp32 arithmetic, one rounding on output; s == 1 / b == 1 copy the bits.  Two launches, no atomics, fixed summation order.
+ * stat_rows = st_freeu_stat_rows(H * W) > 0: the apply launch also writes the GroupNorm partials of both outputs,
+ * (N * H * W / stat_rows, C, 2) floats each, in the form st_group_norm_from_stats[_cat] reads (rows = stat_rows);
+ * 0 (a shape it does not tile, or statistics not wanted): stats_h = stats_skip = NULL.
+ * workspace: st_freeu_workspace_bytes(N, C_skip, H * W) bytes, 16-byte aligned, not shared between concurrent launches. */
+size_t st_freeu_workspace_bytes(int N, int C_skip, long HW);
+int st_freeu_stat_rows(long HW);
+int st_freeu(const void* h, const void* skip, void* h_out, void* skip_out, int N, int C_h, int C_skip, int H, int W,
+             const float* params, int slot, int dtype, float* stats_h, float* stats_skip, int stat_rows,
+             void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,17 @@ class _HoistedUNet(nn.Module):
         self._lora_set().unload(name)
         self.refresh_weights()
 
+    # ---- FreeU (freeu.py): a device row the compiled graph reads by address; the captured graphs stay ------------------
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float, version: int = 1) -> None:
+        """diffusers' `UNet2DConditionModel.enable_freeu(s1, s2, b1, b2)`; version 2 = ComfyUI's FreeU_V2 backbone rule.
+        Raises on a wrapper compiled without `freeu=True` (the sites are part of the compiled graph)."""
+        from . import freeu
+        freeu.state_of(self.compiled, "enable_freeu").set(s1, s2, b1, b2, version)
+
+    def disable_freeu(self) -> None:
+        from . import freeu
+        freeu.state_of(self.compiled, "disable_freeu").disable()
+
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
         version it had then.  A different object of the same shape (ComfyUI re-concatenates cond | uncond on every call) is
@@ -205,24 +216,25 @@ class DiffusersUNet(_HoistedUNet):
 
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
-                                 cuda_graph: bool = True) -> DiffusersUNet:
+                                 cuda_graph: bool = True, freeu: bool = False) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
-    `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint)."""
+    `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
+    `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
         model = UNet2DConditionModel(spec)
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
-    compiled = optimize_model(model, cuda_graph=False)
+    compiled = optimize_model(model, cuda_graph=False, freeu=freeu)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
-def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True):
+def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
-    pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph)
+    pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu)
     return pipe
 
 
@@ -242,15 +254,16 @@ class ComfyUNet(_HoistedUNet):
         return self._run(x, timesteps, context, y.to(self.compute_dtype))
 
 
-def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True) -> ComfyUNet:
-    """Compile the `y`-vector entry of a UNet (weights shared with `unet`)."""
+def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False) -> ComfyUNet:
+    """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
+    `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node)."""
     dtype = next(unet.parameters()).dtype
-    compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False)
+    compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
-def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True) -> ComfyUNet:
+def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -1383,3 +1383,39 @@ def lora_merge(plan: LoraPlan, scales: torch.Tensor) -> None:
                                      plan.tiles.data_ptr(),
                                      plan.n_tiles, scales.data_ptr(), scales.numel(), _C.dtype_code(plan.dtype), _C.stream_ptr()),
              "lora_merge")
+
+
+# ----------------------------------------------------------------------------- FreeU
+def freeu(h: torch.Tensor, skip: torch.Tensor, params: torch.Tensor, slot: int):
+    """FreeU at one decoder skip connection (csrc/freeu.hip): h (N, C_h, H, W) the running activation, skip (N, C_s, H, W) the
+    tensor it is concatenated with, `params` the device row (b1, s1, b2, s2, version) of freeu.FreeU, `slot` 0 / 1 = which
+    (b, s) pair.  Returns (h', skip', ColStats of h' or None, ColStats of skip' or None): fresh channels_last tensors (the skip
+    tensor has other readers) and the GroupNorm partials of both, for `group_norm_from_stats_cat`.  Two launches."""
+    _C.require_device(h, skip, params)
+    lib = _C.load()
+    if h.dim() != 4 or skip.dim() != 4 or h.dtype != skip.dtype or h.shape[0] != skip.shape[0] or h.shape[2:] != skip.shape[2:]:
+        raise BackendError(f"freeu: h {tuple(h.shape)} {h.dtype} and skip {tuple(skip.shape)} {skip.dtype} must be (N, C, H, W) "
+                           "tensors of one dtype, batch and image size")
+    if params.dtype != torch.float32 or params.numel() != 5 or not params.is_contiguous():
+        raise BackendError("freeu: params must be a contiguous fp32 row (b1, s1, b2, s2, version)")
+    cl = torch.channels_last
+    if not h.is_contiguous(memory_format=cl):
+        h = h.contiguous(memory_format=cl)
+    if not skip.is_contiguous(memory_format=cl):
+        skip = skip.contiguous(memory_format=cl)
+    N, Ch, H, W = h.shape
+    Cs = skip.shape[1]
+    h_out = torch.empty((N, Ch, H, W), dtype=h.dtype, device=h.device, memory_format=cl)
+    s_out = torch.empty((N, Cs, H, W), dtype=h.dtype, device=h.device, memory_format=cl)
+    rows = lib.st_freeu_stat_rows(H * W)
+    st_h = st_s = None
+    if rows > 0:
+        tiles = N * H * W // rows
+        st_h = torch.empty((tiles, Ch, 2), dtype=torch.float32, device=h.device)
+        st_s = torch.empty((tiles, Cs, 2), dtype=torch.float32, device=h.device)
+    ws = torch.empty(lib.st_freeu_workspace_bytes(N, Cs, H * W), dtype=torch.uint8, device=h.device)
+    _C.check(lib.st_freeu(h.data_ptr(), skip.data_ptr(), h_out.data_ptr(), s_out.data_ptr(), N, Ch, Cs, H, W, params.data_ptr(), int(slot),
+                          _C.dtype_code(h.dtype), _ptr(st_h), _ptr(st_s), rows, ws.data_ptr(), ws.numel(), _C.stream_ptr()), "freeu")
+    if rows > 0:
+        return h_out, s_out, ColStats(st_h, rows, Ch), ColStats(st_s, rows, Cs)
+    return h_out, s_out, None, None

@@ -18,18 +18,22 @@ from torch import fx, nn
 from . import _C, ops
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_freeu, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
-                    gn_stats: bool = True) -> fx.GraphModule:
+                    gn_stats: bool = True, freeu: bool = False) -> fx.GraphModule:
     """Pass pipeline.  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
-    `xattn_fusion` / `gn_stats` switch two of the added fusions off (A/B measurements)."""
+    `xattn_fusion` / `gn_stats` switch two of the added fusions off (A/B measurements).  `freeu` (addition, off by default:
+    the graph is then exactly the one without it) puts a FreeU site in front of the decoder concatenations of the first two
+    stages and installs the neutral parameter state as `gm.freeu` (freeu.py)."""
     stats: Dict[str, int] = {}
+    if freeu:      # first: the readers of a concatenation still carry their module paths
+        stats["freeu_sites"] = insert_freeu(gm)
     stats["dropout"] = remove_dropout(gm)
     if fuse:
         stats["deduped_activations"] = dedupe_pure_calls(gm)
@@ -66,8 +70,10 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
     return replace_backend(gm)
 
 
-def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False) -> fx.GraphModule:
-    """`fp8=True` (addition, BASELINE config #5): the q|k|v, GEGLU and feed-forward output projections of a bf16 model's
+def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False) -> fx.GraphModule:
+    """`freeu=True` (addition): the compiled module carries FreeU sites and `gm.freeu`, their parameter state, neutral until
+    `gm.freeu.set(s1, s2, b1, b2, version)` (freeu.py; in-place, no new capture).
+    `fp8=True` (addition, BASELINE config #5): the q|k|v, GEGLU and feed-forward output projections of a bf16 model's
     transformer blocks run with OCP e4m3 operands on the fp8 matrix pipe, fed by e4m3 copies their producers' epilogues
     leave under delayed per-tensor scales (optimizers/plan_fp8.py); everything else is unchanged."""
     # same preconditions as the reference (optimization.py:29-33), for ROCm
@@ -85,7 +91,7 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     model = model.eval().to(memory_format=torch.channels_last)      # conv weights -> (Cout,R,S,Cin) strides
     if fp8 and p0.dtype != torch.bfloat16:
         raise RuntimeError("fp8 projections need a bfloat16 model")
-    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8)
+    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

@@ -16,6 +16,7 @@ from typing import List, Optional
 import torch
 from torch import fx
 
+from ..freeu import freeu_wrapper
 from .wrappers import conv2d_wrapper, group_norm_stats_wrapper, group_norm_wrapper, linear_residual_wrapper
 
 _VIEWS = ("reshape", "view", "permute", "contiguous")
@@ -36,12 +37,21 @@ def _can_emit(n: fx.Node) -> bool:
         return True
     if _is_fn(n, linear_residual_wrapper):
         return not (len(n.args) > 3 and n.args[3]) and not n.kwargs.get("emit_stats")
+    if _freeu_output(n):          # h' / r' of a FreeU site: the site always returns the partials of both (items 2 and 3)
+        return True
     return False
 
 
+def _freeu_output(n) -> bool:
+    return _is_fn(n, operator.getitem) and _is_fn(n.args[0], freeu_wrapper) and n.args[1] in (0, 1)
+
+
 def _producers(v: fx.Node) -> Optional[List[fx.Node]]:
-    """Producer nodes of the channel ranges of v, in channel order; None when some range has no emitting producer."""
+    """Producer nodes of the channel ranges of v, in channel order; None when some range has no emitting producer.
+    (A FreeU site produces two tensors: its `getitem` nodes stand for them.)"""
     v = _root(v)
+    if _freeu_output(v):
+        return [v]
     if _is_fn(v, operator.getitem) and v.args[1] == 0 and _can_emit(v.args[0]) and v.args[0].kwargs.get("emit_colstats"):
         return [v.args[0]]
     if _can_emit(v):
@@ -58,6 +68,13 @@ def _producers(v: fx.Node) -> Optional[List[fx.Node]]:
 
 def _stats_of(gm: fx.GraphModule, prod: fx.Node) -> fx.Node:
     """The statistics output of a producer, switching it to (out, stats) form on first use."""
+    if _freeu_output(prod):
+        site, want = prod.args[0], prod.args[1] + 2
+        for u in site.users:
+            if _is_fn(u, operator.getitem) and u.args[1] == want:
+                return u
+        with gm.graph.inserting_after(prod):
+            return gm.graph.call_function(operator.getitem, (site, want))
     if not prod.kwargs.get("emit_colstats"):
         prod.kwargs = {**prod.kwargs, "emit_colstats": True}
         with gm.graph.inserting_after(prod):

@@ -33,6 +33,9 @@ also starts any sampler without a host tensor: `denoise(seed=s)` takes the initi
 LoRA adapters (`load_lora`, `set_lora_scale`, `unload_lora`; lora.py) are merged into the UNet's Linear weights in place by
 one grouped kernel launch.  The weights keep their addresses, so the captured graph stays; the loop re-derives, in place,
 what it had computed from them: derived weights, the hoisted text-context K/V and the time tables.
+
+FreeU (`set_freeu`; freeu.py) is a device row of five floats the sites of a UNet compiled with `freeu=True` read by
+address: setting or clearing it is an in-place write, the captured graph stays.
 """
 from __future__ import annotations
 
@@ -228,6 +231,20 @@ class DenoiseLoop:
         """Remove an adapter; with none left every weight has its original bits again."""
         self._lora_set().unload(name)
         self._weights_changed()
+
+    def set_freeu(self, s1: Optional[float] = None, s2: Optional[float] = None, b1: Optional[float] = None,
+                  b2: Optional[float] = None, version: int = 1) -> None:
+        """FreeU parameters (freeu.py; diffusers' argument order; version 1 = diffusers, 2 = ComfyUI FreeU_V2), or
+        `set_freeu(None)` for neutral ones.  An in-place write of the device row the UNet's FreeU sites read: the next run
+        uses it without a new capture.  The UNet must have been compiled with `freeu=True`."""
+        from . import freeu
+        state = freeu.state_of(self.unet, "set_freeu")
+        if s1 is None:
+            if not (s2 is None and b1 is None and b2 is None):
+                raise ValueError("set_freeu: takes (s1, s2, b1, b2[, version]) or None")
+            state.disable()
+        else:
+            state.set(s1, s2, b1, b2, version)
 
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
