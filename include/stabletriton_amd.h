@@ -56,7 +56,8 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               16: next_weights_bytes carries the geometry of a strided touch in bits 40-61;
                                               17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, and then
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
-                                              st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, added without a bump: new entry
+                                              st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
+                                              st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, added without a bump: new entry
                                               points, no existing signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
@@ -393,6 +394,41 @@ int st_freeu_stat_rows(long HW);
 int st_freeu(const void* h, const void* skip, void* h_out, void* skip_out, int N, int C_h, int C_skip, int H, int W,
              const float* params, int slot, int dtype, float* stats_h, float* stats_skip, int stat_rows,
              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- perturbed-attention guidance (PAG; Ahn et al. 2024; no reference counterpart: diffusers' PAGMixin and
+ * PAGCFGIdentitySelfAttnProcessor2_0, ComfyUI's PerturbedAttentionGuidance node).
+ *
+ * st_attention_pag: st_attention whose LAST ident_count batch entries (0 <= ident_count <= B) are perturbed: their softmax matrix is
+ * the identity, so out = v for them (csrc/pag.hip).  ident_count > 0 needs T == S (self-attention).  Two launches at most: the
+ * unmodified attention kernels on the leading B - ident_count entries (the same pointers with a smaller B: those entries are
+ * bit-identical to st_attention on that sub-batch; skipped when there are none) and a strided row copy of ident_count * T rows of
+ * H * D values from row stride ldv to row stride ldo, 16-byte accesses, no atomics, nothing written outside those rows.  Every
+ * dtype and head size st_attention takes; all four pointers 16-byte aligned and all four strides multiples of 16 bytes of elements.
+ * An image armed by st_arm_split_output for the whole (B * T, H * D) fp32 output is completed by both launches: the attention launch
+ * writes the rows of its sub-batch, the copy the rows of the tail, bit-equal to st_split_f32 of the copied values. */
+int st_attention_pag(const void* q, const void* k, const void* v, void* out, int B, int T, int S, int H, int D,
+                     long ldq, long ldk, long ldv, long ldo, float scale, int dtype, int ident_count, void* stream);
+
+/* The three updates with a third noise prediction: st_cfg_euler_step, st_dpmpp2m_step and st_sde_step with one more device table
+ * `pag` of n_steps floats (never NULL) and one more row block of eps / next_in, the prediction under perturbed self-attention.
+ * With i = *step, s = pag[i]:
+ *   guidance != NULL: eps and next_in have 3*batch rows [negative | positive | perturbed],
+ *                     e = e_neg + guidance[i] * (e_pos - e_neg) + s * (e_pos - e_pert);
+ *   guidance == NULL: they have 2*batch rows [positive | perturbed], e = e_pos + s * (e_pos - e_pert); rescale must be NULL.
+ * Everything after e is the two-way entry point's arithmetic: the rescale of the total e against std(e_pos) through the same
+ * workspace, the row update, history, noise keyed by the latent sample; every row block of next_in receives the same values.
+ * The same kernels under a template flag: pag[i] == 0 gives the two-way entry point's latent and history bit for bit.  Alignment,
+ * per_sample % 8 == 0, workspace and determinism as there. */
+int st_pag_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
+                      const float* guidance, const float* rescale, const float* pag, const int* step, int batch, long per_sample,
+                      int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int st_pag_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                        const float* guidance, const float* rescale, const float* pag, const int* step, const int* start, int batch,
+                        long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int st_pag_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                    const float* guidance, const float* rescale, const float* pag, const int* step, const int* start,
+                    const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -125,28 +125,51 @@ __device__ __forceinline__ void cfg_store8(T* p, const float (&v)[8]) {
     }
 }
 
-// the guided eps of 8 values at offset j of sample b (also returns e_pos for the statistics)
-template <typename T>
-__device__ __forceinline__ void cfg_guided8(const T* __restrict__ eps, int batch, int b, long per_sample, long j, float g,
+// The PAG instantiations of the kernels below take one more argument, the `pag` table, as a parameter pack: the plain instantiations
+// keep the parameter list (and with it the kernel-argument layout and the code) they always had.
+__device__ __forceinline__ const float* pag_table() { return nullptr; }
+__device__ __forceinline__ const float* pag_table(const float* p) { return p; }
+
+// the guided eps of 8 values at offset j of sample b (also returns e_pos for the statistics).  PAG (perturbed-attention
+// guidance, below): one more row block [.. | perturbed] and e += s * (e_pos - e_pert); GUIDED = false (PAG only): rows
+// [positive | perturbed], e = e_pos + s * (e_pos - e_pert).  The plain instantiation <T> is the code it always was.
+template <typename T, bool PAG = false, bool GUIDED = true>
+__device__ __forceinline__ void cfg_guided8(const T* __restrict__ eps, int batch, int b, long per_sample, long j, float g, float s,
                                             float (&e)[8], float (&pos)[8]) {
-    float neg[8];
-    cfg_load8(eps + (long)b * per_sample + j, neg);
-    cfg_load8(eps + (long)(batch + b) * per_sample + j, pos);
+    static_assert(PAG || GUIDED, "cfg_guided8: nothing to combine");
+    if constexpr (GUIDED) {
+        float neg[8];
+        cfg_load8(eps + (long)b * per_sample + j, neg);
+        cfg_load8(eps + (long)(batch + b) * per_sample + j, pos);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) e[k] = neg[k] + g * (pos[k] - neg[k]);
+        for (int k = 0; k < 8; ++k) e[k] = neg[k] + g * (pos[k] - neg[k]);
+    } else {
+        cfg_load8(eps + (long)b * per_sample + j, pos);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) e[k] = pos[k];
+    }
+    if constexpr (PAG) {
+        float pert[8];
+        cfg_load8(eps + (long)((GUIDED ? 2 : 1) * batch + b) * per_sample + j, pert);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) e[k] = e[k] + s * (pos[k] - pert[k]);      // s = 0: + 0 * finite, the two-way value
+    }
 }
 
 // launch 1 (rescale only): ws[(b * nblk + blk) * 4 + {0..3}] = fp64 (sum e_pos, sum e_pos^2, sum e, sum e^2) over the block's values
-template <typename T>
+template <typename T, bool PAG = false, typename... Extra>
 __global__ __launch_bounds__(CFG_THREADS) void cfg_stats_kernel(const T* __restrict__ eps, const float* __restrict__ guidance,
                                                                 const int* __restrict__ step, int batch, long per_sample,
-                                                                double* __restrict__ ws) {
+                                                                double* __restrict__ ws, Extra... extra) {
+    const float* __restrict__ pag = pag_table(extra...);
     const int b = blockIdx.y;
     const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
     if (j < per_sample) {                        // per_sample % 8 == 0: a lane's 8 values are all inside or all outside
         float e[8], pos[8];
-        cfg_guided8(eps, batch, b, per_sample, j, guidance[*step], e, pos);
+        float s = 0.f;
+        if constexpr (PAG) s = pag[*step];
+        cfg_guided8<T, PAG>(eps, batch, b, per_sample, j, guidance[*step], s, e, pos);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const double p = pos[k], q = e[k];
@@ -193,12 +216,14 @@ __device__ __forceinline__ float cfg_rescale_ratio(const double* __restrict__ ws
 }
 
 // launch 2: guidance (+ rescale with the sample's ratio) + Euler update + both halves of the next UNet input
-template <typename T, bool RESCALE>
+template <typename T, bool RESCALE, bool PAG = false, bool GUIDED = true, typename... Extra>
 __global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
                                                                 const float* __restrict__ dsigma, const float* __restrict__ in_scale,
                                                                 const float* __restrict__ guidance, const float* __restrict__ rescale,
                                                                 const int* __restrict__ step, int batch, long per_sample, int n_steps,
-                                                                const double* __restrict__ ws) {
+                                                                const double* __restrict__ ws, Extra... extra) {
+    const float* __restrict__ pag = pag_table(extra...);
+    static_assert(GUIDED || !RESCALE, "guidance rescale needs classifier-free guidance");
     const int b = blockIdx.y, i = *step;
     float ratio = 1.f, phi = 0.f;
     if constexpr (RESCALE) {
@@ -207,10 +232,13 @@ __global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restric
     }
     const long j = (long)blockIdx.x * CFG_BLOCK_ELEMS + threadIdx.x * CFG_VEC;
     if (j >= per_sample) return;
-    const float g = guidance[i], ds = dsigma[i];
+    float g = 0.f, s = 0.f;
+    if constexpr (GUIDED) g = guidance[i];
+    if constexpr (PAG) s = pag[i];
+    const float ds = dsigma[i];
     const float sc = in_scale[i + 1 < n_steps ? i + 1 : n_steps - 1];
     float e[8], pos[8], x[8];
-    cfg_guided8(eps, batch, b, per_sample, j, g, e, pos);
+    cfg_guided8<T, PAG, GUIDED>(eps, batch, b, per_sample, j, g, s, e, pos);
     if constexpr (RESCALE) {
         const float keep = 1.f - phi;
 #pragma unroll
@@ -234,7 +262,8 @@ __global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restric
     *reinterpret_cast<f32x4*>(lat) = a;
     *reinterpret_cast<f32x4*>(lat + 4) = c;
     cfg_store8(next_in + (long)b * per_sample + j, y);
-    cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+    if constexpr (GUIDED) cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+    if constexpr (PAG) cfg_store8(next_in + (long)((GUIDED ? 2 : 1) * batch + b) * per_sample + j, y);      // every row block: the same values
 }
 
 extern "C" size_t st_cfg_step_workspace_bytes(int batch, long per_sample) {
@@ -244,8 +273,24 @@ extern "C" size_t st_cfg_step_workspace_bytes(int batch, long per_sample) {
 
 template <typename T>
 static int cfg_launch(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale, const float* guidance,
-                       const float* rescale, const int* step, int batch, long per_sample, int n_steps, double* ws, hipStream_t st) {
+                       const float* rescale, const float* pag, const int* step, int batch, long per_sample, int n_steps, double* ws,
+                       hipStream_t st) {
     const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (pag) {                                   // the three-way instantiations (st_pag_euler_step)
+        if (rescale) {
+            hipLaunchKernelGGL((cfg_stats_kernel<T, true, const float*>), grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws, pag);
+            if (st_check_launch("pag_euler_step (statistics)")) return 1;
+            hipLaunchKernelGGL((cfg_euler_kernel<T, true, true, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, dsigma,
+                               in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)ws, pag);
+        } else if (guidance) {
+            hipLaunchKernelGGL((cfg_euler_kernel<T, false, true, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, dsigma,
+                               in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)nullptr, pag);
+        } else {
+            hipLaunchKernelGGL((cfg_euler_kernel<T, false, true, false, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, dsigma,
+                               in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)nullptr, pag);
+        }
+        return st_check_launch("pag_euler_step");
+    }
     if (rescale) {
         hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
         if (st_check_launch("cfg_euler_step (statistics)")) return 1;
@@ -258,31 +303,56 @@ static int cfg_launch(float* latent, const void* eps, void* next_in, const float
     return st_check_launch("cfg_euler_step");
 }
 
-extern "C" int st_cfg_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
-                                 const float* guidance, const float* rescale, const int* step, int batch, long per_sample,
-                                 int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    ST_REQUIRE(latent && eps && next_in && dsigma && in_scale && guidance && step, "cfg_euler_step: null pointer");
-    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "cfg_euler_step: bad sizes (batch %d, per_sample %ld, n_steps %d)",
+// shared by st_cfg_euler_step (pag_entry false: `pag` is NULL, `guidance` required) and st_pag_euler_step
+static int cfg_euler_entry(const char* who, bool pag_entry, float* latent, const void* eps, void* next_in, const float* dsigma,
+                           const float* in_scale, const float* guidance, const float* rescale, const float* pag, const int* step,
+                           int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(latent && eps && next_in && dsigma && in_scale && (pag_entry ? pag != nullptr : guidance != nullptr) && step, "%s: null pointer", who);
+    ST_REQUIRE(!rescale || guidance, "%s: a rescale table needs a guidance table", who);
+    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "%s: bad sizes (batch %d, per_sample %ld, n_steps %d)", who,
                batch, per_sample, n_steps);
-    ST_REQUIRE(per_sample % CFG_VEC == 0, "cfg_euler_step: per_sample %ld is not a multiple of %d (16-byte vectors)", per_sample, CFG_VEC);
-    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "cfg_euler_step: grid too large");
+    ST_REQUIRE(per_sample % CFG_VEC == 0, "%s: per_sample %ld is not a multiple of %d (16-byte vectors)", who, per_sample, CFG_VEC);
+    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "%s: grid too large", who);
     ST_REQUIRE((uintptr_t)latent % 16 == 0 && (uintptr_t)eps % 16 == 0 && (uintptr_t)next_in % 16 == 0,
-               "cfg_euler_step: latent, eps and next_in must be 16-byte aligned");
+               "%s: latent, eps and next_in must be 16-byte aligned", who);
     if (rescale) {
         const size_t need = st_cfg_step_workspace_bytes(batch, per_sample);
-        ST_REQUIRE(workspace && workspace_bytes >= need, "cfg_euler_step: the rescale path needs a workspace of %zu bytes, got %zu",
+        ST_REQUIRE(workspace && workspace_bytes >= need, "%s: the rescale path needs a workspace of %zu bytes, got %zu", who,
                    need, workspace ? workspace_bytes : (size_t)0);
-        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "cfg_euler_step: workspace must be 16-byte aligned");
+        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     }
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
     if (dtype == ST_BF16)
-        return cfg_launch<bf16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
+        return cfg_launch<bf16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st);
     if (dtype == ST_F16)
-        return cfg_launch<f16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
+        return cfg_launch<f16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st);
     if (dtype == ST_F32)
-        return cfg_launch<float>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, ws, st);
-    return st_fail("cfg_euler_step: unsupported dtype %d", dtype);
+        return cfg_launch<float>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st);
+    return st_fail("%s: unsupported dtype %d", who, dtype);
+}
+
+extern "C" int st_cfg_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
+                                 const float* guidance, const float* rescale, const int* step, int batch, long per_sample,
+                                 int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    return cfg_euler_entry("cfg_euler_step", false, latent, eps, next_in, dsigma, in_scale, guidance, rescale, nullptr, step, batch,
+                           per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- perturbed-attention guidance (PAG; Ahn et al. 2024; restated diffusers PAGMixin) in the three updates ------------------
+// One more row block of eps / next_in, the UNet's prediction with the perturbed self-attention (csrc/pag.hip), and one more device
+// table `pag` of n_steps floats, s = pag[i]:
+//   guidance != NULL   rows [negative | positive | perturbed], 3 * batch:   e = e_neg + g * (e_pos - e_neg) + s * (e_pos - e_pert)
+//   guidance == NULL   rows [positive | perturbed], 2 * batch:              e = e_pos + s * (e_pos - e_pert)   (no rescale)
+// Everything after e is the arithmetic above and below, unchanged: the rescale statistics of the total e against e_pos through the
+// same workspace, the Euler / DPM++ / SDE row update, the history, the noise keyed by the latent sample; every row block of next_in
+// receives the same values.  The kernels are the existing ones with a PAG template flag (cfg_guided8, cfg_stats_kernel and the
+// three update kernels), so s = 0 gives the two-way kernels' latent and history bit for bit.
+extern "C" int st_pag_euler_step(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale,
+                                 const float* guidance, const float* rescale, const float* pag, const int* step, int batch,
+                                 long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    return cfg_euler_entry("pag_euler_step", true, latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch,
+                           per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
 }
 
 // ---- DPM-Solver++(2M) update (scheduler.py docstring; k-diffusion's sample_dpmpp_2m in sigma form) ----------------------
@@ -294,13 +364,14 @@ extern "C" int st_cfg_euler_step(float* latent, const void* eps, void* next_in, 
 //                                                 never reach the output)
 //   history = d;  next_in row b (and B + b when guided) = x * in_scale[min(i + 1, n - 1)]
 // The block mapping, the 16-byte vectors and the rescale statistics (cfg_stats_kernel, launch 1) are the CFG kernel's.
-template <typename T, bool GUIDED, bool RESCALE>
+template <typename T, bool GUIDED, bool RESCALE, bool PAG = false, typename... Extra>
 __global__ __launch_bounds__(CFG_THREADS) void dpmpp2m_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
                                                               float* __restrict__ history, const float* __restrict__ coef,
                                                               const float* __restrict__ in_scale, const float* __restrict__ guidance,
                                                               const float* __restrict__ rescale, const int* __restrict__ step,
                                                               const int* __restrict__ start, int batch, long per_sample, int n_steps,
-                                                              const double* __restrict__ ws) {
+                                                              const double* __restrict__ ws, Extra... extra) {
+    const float* __restrict__ pag = pag_table(extra...);
     const int b = blockIdx.y, i = *step;
     float ratio = 1.f, phi = 0.f;
     if constexpr (RESCALE) {
@@ -313,9 +384,11 @@ __global__ __launch_bounds__(CFG_THREADS) void dpmpp2m_kernel(float* __restrict_
     const bool second = i != *start && k != 0.f;
     const float sc = in_scale[i + 1 < n_steps ? i + 1 : n_steps - 1];
     float e[8];
-    if constexpr (GUIDED) {
-        float pos[8];
-        cfg_guided8(eps, batch, b, per_sample, j, guidance[i], e, pos);
+    if constexpr (GUIDED || PAG) {
+        float pos[8], g = 0.f, s = 0.f;
+        if constexpr (GUIDED) g = guidance[i];
+        if constexpr (PAG) s = pag[i];
+        cfg_guided8<T, PAG, GUIDED>(eps, batch, b, per_sample, j, g, s, e, pos);
         if constexpr (RESCALE) {
             const float keep = 1.f - phi;
 #pragma unroll
@@ -346,13 +419,29 @@ __global__ __launch_bounds__(CFG_THREADS) void dpmpp2m_kernel(float* __restrict_
     cfg_store8(lat, x);
     cfg_store8(next_in + (long)b * per_sample + j, y);
     if constexpr (GUIDED) cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+    if constexpr (PAG) cfg_store8(next_in + (long)((GUIDED ? 2 : 1) * batch + b) * per_sample + j, y);      // every row block: the same values
 }
 
 template <typename T>
 static int dpm_launch(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
-                      const float* guidance, const float* rescale, const int* step, const int* start, int batch, long per_sample,
-                      int n_steps, double* ws, hipStream_t st) {
+                      const float* guidance, const float* rescale, const float* pag, const int* step, const int* start, int batch,
+                      long per_sample, int n_steps, double* ws, hipStream_t st) {
     const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (pag) {                                   // the three-way instantiations (st_pag_dpmpp2m_step)
+        if (rescale) {
+            hipLaunchKernelGGL((cfg_stats_kernel<T, true, const float*>), grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws, pag);
+            if (st_check_launch("pag_dpmpp2m_step (statistics)")) return 1;
+            hipLaunchKernelGGL((dpmpp2m_kernel<T, true, true, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                               coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)ws, pag);
+        } else if (guidance) {
+            hipLaunchKernelGGL((dpmpp2m_kernel<T, true, false, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                               coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)nullptr, pag);
+        } else {
+            hipLaunchKernelGGL((dpmpp2m_kernel<T, false, false, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                               coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)nullptr, pag);
+        }
+        return st_check_launch("pag_dpmpp2m_step");
+    }
     if (rescale) {
         hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
         if (st_check_launch("dpmpp2m_step (statistics)")) return 1;
@@ -368,32 +457,50 @@ static int dpm_launch(float* latent, const void* eps, void* next_in, float* hist
     return st_check_launch("dpmpp2m_step");
 }
 
-extern "C" int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
-                               const float* guidance, const float* rescale, const int* step, const int* start, int batch,
-                               long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
-    ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start, "dpmpp2m_step: null pointer");
-    ST_REQUIRE(!rescale || guidance, "dpmpp2m_step: a rescale table needs a guidance table");
-    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "dpmpp2m_step: bad sizes (batch %d, per_sample %ld, n_steps %d)",
+// shared by st_dpmpp2m_step (pag_entry false: `pag` is NULL) and st_pag_dpmpp2m_step
+static int dpm_entry(const char* who, bool pag_entry, float* latent, const void* eps, void* next_in, float* history, const float* coef,
+                     const float* in_scale, const float* guidance, const float* rescale, const float* pag, const int* step,
+                     const int* start, int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes,
+                     void* stream) {
+    ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start && (!pag_entry || pag), "%s: null pointer", who);
+    ST_REQUIRE(!rescale || guidance, "%s: a rescale table needs a guidance table", who);
+    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "%s: bad sizes (batch %d, per_sample %ld, n_steps %d)", who,
                batch, per_sample, n_steps);
-    ST_REQUIRE(per_sample % CFG_VEC == 0, "dpmpp2m_step: per_sample %ld is not a multiple of %d (16-byte vectors)", per_sample, CFG_VEC);
-    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "dpmpp2m_step: grid too large");
+    ST_REQUIRE(per_sample % CFG_VEC == 0, "%s: per_sample %ld is not a multiple of %d (16-byte vectors)", who, per_sample, CFG_VEC);
+    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "%s: grid too large", who);
     ST_REQUIRE((uintptr_t)latent % 16 == 0 && (uintptr_t)eps % 16 == 0 && (uintptr_t)next_in % 16 == 0 && (uintptr_t)history % 16 == 0,
-               "dpmpp2m_step: latent, eps, next_in and history must be 16-byte aligned");
+               "%s: latent, eps, next_in and history must be 16-byte aligned", who);
     if (rescale) {
         const size_t need = st_cfg_step_workspace_bytes(batch, per_sample);
-        ST_REQUIRE(workspace && workspace_bytes >= need, "dpmpp2m_step: the rescale path needs a workspace of %zu bytes, got %zu",
+        ST_REQUIRE(workspace && workspace_bytes >= need, "%s: the rescale path needs a workspace of %zu bytes, got %zu", who,
                    need, workspace ? workspace_bytes : (size_t)0);
-        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "dpmpp2m_step: workspace must be 16-byte aligned");
+        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     }
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
     if (dtype == ST_BF16)
-        return dpm_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
+        return dpm_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st);
     if (dtype == ST_F16)
-        return dpm_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
+        return dpm_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st);
     if (dtype == ST_F32)
-        return dpm_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, ws, st);
-    return st_fail("dpmpp2m_step: unsupported dtype %d", dtype);
+        return dpm_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st);
+    return st_fail("%s: unsupported dtype %d", who, dtype);
+}
+
+extern "C" int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                               const float* guidance, const float* rescale, const int* step, const int* start, int batch,
+                               long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    return dpm_entry("dpmpp2m_step", false, latent, eps, next_in, history, coef, in_scale, guidance, rescale, nullptr, step, start, batch,
+                     per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
+}
+
+// st_dpmpp2m_step with the perturbed row block (st_pag_euler_step's comment states e)
+extern "C" int st_pag_dpmpp2m_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                                   const float* guidance, const float* rescale, const float* pag, const int* step, const int* start,
+                                   int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return dpm_entry("pag_dpmpp2m_step", true, latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch,
+                     per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
 }
 
 // ---- stochastic samplers: Euler ancestral, DPM++ 2M SDE (scheduler.py docstring), with counter-based noise (philox.h) ------
@@ -404,13 +511,15 @@ extern "C" int st_dpmpp2m_step(float* latent, const void* eps, void* next_in, fl
 //   history = d;  next_in row b (and B + b when guided) = x * in_scale[min(i + 1, n - 1)]
 // With guidance the noise belongs to latent sample b (B seeds), not to the 2B UNet rows.  A lane's 8 values start at a
 // multiple of 8: exactly the two Philox calls q = j / 4 and j / 4 + 1.
-template <typename T, bool GUIDED, bool RESCALE>
+template <typename T, bool GUIDED, bool RESCALE, bool PAG = false, typename... Extra>
 __global__ __launch_bounds__(CFG_THREADS) void sde_kernel(float* __restrict__ latent, const T* __restrict__ eps, T* __restrict__ next_in,
                                                           float* __restrict__ history, const float* __restrict__ coef,
                                                           const float* __restrict__ in_scale, const float* __restrict__ guidance,
                                                           const float* __restrict__ rescale, const int* __restrict__ step,
                                                           const int* __restrict__ start, const unsigned long long* __restrict__ seeds,
-                                                          int batch, long per_sample, int n_steps, const double* __restrict__ ws) {
+                                                          int batch, long per_sample, int n_steps, const double* __restrict__ ws,
+                                                          Extra... extra) {
+    const float* __restrict__ pag = pag_table(extra...);
     const int b = blockIdx.y, i = *step;
     float ratio = 1.f, phi = 0.f;
     if constexpr (RESCALE) {
@@ -423,9 +532,11 @@ __global__ __launch_bounds__(CFG_THREADS) void sde_kernel(float* __restrict__ la
     const bool second = i != *start && k != 0.f;
     const float sc = in_scale[i + 1 < n_steps ? i + 1 : n_steps - 1];
     float e[8];
-    if constexpr (GUIDED) {
-        float pos[8];
-        cfg_guided8(eps, batch, b, per_sample, j, guidance[i], e, pos);
+    if constexpr (GUIDED || PAG) {
+        float pos[8], g = 0.f, s = 0.f;
+        if constexpr (GUIDED) g = guidance[i];
+        if constexpr (PAG) s = pag[i];
+        cfg_guided8<T, PAG, GUIDED>(eps, batch, b, per_sample, j, g, s, e, pos);
         if constexpr (RESCALE) {
             const float keep = 1.f - phi;
 #pragma unroll
@@ -467,13 +578,29 @@ __global__ __launch_bounds__(CFG_THREADS) void sde_kernel(float* __restrict__ la
     cfg_store8(lat, x);
     cfg_store8(next_in + (long)b * per_sample + j, y);
     if constexpr (GUIDED) cfg_store8(next_in + (long)(batch + b) * per_sample + j, y);
+    if constexpr (PAG) cfg_store8(next_in + (long)((GUIDED ? 2 : 1) * batch + b) * per_sample + j, y);      // every row block: the same values
 }
 
 template <typename T>
 static int sde_launch(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
-                      const float* guidance, const float* rescale, const int* step, const int* start,
+                      const float* guidance, const float* rescale, const float* pag, const int* step, const int* start,
                       const unsigned long long* seeds, int batch, long per_sample, int n_steps, double* ws, hipStream_t st) {
     const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (pag) {                                   // the three-way instantiations (st_pag_sde_step)
+        if (rescale) {
+            hipLaunchKernelGGL((cfg_stats_kernel<T, true, const float*>), grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws, pag);
+            if (st_check_launch("pag_sde_step (statistics)")) return 1;
+            hipLaunchKernelGGL((sde_kernel<T, true, true, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                               coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)ws, pag);
+        } else if (guidance) {
+            hipLaunchKernelGGL((sde_kernel<T, true, false, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                               coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)nullptr, pag);
+        } else {
+            hipLaunchKernelGGL((sde_kernel<T, false, false, true, const float*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in, history,
+                               coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)nullptr, pag);
+        }
+        return st_check_launch("pag_sde_step");
+    }
     if (rescale) {
         hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
         if (st_check_launch("sde_step (statistics)")) return 1;
@@ -492,36 +619,54 @@ static int sde_launch(float* latent, const void* eps, void* next_in, float* hist
 // the generator's counter word is 32 bits: a sample holds at most 4 * 2^32 values
 constexpr long PHILOX_MAX_PER_SAMPLE = 4L << 32;
 
-extern "C" int st_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
-                           const float* guidance, const float* rescale, const int* step, const int* start,
-                           const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
-                           size_t workspace_bytes, void* stream) {
-    ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start && seeds, "sde_step: null pointer");
-    ST_REQUIRE(!rescale || guidance, "sde_step: a rescale table needs a guidance table");
-    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "sde_step: bad sizes (batch %d, per_sample %ld, n_steps %d)",
+// shared by st_sde_step (pag_entry false: `pag` is NULL) and st_pag_sde_step
+static int sde_entry(const char* who, bool pag_entry, float* latent, const void* eps, void* next_in, float* history, const float* coef,
+                     const float* in_scale, const float* guidance, const float* rescale, const float* pag, const int* step,
+                     const int* start, const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start && seeds && (!pag_entry || pag), "%s: null pointer", who);
+    ST_REQUIRE(!rescale || guidance, "%s: a rescale table needs a guidance table", who);
+    ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "%s: bad sizes (batch %d, per_sample %ld, n_steps %d)", who,
                batch, per_sample, n_steps);
-    ST_REQUIRE(per_sample % CFG_VEC == 0, "sde_step: per_sample %ld is not a multiple of %d (16-byte vectors)", per_sample, CFG_VEC);
-    ST_REQUIRE(per_sample <= PHILOX_MAX_PER_SAMPLE, "sde_step: per_sample %ld exceeds the generator's %ld values per sample",
+    ST_REQUIRE(per_sample % CFG_VEC == 0, "%s: per_sample %ld is not a multiple of %d (16-byte vectors)", who, per_sample, CFG_VEC);
+    ST_REQUIRE(per_sample <= PHILOX_MAX_PER_SAMPLE, "%s: per_sample %ld exceeds the generator's %ld values per sample", who,
                per_sample, PHILOX_MAX_PER_SAMPLE);
-    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "sde_step: grid too large");
+    ST_REQUIRE(cfg_blocks_per_sample(per_sample) <= 0x7fffffffL && batch <= 65535, "%s: grid too large", who);
     ST_REQUIRE((uintptr_t)latent % 16 == 0 && (uintptr_t)eps % 16 == 0 && (uintptr_t)next_in % 16 == 0 && (uintptr_t)history % 16 == 0,
-               "sde_step: latent, eps, next_in and history must be 16-byte aligned");
-    ST_REQUIRE((uintptr_t)seeds % 8 == 0, "sde_step: seeds must be 8-byte aligned");
+               "%s: latent, eps, next_in and history must be 16-byte aligned", who);
+    ST_REQUIRE((uintptr_t)seeds % 8 == 0, "%s: seeds must be 8-byte aligned", who);
     if (rescale) {
         const size_t need = st_cfg_step_workspace_bytes(batch, per_sample);
-        ST_REQUIRE(workspace && workspace_bytes >= need, "sde_step: the rescale path needs a workspace of %zu bytes, got %zu",
+        ST_REQUIRE(workspace && workspace_bytes >= need, "%s: the rescale path needs a workspace of %zu bytes, got %zu", who,
                    need, workspace ? workspace_bytes : (size_t)0);
-        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "sde_step: workspace must be 16-byte aligned");
+        ST_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     }
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
     if (dtype == ST_BF16)
-        return sde_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, ws, st);
+        return sde_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st);
     if (dtype == ST_F16)
-        return sde_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, ws, st);
+        return sde_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st);
     if (dtype == ST_F32)
-        return sde_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, ws, st);
-    return st_fail("sde_step: unsupported dtype %d", dtype);
+        return sde_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st);
+    return st_fail("%s: unsupported dtype %d", who, dtype);
+}
+
+extern "C" int st_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                           const float* guidance, const float* rescale, const int* step, const int* start,
+                           const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    return sde_entry("sde_step", false, latent, eps, next_in, history, coef, in_scale, guidance, rescale, nullptr, step, start, seeds, batch,
+                     per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
+}
+
+// st_sde_step with the perturbed row block (st_pag_euler_step's comment states e); the noise stays keyed by the latent sample
+extern "C" int st_pag_sde_step(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
+                               const float* guidance, const float* rescale, const float* pag, const int* step, const int* start,
+                               const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return sde_entry("pag_sde_step", true, latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch,
+                     per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
 }
 
 // out[b][4q .. 4q + 3] = the stream of seeds[b] at counter word ctr, one Philox call (16-byte store) per lane

@@ -52,6 +52,7 @@ class _HoistedUNet(nn.Module):
         self._steps: Dict[tuple, object] = {}     # ehs shape -> (graphed) step function
         self._new_prompt = False                  # set when a context was (re)projected: the fp8 plan measures its scales again
         self._last_t = None                       # fp8 plan only: the last call's (largest) timestep, to tell where a trajectory starts
+        self._pag_chunks = 0                      # enable_pag: the last B // chunks rows of a call are perturbed (0: none)
 
     def refresh_weights(self) -> int:
         """Re-derive fused / folded weight buffers after an in-place weight update (also done at every new prompt).
@@ -91,6 +92,28 @@ class _HoistedUNet(nn.Module):
         from . import freeu
         freeu.state_of(self.compiled, "disable_freeu").disable()
 
+    # ---- perturbed-attention guidance (pag.py): which rows of a call are the perturbed ones; one captured graph per setting ----
+    def enable_pag(self, chunks: int) -> None:
+        """The last B // chunks batch rows of every following call take the perturbed self-attention (out = v at the sites
+        compiled in with `pag_layers`): 3 for diffusers' PAG pipelines with guidance ([uncond | cond | cond]), 2 without
+        ([cond | cond]), 1 for a fully perturbed call (ComfyUI's PerturbedAttentionGuidance node).  Only the UNet is evaluated
+        here: the guidance combine stays with the calling pipeline.  Raises on a wrapper compiled without `pag_layers`."""
+        from . import pag
+        pag.state_of(self.compiled, "enable_pag")
+        if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 1:
+            raise ValueError(f"enable_pag: chunks must be a positive integer (3, 2 or 1), got {chunks!r}")
+        self._pag_chunks = chunks             # (the state's own `chunks` is set around this wrapper's calls only: _pag_scope)
+
+    def disable_pag(self) -> None:
+        from . import pag
+        pag.state_of(self.compiled, "disable_pag")
+        self._pag_chunks = 0
+
+    def _pag_scope(self, chunks: int):
+        import contextlib
+        state = getattr(self.compiled, "pag", None)
+        return state.using(chunks) if state is not None else contextlib.nullcontext()
+
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
         version it had then.  A different object of the same shape (ComfyUI re-concatenates cond | uncond on every call) is
@@ -123,8 +146,9 @@ class _HoistedUNet(nn.Module):
         if fn is None:
             ctx = self._ctx[shape]                 # closed over: the graph reads these buffers in place
 
-            def step(sample, timesteps, cond):
-                return self.compiled.forward_with_context(sample, timesteps, ctx, cond)[0]
+            def step(sample, timesteps, cond, pag_chunks=0):      # (a plain integer: part of the graph cache's key)
+                with self._pag_scope(pag_chunks):
+                    return self.compiled.forward_with_context(sample, timesteps, ctx, cond)[0]
 
             fn = make_dynamic_graphed_callable(step) if self.cuda_graph else step
             self._steps[shape] = fn
@@ -145,7 +169,10 @@ class _HoistedUNet(nn.Module):
         if start:
             from .optimization import recalibrate_fp8
             ctx = self._ctx[shape]
-            run_once = lambda: self.compiled.forward_with_context(x, timesteps, ctx, cond)
+            def run_once():
+                with self._pag_scope(self._pag_chunks):
+                    return self.compiled.forward_with_context(x, timesteps, ctx, cond)
+
             ectx = getattr(self.compiled, "exec_context", None)
             if ectx is not None and ectx.fp8 is None:
                 with torch.no_grad():
@@ -167,7 +194,10 @@ class _HoistedUNet(nn.Module):
             self._fp8_restart(x, timesteps, tuple(ehs.shape), cond)
         self._new_prompt = False
         with torch.no_grad():
-            out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond)
+            if self._pag_chunks:
+                out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond, self._pag_chunks)
+            else:
+                out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond)
         return out.to(io_dtype)
 
 
@@ -216,25 +246,27 @@ class DiffusersUNet(_HoistedUNet):
 
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
-                                 cuda_graph: bool = True, freeu: bool = False) -> DiffusersUNet:
+                                 cuda_graph: bool = True, freeu: bool = False, pag_layers=None) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
-    `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet."""
+    `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
+    `pag_layers=("mid",)` compiles the perturbed-attention sites in (diffusers' `pag_applied_layers`): `enable_pag(chunks)` /
+    `disable_pag()` then say which rows of a call are the perturbed ones."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
         model = UNet2DConditionModel(spec)
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
-    compiled = optimize_model(model, cuda_graph=False, freeu=freeu)
+    compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
-def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False):
+def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
-    pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu)
+    pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers)
     return pipe
 
 
@@ -254,16 +286,17 @@ class ComfyUNet(_HoistedUNet):
         return self._run(x, timesteps, context, y.to(self.compute_dtype))
 
 
-def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False) -> ComfyUNet:
+def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
-    `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node)."""
+    `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
+    perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`."""
     dtype = next(unet.parameters()).dtype
-    compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu)
+    compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
-def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False) -> ComfyUNet:
+def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph, freeu)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -971,6 +971,67 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int,
     return out
 
 
+def attention_pag(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float, ident_count: int) -> torch.Tensor:
+    """`attention` whose last `ident_count` batch entries are perturbed (PAG, csrc/pag.hip): their softmax matrix is the identity,
+    so their output rows are v's.  The leading entries go through the unmodified attention launch (the bits of `attention` on that
+    sub-batch), the tail is one strided row copy; ident_count = 0 is `attention` itself.  Strict mode: the output's split image is
+    completed by both launches (the copy writes the tail's image rows from the values it copies)."""
+    ident_count = int(ident_count)
+    if ident_count == 0:
+        return attention(q, k, v, num_heads, scale)
+    _C.require_device(q, k, v)
+    lib = _C.load()
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise BackendError("attention_pag expects (B, T, H*D) tensors")
+    B, T, Cc = q.shape
+    S = k.shape[1]
+    D = Cc // num_heads
+    if not 0 <= ident_count <= B:
+        raise BackendError(f"attention_pag: ident_count {ident_count} outside [0, B = {B}]")
+    if T != S or k.shape != q.shape or v.shape != q.shape:
+        raise BackendError(f"attention_pag: the identity tail needs self-attention shapes (T == S); got q {tuple(q.shape)}, "
+                           f"k {tuple(k.shape)}, v {tuple(v.shape)}")
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    q_, ldq = tok(q)
+    k_, ldk = tok(k)
+    v_, ldv = tok(v)
+    lead = B - ident_count
+    es = q.element_size()
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    img = torch.empty((B * T, Cc), dtype=torch.float32, device=q.device) if (EMIT_SPLIT and split_usable(out.dtype, Cc)) else None
+    ki = _image_columns(k_, B * S, ldk) if q.dtype == torch.float32 else None      # strict mode: K / V columns of a producer's split image
+    vi = _image_columns(v_, B * S, ldv) if ki is not None else None
+    code, st = _C.dtype_code(q.dtype), _C.stream_ptr()
+
+    def arm(first_row: int, rows: int):
+        if img is not None:
+            _C.check(lib.st_arm_split_output(img.data_ptr() + 4 * first_row * Cc, rows, Cc), "arm_split_output")
+
+    with _Armed(img):
+        if ki is not None and vi is not None and D == 64:
+            # the split-image attention on the leading sub-batch (the images' leading rows), then the tail alone
+            if lead > 0:
+                arm(0, lead * T)
+                _C.check(lib.st_attention_split(q_.data_ptr(), ki[0].data_ptr() + 4 * ki[1], vi[0].data_ptr() + 4 * vi[1], out.data_ptr(), lead, T, S,
+                                                num_heads, D, ldq, ki[0].shape[1], vi[0].shape[1], Cc, float(scale), st), "attention_split")
+            arm(lead * T, ident_count * T)
+            _C.check(lib.st_attention_pag(q_.data_ptr() + es * lead * T * ldq, k_.data_ptr() + es * lead * S * ldk, v_.data_ptr() + es * lead * S * ldv,
+                                          out.data_ptr() + es * lead * T * Cc, ident_count, T, S, num_heads, D, ldq, ldk, ldv, Cc, float(scale),
+                                          code, ident_count, st), "attention_pag")
+        else:
+            arm(0, B * T)
+            _C.check(lib.st_attention_pag(q_.data_ptr(), k_.data_ptr(), v_.data_ptr(), out.data_ptr(), B, T, S, num_heads, D, ldq, ldk, ldv, Cc,
+                                          float(scale), code, ident_count, st), "attention_pag")
+    _note_split(out, img, B * T, Cc)
+    return out
+
+
 # ----------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int, *,
            upsample2x: bool = False, rowbias: Optional[torch.Tensor] = None,
@@ -1302,6 +1363,92 @@ def sde_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, his
                              in_scale.data_ptr(), _ptr(guidance), _ptr(rescale), step.data_ptr(), start.data_ptr(),
                              seeds.data_ptr(), b, latent[0].numel(), n, _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes,
                              _C.stream_ptr()), "sde_step")
+
+
+def _pag_step_checks(what: str, latent, eps, next_in, history, in_scale, guidance, rescale, pag, step, start, tables):
+    """The checks the three PAG updates share; returns (latent batch, n_steps)."""
+    if latent.dtype != torch.float32 or eps.dtype != next_in.dtype or (history is not None and history.dtype != torch.float32):
+        raise BackendError(f"{what}: latent (and history) must be fp32 and eps/next_in share a dtype")
+    if not (latent.is_contiguous() or latent.is_contiguous(memory_format=torch.channels_last)):
+        raise BackendError(f"{what}: latent must be dense (contiguous or channels_last)")
+    if rescale is not None and guidance is None:
+        raise BackendError(f"{what}: rescale needs guidance")
+    b = latent.shape[0]
+    blocks = 3 if guidance is not None else 2
+    if history is not None and history.shape != latent.shape:
+        raise BackendError(f"{what}: history must match the latent {tuple(latent.shape)}; got {tuple(history.shape)}")
+    if eps.shape != next_in.shape or eps.shape[0] != blocks * b or eps.shape[1:] != latent.shape[1:]:
+        rows = "(3B, ...) [negative | positive | perturbed]" if guidance is not None else "(2B, ...) [positive | perturbed]"
+        raise BackendError(f"{what}: eps and next_in must be {rows} = {(blocks * b, *latent.shape[1:])} for a latent of "
+                           f"{tuple(latent.shape)}; got {tuple(eps.shape)} and {tuple(next_in.shape)}")
+    strides = [latent.stride(), eps.stride(), next_in.stride()] + ([history.stride()] if history is not None else [])
+    if any(st_ != strides[0] for st_ in strides):
+        raise BackendError(f"{what}: latent, history, eps and next_in must share one dense layout")
+    n = in_scale.numel()
+    for name, t in (("in_scale", in_scale), ("guidance", guidance), ("rescale", rescale), ("pag", pag)) + tuple(tables):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise BackendError(f"{what}: {name} must be a contiguous fp32 table of n_steps = {n} values")
+    if pag is None:
+        raise BackendError(f"{what}: the pag table is required")
+    if step.dtype != torch.int32 or (start is not None and start.dtype != torch.int32):
+        raise BackendError(f"{what}: step and start must be int32")
+    return b, n
+
+
+def pag_euler_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, dsigma: torch.Tensor, in_scale: torch.Tensor,
+                   guidance: Optional[torch.Tensor], pag: torch.Tensor, step: torch.Tensor, rescale: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None) -> None:
+    """cfg_euler_step with a third prediction (perturbed-attention guidance): with guidance eps and next_in are (3B, ...), rows
+    [negative | positive | perturbed], e = e_neg + guidance[i] (e_pos - e_neg) + pag[i] (e_pos - e_pert); without, (2B, ...) rows
+    [positive | perturbed], e = e_pos + pag[i] (e_pos - e_pert).  Rescale, Euler update and next_in (every row block) as there."""
+    _C.require_device(latent, eps, next_in, dsigma, in_scale, guidance, pag, step, rescale, workspace)
+    lib = _C.load()
+    b, n = _pag_step_checks("pag_euler_step", latent, eps, next_in, None, in_scale, guidance, rescale, pag, step, None, (("dsigma", dsigma),))
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(lib.st_pag_euler_step(latent.data_ptr(), eps.data_ptr(), next_in.data_ptr(), dsigma.data_ptr(), in_scale.data_ptr(),
+                                   _ptr(guidance), _ptr(rescale), pag.data_ptr(), step.data_ptr(), b, latent[0].numel(), n,
+                                   _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()), "pag_euler_step")
+
+
+def pag_dpmpp2m_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, history: torch.Tensor, coef: torch.Tensor,
+                     in_scale: torch.Tensor, step: torch.Tensor, start: torch.Tensor, pag: torch.Tensor,
+                     guidance: Optional[torch.Tensor] = None, rescale: Optional[torch.Tensor] = None,
+                     workspace: Optional[torch.Tensor] = None) -> None:
+    """dpmpp2m_step whose e is pag_euler_step's three-way (guidance given, 3B rows) or two-way (guidance None, 2B rows) combination."""
+    _C.require_device(latent, eps, next_in, history, coef, in_scale, step, start, pag, guidance, rescale, workspace)
+    lib = _C.load()
+    b, n = _pag_step_checks("pag_dpmpp2m_step", latent, eps, next_in, history, in_scale, guidance, rescale, pag, step, start, ())
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 4) or not coef.is_contiguous():
+        raise BackendError(f"pag_dpmpp2m_step: coef must be a contiguous fp32 (n_steps, 4) = ({n}, 4) table")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(lib.st_pag_dpmpp2m_step(latent.data_ptr(), eps.data_ptr(), next_in.data_ptr(), history.data_ptr(), coef.data_ptr(),
+                                     in_scale.data_ptr(), _ptr(guidance), _ptr(rescale), pag.data_ptr(), step.data_ptr(), start.data_ptr(),
+                                     b, latent[0].numel(), n, _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()),
+             "pag_dpmpp2m_step")
+
+
+def pag_sde_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor, history: torch.Tensor, coef: torch.Tensor,
+                 in_scale: torch.Tensor, step: torch.Tensor, start: torch.Tensor, seeds: torch.Tensor, pag: torch.Tensor,
+                 guidance: Optional[torch.Tensor] = None, rescale: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> None:
+    """sde_step whose e is pag_euler_step's combination; seeds stay one per latent sample."""
+    _C.require_device(latent, eps, next_in, history, coef, in_scale, step, start, seeds, pag, guidance, rescale, workspace)
+    lib = _C.load()
+    b, n = _pag_step_checks("pag_sde_step", latent, eps, next_in, history, in_scale, guidance, rescale, pag, step, start, ())
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 5) or not coef.is_contiguous():
+        raise BackendError(f"pag_sde_step: coef must be a contiguous fp32 (n_steps, 5) = ({n}, 5) table")
+    _check_seeds(seeds, b, "pag_sde_step")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(lib.st_pag_sde_step(latent.data_ptr(), eps.data_ptr(), next_in.data_ptr(), history.data_ptr(), coef.data_ptr(),
+                                 in_scale.data_ptr(), _ptr(guidance), _ptr(rescale), pag.data_ptr(), step.data_ptr(), start.data_ptr(),
+                                 seeds.data_ptr(), b, latent[0].numel(), n, _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes,
+                                 _C.stream_ptr()), "pag_sde_step")
 
 
 def step_advance(step: torch.Tensor, n_steps: int) -> None:

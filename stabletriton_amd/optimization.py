@@ -18,19 +18,21 @@ from torch import fx, nn
 from . import _C, ops
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_freeu, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_pag, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
-                    gn_stats: bool = True, freeu: bool = False) -> fx.GraphModule:
+                    gn_stats: bool = True, freeu: bool = False, pag_layers=None) -> fx.GraphModule:
     """Pass pipeline.  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
     `xattn_fusion` / `gn_stats` switch two of the added fusions off (A/B measurements).  `freeu` (addition, off by default:
     the graph is then exactly the one without it) puts a FreeU site in front of the decoder concatenations of the first two
-    stages and installs the neutral parameter state as `gm.freeu` (freeu.py)."""
+    stages and installs the neutral parameter state as `gm.freeu` (freeu.py).  `pag_layers` (addition, off by default, likewise):
+    regular expressions selecting the self-attention sites that take perturbed batch entries (optimizers/insert_pag.py); the state,
+    `gm.pag`, starts with chunks 0 = ordinary attention."""
     stats: Dict[str, int] = {}
     if freeu:      # first: the readers of a concatenation still carry their module paths
         stats["freeu_sites"] = insert_freeu(gm)
@@ -38,6 +40,8 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     if fuse:
         stats["deduped_activations"] = dedupe_pure_calls(gm)
     stats["attention"] = fuse_attention(gm)
+    if pag_layers is not None:      # directly after: the query projections still carry their module paths
+        stats["pag_sites"] = insert_pag(gm, pag_layers)
     stats["geglu"] = fuse_geglu(gm)
     stats["linear_silu"] = replace_linear_activ(gm, nn.SiLU())
     stats["group_norm_silu"] = replace_group_norm_activation(gm, nn.SiLU())
@@ -70,8 +74,12 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
     return replace_backend(gm)
 
 
-def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False) -> fx.GraphModule:
-    """`freeu=True` (addition): the compiled module carries FreeU sites and `gm.freeu`, their parameter state, neutral until
+def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
+                   pag_layers=None) -> fx.GraphModule:
+    """`pag_layers=("mid",)` (addition): the selected self-attention sites can treat the last B // chunks batch entries of a call as
+    perturbed (perturbed-attention guidance, pag.py): `gm.pag.using(chunks)` around the caller's own calls; chunks 0, the initial
+    state, is ordinary attention.
+    `freeu=True` (addition): the compiled module carries FreeU sites and `gm.freeu`, their parameter state, neutral until
     `gm.freeu.set(s1, s2, b1, b2, version)` (freeu.py; in-place, no new capture).
     `fp8=True` (addition, BASELINE config #5): the q|k|v, GEGLU and feed-forward output projections of a bf16 model's
     transformer blocks run with OCP e4m3 operands on the fp8 matrix pipe, fed by e4m3 copies their producers' epilogues
@@ -91,7 +99,7 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     model = model.eval().to(memory_format=torch.channels_last)      # conv weights -> (Cout,R,S,Cin) strides
     if fp8 and p0.dtype != torch.bfloat16:
         raise RuntimeError("fp8 projections need a bfloat16 model")
-    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu)
+    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()
@@ -109,7 +117,17 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
             return _run_step(gm, lambda: plain(*args, **kwargs))
 
         gm.forward = forward
-    if cuda_graph:
+    if cuda_graph and pag_layers is not None:
+        # the perturbed range is host state the launches are captured with: it is part of the graph cache's key
+        state, inner = gm.pag, gm.forward
+
+        def run_with_chunks(*args, _pag_chunks: int = 0, **kwargs):
+            with state.using(_pag_chunks):
+                return inner(*args, **kwargs)
+
+        graphed = make_dynamic_graphed_callable(run_with_chunks, before_replay=gm.exec_context.refresh_derived)
+        gm.forward = lambda *args, **kwargs: graphed(*args, _pag_chunks=state.chunks, **kwargs)
+    elif cuda_graph:
         gm.forward = make_dynamic_graphed_callable(gm.forward, before_replay=gm.exec_context.refresh_derived)
     return gm
 

@@ -36,6 +36,12 @@ what it had computed from them: derived weights, the hoisted text-context K/V an
 
 FreeU (`set_freeu`; freeu.py) is a device row of five floats the sites of a UNet compiled with `freeu=True` read by
 address: setting or clearing it is an in-place write, the captured graph stays.
+
+Perturbed-attention guidance (`pag_scale`, `set_pag`; pag.py) adds one more block of UNet rows, [negative | positive | perturbed]
+(3B) or, without `guidance_scale`, [positive | perturbed] (2B): the perturbed rows carry the positive conditioning and the same
+latent, and the self-attention sites of a UNet compiled with `pag_layers` return v for them (one copy launch per site instead of
+the attention).  The update is the `st_pag_*` form of the loop's sampler, which adds pag[i] (e_pos - e_pert) before the rescale; the
+scale is one more device table of n_steps floats, so `set_pag` needs no new capture.
 """
 from __future__ import annotations
 
@@ -54,10 +60,18 @@ class DenoiseLoop:
                  tables: Optional[Union[EulerTables, DPMSolverTables, SDETables]] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
                  tokens: int = 77, mode: str = "loop", n_time_ids: int = 6,
                  guidance_scale: Optional[Union[float, Sequence[float]]] = None,
-                 guidance_rescale: Optional[Union[float, Sequence[float]]] = None):
+                 guidance_rescale: Optional[Union[float, Sequence[float]]] = None,
+                 pag_scale: Optional[Union[float, Sequence[float]]] = None):
         assert mode in ("loop", "step", "eager")
         if guidance_rescale is not None and guidance_scale is None:
             raise ValueError("guidance_rescale needs guidance_scale")
+        # perturbed-attention guidance: the UNet's sites must exist (compiled in), and the loop names the perturbed row block
+        # around its own UNet calls only (chunks 3 = [neg | pos | pert], 2 = [pos | pert])
+        self._pag_state = None
+        if pag_scale is not None:
+            from . import pag
+            self._pag_state = pag.state_of(unet, "DenoiseLoop(pag_scale=...)")
+        self._pag_chunks = 0 if pag_scale is None else (3 if guidance_scale is not None else 2)
         self.unet, self.mode, self.dtype = unet, mode, dtype
         self.device = torch.device(device)
         self.tables = tables or euler_discrete_tables(50)
@@ -68,7 +82,8 @@ class DenoiseLoop:
         # both sides multiples of 4: the UNet halves the latent twice (Downsample2D, unet_pt.py:246-256) and doubles it back
         lh, lw = (int(latent_hw[0]), int(latent_hw[1])) if isinstance(latent_hw, (tuple, list)) else (int(latent_hw), int(latent_hw))
         self.batch = batch
-        rows = 2 * batch if guidance_scale is not None else batch       # guidance: the UNet sees [negative | positive]
+        # guidance: the UNet sees [negative | positive]; with pag_scale one more block, [.. | perturbed]
+        rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
         self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
         self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
@@ -101,6 +116,10 @@ class DenoiseLoop:
                 self.rescale = torch.zeros(n, dtype=torch.float32, device=dev)
                 self.cfg_workspace = ops.cfg_workspace(self.latent)
             self.set_guidance(guidance_scale, guidance_rescale)
+        self.pag = None
+        if pag_scale is not None:
+            self.pag = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.set_pag(pag_scale)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -128,14 +147,22 @@ class DenoiseLoop:
         if r is not None:
             self.rescale.copy_(r)
 
-    def _step_table(self, v, what: str) -> torch.Tensor:
+    def _step_table(self, v, what: str, who: str = "set_guidance") -> torch.Tensor:
         try:
             vals = [float(x) for x in v]
         except TypeError:                                  # a scalar (float, numpy scalar, 0-d tensor)
             vals = [float(v)] * self.n_steps
         if len(vals) != self.n_steps:
-            raise ValueError(f"set_guidance: {what} takes a float or {self.n_steps} values (one per step), got {len(vals)}")
+            raise ValueError(f"{who}: {what} takes a float or {self.n_steps} values (one per step), got {len(vals)}")
         return torch.tensor(vals, dtype=torch.float32)
+
+    def set_pag(self, scale: Union[float, Sequence[float]]) -> None:
+        """Perturbed-attention guidance scale per step: a float, or n_steps floats (pag.adaptive_scales gives diffusers' adaptive
+        table).  Written into the device table in place: no new capture.  Scale 0 keeps the perturbed rows and gives the value
+        the loop would compute without them."""
+        if self.pag is None:
+            raise ValueError("set_pag: this loop was built without pag_scale")
+        self.pag.copy_(self._step_table(scale, "scale", "set_pag"))
 
     def set_conditioning(self, encoder_hidden_states, text_embeds, time_ids, negative_encoder_hidden_states=None,
                          negative_text_embeds=None, negative_time_ids=None) -> None:
@@ -143,18 +170,21 @@ class DenoiseLoop:
         state or pooled embedding is zeros (SDXL's force_zeros_for_empty_prompt), missing negative time ids copy the
         positive ones."""
         negatives = (negative_encoder_hidden_states, negative_text_embeds, negative_time_ids)
+        b = self.batch
         if self.guidance is None:
             if any(t is not None for t in negatives):
                 raise ValueError("set_conditioning: negative conditioning needs a loop built with guidance_scale")
-            self.ehs.copy_(encoder_hidden_states)
-            self.text_embeds.copy_(text_embeds)
-            self.time_ids.copy_(time_ids)
+            for buf, pos in ((self.ehs, encoder_hidden_states), (self.text_embeds, text_embeds), (self.time_ids, time_ids)):
+                buf[:b].copy_(pos)
+                if self.pag is not None:                   # the perturbed rows carry the positive conditioning
+                    buf[b:].copy_(pos)
         else:
-            b = self.batch
             for buf, pos, neg in ((self.ehs, encoder_hidden_states, negative_encoder_hidden_states),
                                   (self.text_embeds, text_embeds, negative_text_embeds),
                                   (self.time_ids, time_ids, time_ids if negative_time_ids is None else negative_time_ids)):
-                buf[b:].copy_(pos)
+                buf[b:2 * b].copy_(pos)
+                if self.pag is not None:                   # the perturbed rows carry the positive conditioning
+                    buf[2 * b:].copy_(pos)
                 if neg is None:
                     buf[:b].zero_()
                 else:
@@ -322,12 +352,12 @@ class DenoiseLoop:
         return n - t_start
 
     def _write_input(self, scale: float) -> None:
-        if self.guidance is None:
+        if self.guidance is None and self.pag is None:
             self.x_in.copy_(self.latent * scale)
             return
         v = self.latent * scale
-        self.x_in[:self.batch].copy_(v)
-        self.x_in[self.batch:].copy_(v)
+        for r in range(self.x_in.shape[0] // self.batch):      # every row block sees the same latent
+            self.x_in[r * self.batch:(r + 1) * self.batch].copy_(v)
 
     def _recalibrate(self, i: int) -> None:
         """fp8 plan only: a trajectory starts from scales measured on its own first evaluation (not on the last step of
@@ -343,6 +373,12 @@ class DenoiseLoop:
         return {"text_embeds": self.text_embeds, "time_ids": self.time_ids}
 
     def _unet(self, t, time_row=None):
+        if self._pag_state is not None:      # the last B rows are the perturbed block, for this loop's own calls only
+            with self._pag_state.using(self._pag_chunks):
+                return self._unet_call(t, time_row)
+        return self._unet_call(t, time_row)
+
+    def _unet_call(self, t, time_row=None):
         if self._split:
             if self.ctx is None:
                 raise RuntimeError("set_conditioning() must be called before running the loop")
@@ -365,7 +401,17 @@ class DenoiseLoop:
         ops.step_advance(self.step, self.n_steps)
 
     def _update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
-        if isinstance(self.tables, SDETables):
+        if self.pag is not None:
+            if isinstance(self.tables, SDETables):
+                ops.pag_sde_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+                                 self.pag, self.guidance, self.rescale, self.cfg_workspace)
+            elif self.coef is not None:
+                ops.pag_dpmpp2m_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.pag,
+                                     self.guidance, self.rescale, self.cfg_workspace)
+            else:
+                ops.pag_euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.guidance, self.pag, step, self.rescale,
+                                   self.cfg_workspace)
+        elif isinstance(self.tables, SDETables):
             ops.sde_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
                          self.guidance, self.rescale, self.cfg_workspace)
         elif self.coef is not None:
