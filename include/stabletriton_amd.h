@@ -57,8 +57,8 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, and then
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
                                               st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
-                                              st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, added without a bump: new entry
-                                              points, no existing signature or contract changed) */
+                                              st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then st_lora_merge_dora,
+                                              added without a bump: new entry points, no existing signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -287,6 +287,26 @@ int st_sde_step(float* latent, const void* eps, void* next_in, float* history, c
 enum { ST_LORA_TILE_N = 64, ST_LORA_TILE_K = 128, ST_LORA_MAX_RANK = 128 };
 int st_lora_merge(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
                   const int* tiles, long n_tiles, const float* scales, int n_scales, int dtype, void* stream);
+
+/* The same merge with DoRA segments: a segment may carry a magnitude m (N floats), and its rows are renormalised,
+ *   V_j = fp32(Base_t) + s_j Up_tj DownT_tj^T,   g_j[n] = m_j[n] / ||V_j[n, :]||_2   (g_j = 1 without a magnitude),
+ *   W_t[n][k] = round( (1 + sum_j (g_j[n] - 1)) fp32(Base_t[n][k]) + sum_j g_j[n] s_j sum_r Up_tj[n][r] DownT_tj[k][r] ),
+ * which is Base + sum_j (g_j (.) V_j - Base): PEFT's DoRA, the scale inside the norm, each adapter normalised against the
+ * base alone.  Tables as st_lora_merge, except
+ *   segments:   n_segments rows of 6 int64 [Up, DownT, rp, scale slot, magnitude, workspace offset]: magnitude is the device
+ *               address of N fp32 values, or 0 for a plain segment; the offset (in floats) is where the segment's
+ *               N * ceil(K / ST_LORA_TILE_K) partial sums of squares live in `workspace` (unused for a plain segment);
+ *   norm_tiles: n_norm_tiles rows of [target, tile] listing EVERY tile of every target that has a DoRA segment (a subset of
+ *               `tiles`, possibly empty);
+ *   workspace:  fp32, device, at least the largest offset + its segment's size; written by the first launch, read by the second.
+ * Two launches on `stream` (one when n_norm_tiles == 0): the norm pass writes, per DoRA segment with a non-zero scale, each
+ * row's sum of squares of V over one K-tile (V from the unrounded fp32 product); the merge pass adds a row's partials in a
+ * fixed order.  A segment whose scale is 0 is skipped whole, magnitude included: a weight with no non-zero scale receives
+ * its base's bits.  A row of V_j whose sum of squares is exactly 0 takes g_j[n] = 0 (its g V is the zero it was; no inf or
+ * NaN is produced).  A table without any magnitude gives st_lora_merge's bits.  No atomics: bitwise deterministic. */
+int st_lora_merge_dora(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
+                       const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
+                       float* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

@@ -15,6 +15,25 @@
 // are contiguous in memory, so the copy is coalesced, where operand reads straight from memory take one cache line per lane
 // (measured on SDXL-base at rank 128: 5.4 ms against this form's figure in DESIGN.md).  The ranks are zero-padded to the
 // MFMA's k = 32 by the host, which is exact and leaves no remainder path.  fp32 models use plain fp32 FMAs, ranks padded to 4.
+//
+// DoRA (st_lora_merge_dora) renormalises a segment's rows: V_j = Base + s_j Up_j Down_j, g_j[n] = m_j[n] / ||V_j[n, :]||,
+//
+//   W_t[n][k] = round_to_dtype( (1 + sum_j (g_j[n] - 1)) fp32(Base_t[n][k]) + sum_j g_j[n] s_j sum_r Up_tj[n][r] DownT_tj[k][r] )
+//
+// with g_j = 1 for a segment without a magnitude.  The norm is a reduction over every K-tile of a row, which one tile per
+// workgroup cannot hold, so the merge takes two launches of the SAME kernel body (MODE below):
+//   norm pass   one workgroup per (row block, K-tile) of every target that has a DoRA segment.  It forms the tile of
+//               fp32(Base) + s * acc (acc the unrounded fp32 product) exactly as the merge does, squares it, and writes each
+//               row's sum over the tile's <= 128 columns into the workspace: partial[segment][K-tile][n].
+//   merge pass  today's tile loop; the lanes that share a row add its partials (four interleaved chains in K-tile order, joined
+//               by a fixed xor tree), take g = m / sqrt(sum), and scale.
+// Partials in a workspace, not one workgroup walking all K-tiles of its 64 rows: SDXL's largest conv weight is
+// (1280, 11520), 20 row blocks against 90 K-tiles, and a walk would leave 236 of 256 CUs idle on the weights that carry most
+// of the bytes; with partials the norm pass has the merge's own grid.  The price is 4 N ceil(K / 128) bytes per DoRA segment
+// written once and read by the 64-row blocks that need them - 1/64 of the weight's bytes in a 16-bit model.  Every partial is
+// one lane's fixed-order sum followed by a fixed xor-shuffle tree, and the partials of a row are added in the same fixed
+// order by every workgroup that needs them: no atomics, two merges give the same bits.  A segment at scale 0 is skipped whole in both
+// passes, magnitude included, so "all scales zero" still copies the base's bits.
 #include "common.h"
 
 namespace {
@@ -22,7 +41,10 @@ namespace {
 constexpr int LORA_THREADS = 256;
 constexpr int LORA_TN = ST_LORA_TILE_N;      // 64: four waves of 16 rows
 constexpr int LORA_TK = ST_LORA_TILE_K;      // 128: four pairs of MFMA tiles
-constexpr int TGT_WORDS = 6, SEG_WORDS = 4;
+constexpr int TGT_WORDS = 6;
+enum { MODE_PLAIN = 0, MODE_DORA = 1, MODE_NORM = 2 };      // st_lora_merge's kernel; the DoRA merge pass; the DoRA norm pass
+// a segment row is [Up, DownT, rp, slot] for st_lora_merge and [Up, DownT, rp, slot, magnitude or 0, workspace offset] for DoRA
+template <int MODE> struct SegRow { static constexpr int WORDS = MODE == MODE_PLAIN ? 4 : 6; };
 
 struct Target {
     char* w;
@@ -44,8 +66,9 @@ __device__ __forceinline__ Target load_target(const long long* __restrict__ targ
 
 // base + delta for VEC consecutive k of row n, rounded once; 16-byte accesses when the target allows them (K a multiple of
 // VEC and both images 16-byte aligned), elementwise with a bound check per value otherwise.  `merged` false: the base's bits.
-template <typename T>
-__device__ __forceinline__ void finish_row(const Target& tg, int n, int k, const float* delta, bool merged, bool vec) {
+// DORA: the base is scaled by `bcoef` (one fma; bcoef == 1 gives the plain form's bits).
+template <typename T, bool DORA = false>
+__device__ __forceinline__ void finish_row(const Target& tg, int n, int k, const float* delta, bool merged, bool vec, float bcoef = 1.f) {
     constexpr int VEC = Elem<T>::VEC;
     if (n >= tg.N || k >= tg.K) return;
     const long at = (long)n * tg.K + k;
@@ -55,14 +78,45 @@ __device__ __forceinline__ void finish_row(const Target& tg, int n, int k, const
         Vec16<T> v = load16(b);
         if (merged) {
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) v.set(i, v.get(i) + delta[i]);
+            for (int i = 0; i < VEC; ++i) v.set(i, DORA ? fmaf(bcoef, v.get(i), delta[i]) : v.get(i) + delta[i]);
         }
         store16(w, v);
     } else {
         for (int i = 0; i < VEC && k + i < tg.K; ++i)
-            w[i] = merged ? Elem<T>::from_f(Elem<T>::to_f(b[i]) + delta[i]) : b[i];
+            w[i] = merged ? Elem<T>::from_f(DORA ? fmaf(bcoef, Elem<T>::to_f(b[i]), delta[i]) : Elem<T>::to_f(b[i]) + delta[i]) : b[i];
     }
 }
+
+// fp32 base values of VEC consecutive k of row n, 0 past the weight's edge (never read there): the norm pass's operand
+template <typename T>
+__device__ __forceinline__ void base_row(const Target& tg, int n, int k, bool vec, float* out) {
+    constexpr int VEC = Elem<T>::VEC;
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) out[i] = 0.f;
+    if (n >= tg.N || k >= tg.K) return;
+    const T* b = reinterpret_cast<const T*>(tg.base) + (long)n * tg.K + k;
+    if (vec) {
+        const Vec16<T> v = load16(b);
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) out[i] = v.get(i);
+    } else {
+        for (int i = 0; i < VEC && k + i < tg.K; ++i) out[i] = Elem<T>::to_f(b[i]);
+    }
+}
+
+// One of the `stride` interleaved chains of a row's partial sums of squares (one partial per K-tile): K-tiles first,
+// first + stride, ...  The lanes that share a row take one chain each and join them by a fixed xor tree, so the row's
+// ceil(K / 128) loads (90 for SDXL's widest conv) are neither repeated by every lane nor one serial chain.
+__device__ __forceinline__ float dora_chain(const float* __restrict__ partials, int n, int N, int tiles_k, int first, int stride) {
+    float ss = 0.f;
+#pragma unroll 4
+    for (int kt = first; kt < tiles_k; kt += stride) ss += partials[(long)kt * N + n];
+    return ss;
+}
+
+// g[n] = m[n] / ||V[n, :]|| from the row's sum of squares.  A row of V that is exactly zero has no direction to scale (PEFT
+// divides by zero there): its gain is 0, so the row's g V is the zero it already was and nothing non-finite reaches the weight.
+__device__ __forceinline__ float dora_gain(float ss, float m) { return ss > 0.f ? m / sqrtf(ss) : 0.f; }
 
 template <typename T> struct Mfma16;
 template <> struct Mfma16<bf16> {
@@ -79,10 +133,12 @@ template <> struct Mfma16<f16> {
 // image row 32 p + 16 h + 4 a + b - so the 16 lanes of an operand read take 16 consecutive image rows.
 static inline int lora_lds_row(int max_rank) { return (max_rank + 8) * 2; }      // bytes
 
-template <typename T>
+template <typename T, int MODE>
 __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long long* __restrict__ targets, const long long* __restrict__ segments,
-                                                                   const int* __restrict__ tiles, const float* __restrict__ scales, int lds_row) {
+                                                                   const int* __restrict__ tiles, const float* __restrict__ scales, int lds_row,
+                                                                   float* __restrict__ workspace) {
     typedef typename V16<T>::x8 frag;
+    constexpr int SEG_WORDS = SegRow<MODE>::WORDS;
     extern __shared__ __attribute__((aligned(16))) char lds_down[];
     char* lds_up = lds_down + LORA_TK * lds_row;
     const int t = tiles[2 * blockIdx.x], tile = tiles[2 * blockIdx.x + 1];
@@ -95,7 +151,11 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
     const int rows_k = min(LORA_TK, tg.K - k0), rows_n = min(LORA_TN, tg.N - nt);      // rows of the factors this tile may read
     // the base's 16-byte vectors are requested first: they come from HBM while the factors are staged and multiplied
     Vec16<T> basev[4];
-    if (vec && n0 + c < tg.N) {
+    float basef[MODE == MODE_NORM ? 4 : 1][8];                  // (norm pass) the same values as floats, 0 past the edge
+    if constexpr (MODE == MODE_NORM) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) base_row<T>(tg, n0 + c, k0 + 32 * p + 8 * g, vec, basef[p]);
+    } else if (vec && n0 + c < tg.N) {
 #pragma unroll
         for (int p = 0; p < 4; ++p)
             if (k0 + 32 * p + 8 * g < tg.K)
@@ -104,11 +164,13 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
     f32x4 sum[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) sum[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bcoef = 1.f;                                          // (DoRA) 1 + sum_j (g_j[n] - 1), what the base is scaled by
     bool merged = false;
     for (int j = 0; j < tg.nseg; ++j) {
         const long long* sg = segments + (long)(tg.seg0 + j) * SEG_WORDS;
         const float s = scales[(int)sg[3]];
         if (s == 0.f) continue;                                 // (uniform) an adapter at scale 0 contributes nothing, whatever it holds
+        if (MODE == MODE_NORM && sg[4] == 0) continue;          // (uniform) a plain segment has no norm
         const T* up = (const T*)sg[0] + (long)nt * (int)sg[2];
         const T* down_t = (const T*)sg[1] + (long)k0 * (int)sg[2];
         const int rp = (int)sg[2], chunks = rp >> 3;             // 16-byte chunks per factor row
@@ -139,11 +201,42 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
                 acc[i] = Mfma16<T>::run(a, b, acc[i]);
             }
         }
+        if constexpr (MODE == MODE_NORM) {
+            // the lane's 32 values of row n0 + c in a fixed order (values past the edge - the images hold anything there -
+            // count as 0), then the row's four lane groups by a fixed xor tree: every one of them ends with the same sum
+            float ss = 0.f;
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+            for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sum[i][e] = fmaf(s, acc[i][e], sum[i][e]);
+                for (int e = 0; e < 4; ++e) {
+                    const int k = k0 + 32 * (i >> 1) + 8 * g + 4 * (i & 1) + e;
+                    const float v = (n0 + c < tg.N && k < tg.K) ? fmaf(s, acc[i][e], basef[i >> 1][4 * (i & 1) + e]) : 0.f;
+                    ss = fmaf(v, v, ss);
+                }
+            ss += __shfl_xor(ss, 16);
+            ss += __shfl_xor(ss, 32);
+            if (g == 0 && n0 + c < tg.N) workspace[sg[5] + (long)(tile % tiles_k) * tg.N + n0 + c] = ss;
+        } else {
+            float coef = s;
+            if constexpr (MODE == MODE_DORA) {
+                if (sg[4] != 0) {                               // (uniform) rows past the edge take the last row's gain and are never stored
+                    // a row's four lane groups add one chain of its partials each; the xor tree leaves the same sum in all four
+                    const int n = min(n0 + c, tg.N - 1);
+                    float ss = dora_chain(workspace + sg[5], n, tg.N, tiles_k, g, 4);
+                    ss += __shfl_xor(ss, 16);
+                    ss += __shfl_xor(ss, 32);
+                    const float gain = dora_gain(ss, ((const float*)sg[4])[n]);
+                    bcoef += gain - 1.f;
+                    coef = gain * s;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sum[i][e] = fmaf(coef, acc[i][e], sum[i][e]);
+        }
     }
+    if constexpr (MODE == MODE_NORM) return;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
         float delta[8];
@@ -154,11 +247,12 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
         }
         const int n = n0 + c, k = k0 + 32 * p + 8 * g;
         if (!vec) {
-            finish_row<T>(tg, n, k, delta, merged, false);
+            finish_row<T, MODE == MODE_DORA>(tg, n, k, delta, merged, false, bcoef);
         } else if (n < tg.N && k < tg.K) {                      // k + 8 <= K: k and K are multiples of 8
             if (merged) {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) basev[p].set(e, basev[p].get(e) + delta[e]);
+                for (int e = 0; e < 8; ++e)
+                    basev[p].set(e, MODE == MODE_DORA ? fmaf(bcoef, basev[p].get(e), delta[e]) : basev[p].get(e) + delta[e]);
             }
             store16(reinterpret_cast<T*>(tg.w) + (long)n * tg.K + k, basev[p]);
         }
@@ -166,23 +260,32 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
 }
 
 // fp32: thread (rg, cg) owns rows 8 rg .. 8 rg + 7 and columns 4 cg .. 4 cg + 3 of the tile; factors are read four ranks at a time
+template <int MODE>
 __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long long* __restrict__ targets, const long long* __restrict__ segments,
-                                                                   const int* __restrict__ tiles, const float* __restrict__ scales) {
+                                                                   const int* __restrict__ tiles, const float* __restrict__ scales,
+                                                                   float* __restrict__ workspace) {
+    constexpr int SEG_WORDS = SegRow<MODE>::WORDS;
     const int t = tiles[2 * blockIdx.x], tile = tiles[2 * blockIdx.x + 1];
     const Target tg = load_target(targets, t);
     const int tiles_k = (tg.K + LORA_TK - 1) / LORA_TK;
     const int n0 = (tile / tiles_k) * LORA_TN + (threadIdx.x >> 5) * 8, k0 = (tile % tiles_k) * LORA_TK + (threadIdx.x & 31) * 4;
     const bool vec = tg.K % 4 == 0 && (((uintptr_t)tg.w | (uintptr_t)tg.base) & 15) == 0;
     float sum[8][4];
+    float basef[MODE == MODE_NORM ? 8 : 1][4];
+    float bcoef[MODE == MODE_DORA ? 8 : 1];
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < 8; ++i) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) sum[i][e] = 0.f;
+        if constexpr (MODE == MODE_NORM) base_row<float>(tg, n0 + i, k0, vec, basef[i]);
+        if constexpr (MODE == MODE_DORA) bcoef[i] = 1.f;
+    }
     bool merged = false;
     for (int j = 0; j < tg.nseg; ++j) {
         const long long* sg = segments + (long)(tg.seg0 + j) * SEG_WORDS;
         const float s = scales[(int)sg[3]];
         if (s == 0.f) continue;
+        if (MODE == MODE_NORM && sg[4] == 0) continue;
         merged = true;
         const float* up = (const float*)sg[0];
         const float* down_t = (const float*)sg[1];
@@ -206,13 +309,69 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long l
                     for (int e = 0; e < 4; ++e) acc[i][e] = fmaf(u[q], d[e][q], acc[i][e]);
             }
         }
+        if constexpr (MODE == MODE_NORM) {
+            // a row's 128 columns sit in the 32 lanes of one half wave: four values per lane, then a fixed xor tree inside the half
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+            for (int i = 0; i < 8; ++i) {
+                float ss = 0.f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sum[i][e] = fmaf(s, acc[i][e], sum[i][e]);
+                for (int e = 0; e < 4; ++e) {
+                    const float v = (n0 + i < tg.N && k0 + e < tg.K) ? fmaf(s, acc[i][e], basef[i][e]) : 0.f;
+                    ss = fmaf(v, v, ss);
+                }
+#pragma unroll
+                for (int m = 1; m < 32; m <<= 1) ss += __shfl_xor(ss, m);
+                if ((threadIdx.x & 31) == 0 && n0 + i < tg.N) workspace[sg[5] + (long)(tile % tiles_k) * tg.N + n0 + i] = ss;
+            }
+        } else {
+            // (DoRA) the 32 lanes of a half wave share their 8 rows: lane l adds chain l >> 3 (of four) of row l & 7, an xor tree
+            // joins the chains, and every lane then takes row i's gain from lane i of its half
+            float mine = 0.f;
+            if constexpr (MODE == MODE_DORA) {
+                if (sg[4] != 0) {                               // (uniform)
+                    const int l = threadIdx.x & 31, n = min(n0 + (l & 7), tg.N - 1);
+                    float ss = dora_chain(workspace + sg[5], n, tg.N, tiles_k, l >> 3, 4);
+                    ss += __shfl_xor(ss, 8);
+                    ss += __shfl_xor(ss, 16);
+                    mine = dora_gain(ss, ((const float*)sg[4])[n]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                float coef = s;
+                if constexpr (MODE == MODE_DORA) {
+                    if (sg[4] != 0) {                           // (uniform)
+                        const float gain = __shfl(mine, (int)(threadIdx.x & 32) + i);
+                        bcoef[i] += gain - 1.f;
+                        coef = gain * s;
+                    }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sum[i][e] = fmaf(coef, acc[i][e], sum[i][e]);
+            }
+        }
     }
+    if constexpr (MODE == MODE_NORM) return;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) finish_row<float>(tg, n0 + i, k0, sum[i], merged, vec);
+    for (int i = 0; i < 8; ++i)
+        finish_row<float, MODE == MODE_DORA>(tg, n0 + i, k0, sum[i], merged, vec, MODE == MODE_DORA ? bcoef[i] : 1.f);
+}
+
+template <int MODE>
+static int lora_launch(const char* what, const long long* targets, const long long* segments, int max_rank, const int* tiles, long n_tiles,
+                       const float* scales, float* workspace, int dtype, hipStream_t st) {
+    const dim3 grid((unsigned)n_tiles), block(LORA_THREADS);
+    const int lds_row = lora_lds_row((max_rank + 31) / 32 * 32);
+    const size_t lds = (size_t)(LORA_TK + LORA_TN) * lds_row;
+    if (dtype == ST_BF16)
+        hipLaunchKernelGGL((lora_merge16_kernel<bf16, MODE>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
+    else if (dtype == ST_F16)
+        hipLaunchKernelGGL((lora_merge16_kernel<f16, MODE>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
+    else if (dtype == ST_F32)
+        hipLaunchKernelGGL(lora_merge32_kernel<MODE>, grid, block, 0, st, targets, segments, tiles, scales, workspace);
+    else
+        return st_fail("%s: unsupported dtype %d", what, dtype);
+    return st_check_launch(what);
 }
 
 }  // namespace
@@ -227,17 +386,30 @@ extern "C" int st_lora_merge(const long long* targets, int n_targets, const long
                "lora_merge: misaligned table");
     ST_REQUIRE(max_rank >= 0 && max_rank <= ST_LORA_MAX_RANK && (n_segments == 0 || max_rank > 0),
                "lora_merge: max_rank %d (the largest padded rank of the segments, 1 .. %d)", max_rank, (int)ST_LORA_MAX_RANK);
+    return lora_launch<MODE_PLAIN>("lora_merge", targets, segments, max_rank, tiles, n_tiles, scales, nullptr, dtype, (hipStream_t)stream);
+}
+
+extern "C" int st_lora_merge_dora(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
+                                  const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
+                                  float* workspace, size_t workspace_bytes, int dtype, void* stream) {
+    ST_REQUIRE(targets && tiles && scales && segments, "lora_merge_dora: null pointer");
+    ST_REQUIRE(n_targets > 0 && n_segments > 0 && n_scales > 0, "lora_merge_dora: bad sizes (targets %d, segments %d, scales %d)",
+               n_targets, n_segments, n_scales);
+    ST_REQUIRE(n_tiles > 0 && n_tiles <= 0x7fffffffL && n_norm_tiles >= 0 && n_norm_tiles <= n_tiles,
+               "lora_merge_dora: %ld tiles, %ld norm tiles (a launch takes 1 .. 2^31 - 1; the norm pass covers a subset of the targets)",
+               n_tiles, n_norm_tiles);
+    ST_REQUIRE(n_norm_tiles == 0 || (norm_tiles && workspace && workspace_bytes >= 4),
+               "lora_merge_dora: the norm pass needs its tile list and a workspace");
+    ST_REQUIRE((uintptr_t)targets % 8 == 0 && (uintptr_t)segments % 8 == 0 && (uintptr_t)tiles % 4 == 0 && (uintptr_t)norm_tiles % 4 == 0 &&
+               (uintptr_t)scales % 4 == 0 && (uintptr_t)workspace % 4 == 0, "lora_merge_dora: misaligned table");
+    ST_REQUIRE(max_rank > 0 && max_rank <= ST_LORA_MAX_RANK,
+               "lora_merge_dora: max_rank %d (the largest padded rank of the segments, 1 .. %d)", max_rank, (int)ST_LORA_MAX_RANK);
+    ST_REQUIRE(dtype == ST_BF16 || dtype == ST_F16 || dtype == ST_F32, "lora_merge_dora: unsupported dtype %d", dtype);
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)n_tiles), block(LORA_THREADS);
-    const int lds_row = lora_lds_row((max_rank + 31) / 32 * 32);
-    const size_t lds = (size_t)(LORA_TK + LORA_TN) * lds_row;
-    if (dtype == ST_BF16)
-        hipLaunchKernelGGL(lora_merge16_kernel<bf16>, grid, block, lds, st, targets, segments, tiles, scales, lds_row);
-    else if (dtype == ST_F16)
-        hipLaunchKernelGGL(lora_merge16_kernel<f16>, grid, block, lds, st, targets, segments, tiles, scales, lds_row);
-    else if (dtype == ST_F32)
-        hipLaunchKernelGGL(lora_merge32_kernel, grid, block, 0, st, targets, segments, tiles, scales);
-    else
-        return st_fail("lora_merge: unsupported dtype %d", dtype);
-    return st_check_launch("lora_merge");
+    if (n_norm_tiles > 0) {
+        const int rc = lora_launch<MODE_NORM>("lora_merge_dora (norm pass)", targets, segments, max_rank, norm_tiles, n_norm_tiles, scales,
+                                              workspace, dtype, st);
+        if (rc) return rc;
+    }
+    return lora_launch<MODE_DORA>("lora_merge_dora", targets, segments, max_rank, tiles, n_tiles, scales, workspace, dtype, st);
 }

@@ -67,9 +67,10 @@ class _HoistedUNet(nn.Module):
         from . import lora
         return lora.attach(self.compiled)
 
-    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True):
-        """Merge a LoRA state dict (PEFT / diffusers / kohya keys) into the compiled UNet; returns the keys not applied."""
-        left = self._lora_set().load(name, state_dict, scale, strict)
+    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True, convs: bool = False):
+        """Merge a LoRA state dict (PEFT / diffusers / kohya keys; DoRA magnitudes apply) into the compiled UNet; `convs=True`
+        also takes its convolution factors (LoCon).  Returns the keys not applied."""
+        left = self._lora_set().load(name, state_dict, scale, strict, convs)
         self.refresh_weights()
         return left
 

@@ -11,18 +11,34 @@ subtracting is what makes `unload` restore the base bit for bit, scale 0 equal t
 16-bit models.  The weights keep their addresses, so captured graphs stay valid; the owner re-derives what was computed
 from them (fused q|k|v, LayerNorm-folded projections, split images, the fp8 plan's e4m3 weights: `refresh_derived`).
 
-`parse_lora_state_dict` reads the three spellings in the wild (PEFT / current diffusers, older diffusers, kohya);
+`parse_adapter` reads the three spellings in the wild (PEFT / current diffusers, older diffusers, kohya);
 `LoraSet` owns the state of one module; `attach(compiled)` returns the set of an `optimize_model` result.
 `DenoiseLoop.load_lora` and the hooks' `load_lora` are thin wrappers over it.
 
-Scope: `nn.Linear` targets only (attention projections, feed-forward, proj_in / proj_out, and the time-path Linears when an
-adapter names them).  Convolution adapters (LoCon / LyCORIS), DoRA and text-encoder adapters are reported, not applied.
+DoRA: an adapter that carries a magnitude m (one value per output row / channel) renormalises the rows it touches,
+
+    V_j = Base + s_j * Up_j @ Down_j,    g_j[n] = m_j[n] / ||V_j[n, :]||_2    (g_j = 1 for a plain adapter)
+    W   = round_to_dtype( Base + sum_j (g_j (.) V_j - Base) )
+
+which is PEFT's DoRA (the scale sits inside the norm); several adapters on one weight are each normalised against the base
+alone, as PEFT's forward with several active adapters does.  An adapter whose effective scale is exactly 0 is skipped whole,
+magnitude included, so scale 0 and `unload` still give the base's bits.  That is a jump at 0: PEFT's DoRA at scale 0 is
+m / ||Base|| (.) Base, which a scale that merely approaches 0 approaches here too, and which is not Base.  A row of V_j that is
+exactly zero has no direction (PEFT divides by zero there); its gain is 0 here, so the row's g_j (.) V_j stays the zero it was.
+
+Scope: `nn.Linear` targets (attention projections, feed-forward, proj_in / proj_out, and the time-path Linears when an
+adapter names them) and, with `convs=True`, `nn.Conv2d` targets (LoCon: conv_in / conv_out, the resnets' conv1 / conv2 /
+conv_shortcut, the samplers' conv).  A conv weight (O, I, R, S) is merged through the 2-D view of its own memory - (O, R S I)
+for the channels_last weights of an `optimize_model` result, (O, I R S) for a contiguous one - so the kernel sees it as it
+sees a Linear.  Conv factors are down (r, I, R, S) with the target's kernel size and up (O, r, 1, 1).  Tucker (`lora_mid`),
+LoHa and LoKr factors, DoRA magnitudes along the input axis, grouped or dilated targets are refused; text-encoder adapters
+are reported, not applied.
 """
 from __future__ import annotations
 
 import re
 from collections import OrderedDict
-from typing import Callable, Dict, Iterable, List, Mapping, Optional, Tuple
+from typing import Callable, Dict, Iterable, List, Mapping, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -34,7 +50,10 @@ _TEXT_ENCODER = re.compile(r"^(lora_te\d*_|text_encoder(_\d+)?\.|te\d*\.|lora_pr
 _PEFT = re.compile(r"^(?P<path>.+)\.lora_(?P<ab>[AB])(?:\.[^.]+)?\.weight$")
 _OLD_PROC = re.compile(r"^(?P<attn>.+?)\.(?:processor\.)?(?P<proj>to_q|to_k|to_v|to_out)_lora\.(?P<du>down|up)\.weight$")
 _OLD_LAYER = re.compile(r"^(?P<path>.+)\.lora(?:_layer)?\.(?P<du>down|up)\.weight$")
-_KOHYA = re.compile(r"^(?P<stem>lora_unet_[^.]+)\.(?P<what>lora_down\.weight|lora_up\.weight|alpha)$")
+_KOHYA = re.compile(r"^(?P<stem>lora_unet_[^.]+)\.(?P<what>lora_down\.weight|lora_up\.weight|alpha|dora_scale)$")
+_PEFT_MAGNITUDE = re.compile(r"^(?P<path>.+)\.lora_magnitude_vector(?:\.[^.]+)?(?:\.weight)?$")
+# factorisations this merge does not implement: Tucker's core (`lora_mid`), LoHa (`hada_*`), LoKr (`lokr_*`)
+_OTHER_FORMS = re.compile(r"^(?P<stem>.+?)\.(?P<what>lora_mid|hada_(?:w[12]_[ab]|t[12])|lokr_(?:w[12](?:_[ab])?|t2))(?:\.weight)?$")
 
 
 def is_text_encoder_key(key: str) -> bool:
@@ -42,14 +61,24 @@ def is_text_encoder_key(key: str) -> bool:
 
 
 def _place(key: str, flat: Mapping[str, str], names) -> Optional[Tuple[str, str]]:
-    """(module name, 'down' | 'up' | 'alpha') for one state-dict key, or None when the key names no target."""
+    """(module name, 'down' | 'up' | 'alpha' | 'magnitude') for one state-dict key, or None when the key names no target."""
+    m = _OTHER_FORMS.match(key)
+    if m:
+        stem = m["stem"]
+        name = flat.get(stem[len("lora_unet_"):]) if stem.startswith("lora_unet_") else stem[len("unet."):] if stem.startswith("unet.") else stem
+        if name in names:
+            raise ValueError(f"{name}: {key!r} belongs to a Tucker (lora_mid), LoHa or LoKr factorisation, which is not supported")
+        return None
     m = _KOHYA.match(key)
     if m:
         name = flat.get(m["stem"][len("lora_unet_"):])
-        what = {"lora_down.weight": "down", "lora_up.weight": "up", "alpha": "alpha"}[m["what"]]
+        what = {"lora_down.weight": "down", "lora_up.weight": "up", "alpha": "alpha", "dora_scale": "magnitude"}[m["what"]]
         return (name, what) if name is not None else None
     if key.startswith("unet."):
         key = key[len("unet."):]
+    m = _PEFT_MAGNITUDE.match(key)
+    if m:
+        return (m["path"], "magnitude") if m["path"] in names else None
     m = _PEFT.match(key)
     if m:
         return (m["path"], "down" if m["ab"] == "A" else "up") if m["path"] in names else None
@@ -65,16 +94,46 @@ def _place(key: str, flat: Mapping[str, str], names) -> Optional[Tuple[str, str]
     return None
 
 
-def parse_lora_state_dict(sd: Mapping[str, torch.Tensor], module_names: Iterable[str]):
-    """Place a LoRA state dict on the modules named by `module_names` (the model's own `nn.Linear` names).
+class Placed(NamedTuple):
+    """What an adapter holds for one module: down (r, K) and up (N, r) - (r, I, R, S) and (O, r, 1, 1) for a convolution - its
+    alpha, and its DoRA magnitude as the file holds it (None for a plain adapter)."""
+    down: torch.Tensor
+    up: torch.Tensor
+    alpha: float
+    magnitude: Optional[torch.Tensor] = None
 
-    Returns `(placed, unplaced)`: `placed[name] = (down (r, K), up (N, r), alpha)`, `unplaced` the keys that name no target
-    (convolutions, other networks, text encoders - `is_text_encoder_key` tells the latter apart).  Spellings:
+
+def parse_lora_state_dict(sd: Mapping[str, torch.Tensor], module_names):
+    """`parse_adapter` in the form this function has always had: `placed[name] = (down, up, alpha)`.  DoRA magnitudes are placed
+    and checked like everything else but are not part of the triples; `parse_adapter` returns them.
+
+    Keys that name a listed module in a form the merge cannot apply RAISE ValueError; they are no longer reported as unplaced:
+    Tucker (`lora_mid`), LoHa (`hada_*`) and LoKr (`lokr_*`) factors, a `dora_scale` along the input axis or with the wrong first
+    dimension, a magnitude without its factors.  Applying the rest of such a file would merge something its author never
+    trained, so `strict=False` in `LoraSet.load` does not turn these into a list either; the same keys on modules that are
+    not listed (a conv key with the Linear names alone) stay in `unplaced` as before."""
+    placed, unplaced = parse_adapter(sd, module_names)
+    return {n: (p.down, p.up, p.alpha) for n, p in placed.items()}, unplaced
+
+
+def parse_adapter(sd: Mapping[str, torch.Tensor], module_names) -> Tuple[Dict[str, Placed], List[str]]:
+    """Place a LoRA state dict on the modules named by `module_names`: the model's own `nn.Linear` (and, for conv adapters,
+    `nn.Conv2d`) names, or a mapping from those names to the weights' shapes, with which every placed adapter is also checked
+    against its target (`check_shapes`).
+
+    Returns `(placed, unplaced)`: `placed[name] = Placed(down, up, alpha, magnitude)` - down (r, K) and up (N, r), or
+    (r, I, R, S) and (O, r, 1, 1) for a convolution; magnitude None for a plain adapter - `unplaced` the keys that name no target
+    (modules not listed, other networks, text encoders - `is_text_encoder_key` tells the latter apart).  Spellings:
       PEFT / diffusers      <path>.lora_A.weight, <path>.lora_B.weight  [, <path>.alpha]
+                            <path>.lora_magnitude_vector[.<adapter>][.weight]
       older diffusers       <attn>.to_q_lora.down.weight / .up.weight, with or without `.processor`; <path>.lora.down.weight
-      kohya                 lora_unet_<path with underscores>.lora_down.weight / .lora_up.weight / .alpha
+      kohya / LyCORIS       lora_unet_<path with underscores>.lora_down.weight / .lora_up.weight / .alpha / .dora_scale
     An optional `unet.` prefix is dropped.  kohya's underscores are resolved against the module names themselves
-    (`name.replace(".", "_")`), never by guessing where the dots were.  `alpha` defaults to the rank."""
+    (`name.replace(".", "_")`), never by guessing where the dots were.  `alpha` defaults to the rank.  A `dora_scale` along
+    the input axis (first dimension 1, more than one element) and Tucker / LoHa / LoKr keys on a listed module are errors.
+    A PEFT magnitude may have any shape of N elements; a kohya `dora_scale` has N (the rows of its up factor) as its first
+    dimension, anything else is an error."""
+    shapes = module_names if isinstance(module_names, Mapping) else None
     names = set(module_names)
     flat: Dict[str, str] = {}
     for n in names:
@@ -93,7 +152,12 @@ def parse_lora_state_dict(sd: Mapping[str, torch.Tensor], module_names: Iterable
         slot = parts.setdefault(name, {})
         if what in slot:
             raise ValueError(f"{name}: the state dict holds two {what} entries (the second is {key!r})")
+        if what == "magnitude" and key.endswith(".dora_scale") and val.dim() > 1 and val.shape[0] == 1 and val.numel() > 1:
+            raise ValueError(f"{name}: {key!r} has shape {tuple(val.shape)}: a DoRA magnitude along the input axis (LyCORIS's "
+                             "other decomposition) is not supported, only one value per output row / channel")
         slot[what] = val
+        if what == "magnitude":
+            slot["kohya_magnitude"] = key.endswith(".dora_scale")
     placed = {}
     for name, p in parts.items():
         if "down" not in p or "up" not in p:
@@ -102,21 +166,43 @@ def parse_lora_state_dict(sd: Mapping[str, torch.Tensor], module_names: Iterable
         if down.dim() == 4 and tuple(down.shape[2:]) == (1, 1) and up.dim() == 4 and tuple(up.shape[2:]) == (1, 1):
             down, up = down[:, :, 0, 0], up[:, :, 0, 0]          # a Linear that another exporter wrote as a 1x1 convolution
         alpha = float(p["alpha"]) if "alpha" in p else float(down.shape[0])
-        placed[name] = (down, up, alpha)
+        placed[name] = Placed(down, up, alpha, p.get("magnitude"))
+        if p.get("kohya_magnitude") and (p["magnitude"].dim() == 0 or p["magnitude"].shape[0] != up.shape[0]):
+            raise ValueError(f"{name}: a dora_scale has the output rows / channels ({up.shape[0]}) as its first dimension; "
+                             f"got shape {tuple(p['magnitude'].shape)}")
+        if shapes is not None:
+            check_shapes(name, tuple(shapes[name]), down, up, p.get("magnitude"))
     return placed, unplaced
 
 
-def check_shapes(name: str, weight_shape, down: torch.Tensor, up: torch.Tensor) -> int:
-    """up is (N, r), down is (r, K), r at most MAX_RANK; returns r."""
-    n, k = weight_shape
-    if down.dim() != 2 or up.dim() != 2:
-        raise ValueError(f"{name}: LoRA factors must be 2-D, got down {tuple(down.shape)} and up {tuple(up.shape)}")
-    r = down.shape[0]
+def check_shapes(name: str, weight_shape, down: torch.Tensor, up: torch.Tensor, magnitude: Optional[torch.Tensor] = None) -> int:
+    """A Linear weight (N, K) takes up (N, r) and down (r, K); a conv weight (O, I, R, S) takes up (O, r, 1, 1) and down
+    (r, I, R, S) (2-D factors stand for 1x1 ones); r at most MAX_RANK; a magnitude has N (O) elements (the parser
+    also holds kohya's `dora_scale` to N as its first dimension).  Returns r."""
+    if len(weight_shape) == 4:
+        o, i, kr, ks = weight_shape
+        down4 = down[:, :, None, None] if down.dim() == 2 else down
+        up4 = up[:, :, None, None] if up.dim() == 2 else up
+        if down4.dim() != 4 or up4.dim() != 4:
+            raise ValueError(f"{name}: conv LoRA factors must be 4-D, got down {tuple(down.shape)} and up {tuple(up.shape)}")
+        if tuple(down4.shape[2:]) != (kr, ks):
+            raise ValueError(f"{name}: the down factor's kernel {tuple(down4.shape[2:])} differs from the convolution's {(kr, ks)}")
+        r = down4.shape[0]
+        ok = tuple(down4.shape) == (r, i, kr, ks) and tuple(up4.shape) == (o, r, 1, 1)
+        n, want = o, f"a {(o, i, kr, ks)} conv weight takes down ({r}, {i}, {kr}, {ks}) and up ({o}, {r}, 1, 1)"
+    else:
+        n, k = weight_shape
+        if down.dim() != 2 or up.dim() != 2:
+            raise ValueError(f"{name}: LoRA factors must be 2-D, got down {tuple(down.shape)} and up {tuple(up.shape)}")
+        r = down.shape[0]
+        ok = tuple(down.shape) == (r, k) and tuple(up.shape) == (n, r)
+        want = f"a ({n}, {k}) weight takes down ({r}, {k}) and up ({n}, {r})"
     if r < 1 or r > MAX_RANK:
         raise ValueError(f"{name}: rank {r} is outside 1 .. {MAX_RANK}")
-    if tuple(down.shape) != (r, k) or tuple(up.shape) != (n, r):
-        raise ValueError(f"{name}: a ({n}, {k}) weight takes down ({r}, {k}) and up ({n}, {r}); got down {tuple(down.shape)} "
-                         f"and up {tuple(up.shape)}")
+    if not ok:
+        raise ValueError(f"{name}: {want}; got down {tuple(down.shape)} and up {tuple(up.shape)}")
+    if magnitude is not None and magnitude.numel() != n:
+        raise ValueError(f"{name}: a DoRA magnitude has one value per output row ({n}); got shape {tuple(magnitude.shape)}")
     return r
 
 
@@ -124,17 +210,36 @@ def target_linears(module: nn.Module) -> "OrderedDict[str, nn.Linear]":
     """The module's `nn.Linear` submodules under the names an adapter uses.  A compiled module also holds its hoisted
     context / time sub-graphs, which reference the same Linear objects: each object is listed once, under its first (own)
     name.  A wrapper that keeps the network in `.unet` (the label-vector entry) does not add its prefix."""
+    return target_modules(module, convs=False)
+
+
+def target_modules(module: nn.Module, convs: bool) -> "OrderedDict[str, nn.Module]":
+    """`target_linears`, and with `convs` also the module's `nn.Conv2d` submodules, under the same naming rule."""
+    kinds = (nn.Linear, nn.Conv2d) if convs else nn.Linear
     out = OrderedDict()
     for name, m in module.named_modules():
-        if isinstance(m, nn.Linear):
+        if isinstance(m, kinds):
             out[name[len("unet."):] if name.startswith("unet.") else name] = m
     return out
+
+
+def weight_rows(w: torch.Tensor) -> Tuple[torch.Tensor, bool]:
+    """The row-major (N, K) view of a weight's own memory, and whether K runs (R, S, I) - a channels_last conv weight - and
+    not (I, R, S).  A Linear weight is its own view."""
+    if w.dim() == 2:
+        return w, False
+    nhwc = w.permute(0, 2, 3, 1)
+    if nhwc.is_contiguous():
+        return nhwc.reshape(w.shape[0], -1), True
+    if w.is_contiguous():
+        return w.reshape(w.shape[0], -1), False
+    raise ValueError(f"a conv weight must be dense, channels_last or contiguous; got strides {w.stride()} for {tuple(w.shape)}")
 
 
 class _Adapter:
     def __init__(self, slot: int, scale: float):
         self.slot, self.scale = slot, scale
-        self.factors: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}      # module -> (Up (N, rp), DownT (K, rp)), zero-padded ranks
+        self.factors: Dict[str, tuple] = {}      # module -> (Up (N, rp), DownT (K, rp)[, magnitude (N,) fp32]), zero-padded ranks
 
 
 class LoraSet:
@@ -154,6 +259,7 @@ class LoraSet:
         self.linears = target_linears(module)
         if not self.linears:
             raise ValueError("LoraSet: the module has no nn.Linear to adapt")
+        self.targets = target_modules(module, convs=True)      # what `load(convs=True)` may name; `linears` is the default
         ectx = getattr(module, "exec_context", None)
         self.on_change = on_change if on_change is not None else ((lambda: ectx.refresh_derived(full=True)) if ectx is not None else None)
         self._adapters: "OrderedDict[str, _Adapter]" = OrderedDict()
@@ -178,30 +284,46 @@ class LoraSet:
         return self._global
 
     # ---- changes -------------------------------------------------------------------------------
-    def load(self, name: str, state_dict: Mapping[str, torch.Tensor], scale: float = 1.0, strict: bool = True) -> List[str]:
+    def load(self, name: str, state_dict: Mapping[str, torch.Tensor], scale: float = 1.0, strict: bool = True,
+             convs: bool = False) -> List[str]:
         """Merge the adapter `state_dict` under `name` at `scale`.  Everything is checked before anything is written.
-        Returns the keys that were not applied (text-encoder keys always; with strict=False also keys that name no Linear
-        of this module, which strict=True refuses)."""
+        `convs=True` also takes the adapter's convolution factors (LoCon) on this module's `nn.Conv2d`; DoRA magnitudes are
+        applied wherever their module is a target.  Returns the keys that were not applied (text-encoder keys always; with
+        strict=False also keys that name no target of this module, which strict=True refuses).  Tucker / LoHa / LoKr keys and
+        input-axis magnitudes ON a target raise whatever `strict` says (`parse_lora_state_dict`)."""
         if name in self._adapters:
             raise ValueError(f"a LoRA named {name!r} is already loaded (unload it first)")
         if len(self._adapters) >= MAX_ADAPTERS:
             raise ValueError(f"at most {MAX_ADAPTERS} adapters can be loaded at once")
-        placed, unplaced = parse_lora_state_dict(state_dict, self.linears.keys())
+        targets = self.targets if convs else self.linears
+        kind = "nn.Linear or nn.Conv2d" if convs else "nn.Linear"
+        placed, unplaced = parse_adapter(state_dict, targets.keys())
         foreign = [k for k in unplaced if not is_text_encoder_key(k)]
         if strict and foreign:
-            raise ValueError(f"LoRA {name!r}: {len(foreign)} keys name no nn.Linear of this model (convolution adapters are not "
-                             f"supported; pass strict=False to load the rest): {foreign[:8]}{' ...' if len(foreign) > 8 else ''}")
+            hint = "" if convs else "convolution adapters are only applied on request: pass convs=True; "
+            raise ValueError(f"LoRA {name!r}: {len(foreign)} keys name no {kind} of this model ({hint}"
+                             f"pass strict=False to load the rest): {foreign[:8]}{' ...' if len(foreign) > 8 else ''}")
         if not placed:
-            raise ValueError(f"LoRA {name!r}: no key names an nn.Linear of this model")
-        for mod, (down, up, _) in placed.items():
-            check_shapes(mod, tuple(self.linears[mod].weight.shape), down, up)
+            raise ValueError(f"LoRA {name!r}: no key names an {kind} of this model")
+        for mod, p in placed.items():
+            m = targets[mod]
+            if isinstance(m, nn.Conv2d) and (m.groups != 1 or tuple(m.dilation) != (1, 1)):
+                raise ValueError(f"{mod}: a grouped or dilated convolution (groups {m.groups}, dilation {tuple(m.dilation)}) takes no adapter")
+            check_shapes(mod, tuple(m.weight.shape), p.down, p.up, p.magnitude)
+            if isinstance(m, nn.Conv2d):
+                weight_rows(m.weight)                                  # (refuses a weight that is not dense)
         scale = float(scale)
         slot = min(set(range(MAX_ADAPTERS)) - {a.slot for a in self._adapters.values()})
         ad = _Adapter(slot, scale)
         with torch.no_grad():
-            for mod, (down, up, alpha) in placed.items():
-                w = self.linears[mod].weight
+            for mod, p in placed.items():
+                down, up, alpha = p.down, p.up, p.alpha
+                w, nhwc = weight_rows(targets[mod].weight.detach())
                 r = down.shape[0]
+                if len(targets[mod].weight.shape) == 4:               # the down factor in the K order of the weight's memory
+                    down = down[:, :, None, None] if down.dim() == 2 else down
+                    down = (down.permute(0, 2, 3, 1) if nhwc else down).reshape(r, -1)
+                    up = up.reshape(up.shape[0], r)
                 mult = 4 if w.dtype == torch.float32 else 32
                 rp = -(-r // mult) * mult
                 up_p = torch.zeros((w.shape[0], rp), dtype=w.dtype, device=w.device)
@@ -209,8 +331,10 @@ class LoraSet:
                 up_p[:, :r] = (up.to(device=w.device, dtype=torch.float32) * (alpha / r)).to(w.dtype)
                 down_t[:, :r] = down.to(device=w.device, dtype=w.dtype).t()
                 ad.factors[mod] = (up_p, down_t)
+                if p.magnitude is not None:
+                    ad.factors[mod] += (p.magnitude.detach().to(device=w.device, dtype=torch.float32).reshape(-1).contiguous(),)
                 if mod not in self._base:
-                    self._base[mod] = w.detach().clone(memory_format=torch.contiguous_format)
+                    self._base[mod] = w.clone(memory_format=torch.contiguous_format)
         self._adapters[name] = ad
         self._plan = None
         self._merge()
@@ -270,11 +394,13 @@ class LoraSet:
         return eff
 
     def _entries(self):
-        """Per snapshotted module: (weight, base, [(Up, DownT, slot), ...]) in load order (the kernel's summation order)."""
+        """Per snapshotted module: (parameter, its (N, K) view, base, [(Up, DownT, slot[, magnitude]), ...]) in load order (the
+        kernel's summation order)."""
         out = []
         for mod, base in self._base.items():
-            facs = [(*a.factors[mod], a.slot) for a in self._adapters.values() if mod in a.factors]
-            out.append((self.linears[mod].weight, base, facs))
+            facs = [(*a.factors[mod][:2], a.slot, *a.factors[mod][2:]) for a in self._adapters.values() if mod in a.factors]
+            param = self.targets[mod].weight
+            out.append((param, weight_rows(param.detach())[0], base, facs))
         return out
 
     def _merge(self) -> None:
@@ -282,38 +408,52 @@ class LoraSet:
             return
         eff = self._effective()
         entries = self._entries()
-        w0 = entries[0][0]
+        w0 = entries[0][1]
         with torch.no_grad():
             if w0.device.type == "cuda":
                 from . import ops
-                if any(not w.is_contiguous() for w, _, _ in entries):
+                if any(not w.is_contiguous() for _, w, _, _ in entries):
                     raise ops.BackendError("LoraSet: an adapted weight is not contiguous")
                 if self._scales is None:
                     self._scales = torch.zeros(MAX_ADAPTERS, dtype=torch.float32, device=w0.device)
                 if self._plan is None:
-                    self._plan = ops.lora_plan([(w.detach(), b, f) for w, b, f in entries])
+                    self._plan = ops.lora_plan([(w, b, f) for _, w, b, f in entries])
                 self._scales.copy_(torch.tensor(eff, dtype=torch.float32))
                 ops.lora_merge(self._plan, self._scales)
             else:
-                for w, base, facs in entries:
+                for _, w, base, facs in entries:
                     _merge_torch(w, base, facs, eff)
-        for w, _, _ in entries:
-            torch.autograd.graph.increment_version(w)
+        for param, _, _, _ in entries:
+            torch.autograd.graph.increment_version(param)
         if self.on_change is not None:
             self.on_change()
 
 
 def _merge_torch(w: torch.Tensor, base: torch.Tensor, facs, eff) -> None:
     """The kernel's formula in torch (CPU): fp32 products and sums, one rounding to the storage dtype, base bits when every
-    scale is zero."""
-    live = [(up, down_t, eff[slot]) for up, down_t, slot in facs if eff[slot] != 0.0]
+    scale is zero.  `w` is the weight's (N, K) view; a factor tuple is (Up, DownT, slot) or (Up, DownT, slot, magnitude)."""
+    live = [(f[0], f[1], eff[f[2]], f[3] if len(f) > 3 else None) for f in facs if eff[f[2]] != 0.0]
     if not live:
         w.detach().copy_(base)
         return
     delta = torch.zeros(w.shape, dtype=torch.float32)
-    for up, down_t, s in live:
-        delta.add_(up.float() @ down_t.float().t(), alpha=s)
-    w.detach().copy_((base.float() + delta).to(w.dtype))
+    if all(mag is None for _, _, _, mag in live):
+        for up, down_t, s, _ in live:
+            delta.add_(up.float() @ down_t.float().t(), alpha=s)
+        w.detach().copy_((base.float() + delta).to(w.dtype))
+        return
+    b = base.float()
+    bcoef = torch.ones((w.shape[0], 1), dtype=torch.float32)
+    for up, down_t, s, mag in live:
+        acc = up.float() @ down_t.float().t()
+        if mag is None:
+            delta.add_(acc, alpha=s)
+            continue
+        ss = (b + s * acc).pow(2).sum(dim=1)
+        gain = torch.where(ss > 0, mag / ss.sqrt(), torch.zeros_like(ss))[:, None]      # m / ||Base + s Up Down|| per row; 0 for a zero row
+        bcoef += gain - 1.0
+        delta += (gain * s) * acc
+    w.detach().copy_((bcoef * b + delta).to(w.dtype))
 
 
 def attach(compiled: nn.Module) -> LoraSet:

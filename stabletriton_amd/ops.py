@@ -1467,18 +1467,32 @@ def lora_rank_multiple(dtype: torch.dtype) -> int:
 
 class LoraPlan:
     """Descriptor table, segment table and flat tile list of one set of targets, on the device.  Built once per load / unload;
-    a scale change reuses it.  Holds every tensor the tables point at."""
+    a scale change reuses it.  Holds every tensor the tables point at.  `dora`: some segment carries a magnitude; the plan then
+    has 6-word segment rows, the tile list of the norm pass and its workspace (st_lora_merge_dora)."""
 
-    def __init__(self, targets, segments, tiles, n_targets, n_segments, n_tiles, n_slots, max_rank, dtype, keep):
+    def __init__(self, targets, segments, tiles, n_targets, n_segments, n_tiles, n_slots, max_rank, dtype, keep,
+                 norm_tiles=None, workspace=None):
         self.targets, self.segments, self.tiles = targets, segments, tiles
         self.n_targets, self.n_segments, self.n_tiles, self.n_slots, self.max_rank = n_targets, n_segments, n_tiles, n_slots, max_rank
         self.dtype, self.keep = dtype, keep
+        self.norm_tiles, self.workspace = norm_tiles, workspace
+        self.dora = workspace is not None
+
+
+def _lora_tiles(counts, which) -> torch.Tensor:
+    """[target, tile] rows (int32) of the targets in `which`, in order."""
+    cnt = torch.tensor([counts[t] for t in which], dtype=torch.int64)
+    first = torch.cumsum(cnt, 0) - cnt
+    idx = torch.repeat_interleave(torch.arange(len(which), dtype=torch.int64), cnt)
+    tgt = torch.tensor(which, dtype=torch.int64)[idx]
+    return torch.stack([tgt, torch.arange(int(cnt.sum()), dtype=torch.int64) - first[idx]], dim=1).to(torch.int32).contiguous()
 
 
 def lora_plan(entries) -> LoraPlan:
-    """`entries`: one (weight, base, [(up, down_t, slot), ...]) per target.  weight / base: (N, K) contiguous, same dtype,
-    distinct storage; up: (N, rp), down_t: (K, rp) - the down factor transposed - contiguous in the weight's dtype with rp a
-    multiple of lora_rank_multiple(dtype) (zero padding).  A target with no factors is restored to its base by the launch."""
+    """`entries`: one (weight, base, [(up, down_t, slot) or (up, down_t, slot, magnitude), ...]) per target.  weight / base:
+    (N, K) contiguous, same dtype, distinct storage; up: (N, rp), down_t: (K, rp) - the down factor transposed - contiguous in
+    the weight's dtype with rp a multiple of lora_rank_multiple(dtype) (zero padding); magnitude: None, or the DoRA magnitude
+    of the segment, N fp32 values on the device (any shape).  A target with no factors is restored to its base by the launch."""
     if not entries:
         raise BackendError("lora_plan: no targets")
     w0 = entries[0][0]
@@ -1486,6 +1500,7 @@ def lora_plan(entries) -> LoraPlan:
     _C.dtype_code(dtype)
     mult = lora_rank_multiple(dtype)
     trows, srows, counts, keep, slots = [], [], [], [], 0
+    ws_floats, norm_targets = 0, []
     for w, base, factors in entries:
         _C.require_device(w, base)
         if w.dim() != 2 or not w.is_contiguous() or w.dtype != dtype or w.device != device:
@@ -1495,8 +1510,11 @@ def lora_plan(entries) -> LoraPlan:
         if base.data_ptr() == w.data_ptr():
             raise BackendError("lora_plan: a base snapshot aliases its weight")
         n, k = w.shape
+        tiles_k = -(-k // _C.LORA_TILE_K)
         trows.append([w.data_ptr(), base.data_ptr(), n, k, len(srows), len(factors)])
-        for up, down_t, slot in factors:
+        for fac in factors:
+            up, down_t, slot = fac[:3]
+            mag = fac[3] if len(fac) > 3 else None
             _C.require_device(up, down_t)
             rp = up.shape[-1]
             if (tuple(up.shape) != (n, rp) or tuple(down_t.shape) != (k, rp) or rp == 0 or rp % mult or up.dtype != dtype
@@ -1506,26 +1524,47 @@ def lora_plan(entries) -> LoraPlan:
                                    f"{dtype}, rp a multiple of {mult}; got {tuple(up.shape)} {up.dtype} and {tuple(down_t.shape)} {down_t.dtype}")
             if rp > LORA_MAX_RANK or slot < 0:
                 raise BackendError(f"lora_plan: padded rank {rp} (at most {LORA_MAX_RANK}) / scale slot {slot}")
-            srows.append([up.data_ptr(), down_t.data_ptr(), rp, slot])
+            row = [up.data_ptr(), down_t.data_ptr(), rp, slot, 0, 0]
+            if mag is not None:
+                _C.require_device(mag)
+                if mag.dtype != torch.float32 or mag.numel() != n or not mag.is_contiguous() or mag.device != device:
+                    raise BackendError(f"lora_plan: the magnitude of a {(n, k)} weight must be {n} contiguous fp32 values on {device}; "
+                                       f"got {tuple(mag.shape)} {mag.dtype}")
+                row[4:] = [mag.data_ptr(), ws_floats]
+                ws_floats += n * tiles_k
+                if not norm_targets or norm_targets[-1] != len(trows) - 1:
+                    norm_targets.append(len(trows) - 1)
+                keep.append(mag)
+            srows.append(row)
             slots = max(slots, slot + 1)
             keep += [up, down_t]
-        counts.append(-(-n // _C.LORA_TILE_N) * -(-k // _C.LORA_TILE_K))
+        counts.append(-(-n // _C.LORA_TILE_N) * tiles_k)
         keep += [w, base]
-    cnt = torch.tensor(counts, dtype=torch.int64)
-    first = torch.cumsum(cnt, 0) - cnt
-    tgt = torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int64), cnt)
-    tiles = torch.stack([tgt, torch.arange(int(cnt.sum()), dtype=torch.int64) - first[tgt]], dim=1).to(torch.int32).contiguous()
-    segments = torch.tensor(srows, dtype=torch.int64).reshape(-1, 4).to(device) if srows else None
-    return LoraPlan(torch.tensor(trows, dtype=torch.int64).to(device), segments, tiles.to(device), len(trows), len(srows),
-                    tiles.shape[0], slots, max((r[2] for r in srows), default=0), dtype, keep)
+    tiles = _lora_tiles(counts, list(range(len(counts))))
+    args = (len(trows), len(srows), tiles.shape[0], slots, max((r[2] for r in srows), default=0), dtype, keep)
+    targets = torch.tensor(trows, dtype=torch.int64).to(device)
+    if not norm_targets:           # no DoRA segment: the 4-word rows of st_lora_merge
+        segments = torch.tensor([r[:4] for r in srows], dtype=torch.int64).reshape(-1, 4).to(device) if srows else None
+        return LoraPlan(targets, segments, tiles.to(device), *args)
+    segments = torch.tensor(srows, dtype=torch.int64).reshape(-1, 6).to(device)
+    return LoraPlan(targets, segments, tiles.to(device), *args, norm_tiles=_lora_tiles(counts, norm_targets).to(device),
+                    workspace=torch.empty(ws_floats, dtype=torch.float32, device=device))
 
 
 def lora_merge(plan: LoraPlan, scales: torch.Tensor) -> None:
-    """Rebuild every target of `plan` from its base: W = round(base + sum_j scales[slot_j] * up_j @ down_j), one launch.
+    """Rebuild every target of `plan` from its base: W = round(base + sum_j scales[slot_j] * up_j @ down_j), one launch; with
+    DoRA segments in the plan W = round(base + sum_j (g_j V_j - base)), V_j = base + scales[slot_j] * up_j @ down_j and
+    g_j[n] = magnitude_j[n] / ||V_j[n]|| (1 for a plain segment), two launches (row norms, then the merge).
     Writes through raw pointers: the caller bumps the version counters of the rewritten parameters."""
     _C.require_device(scales)
     if scales.dtype != torch.float32 or not scales.is_contiguous() or scales.numel() < max(plan.n_slots, 1) or scales.device != plan.targets.device:
         raise BackendError(f"lora_merge: scales must be a contiguous fp32 device table of at least {max(plan.n_slots, 1)} slots")
+    if plan.dora:
+        _C.check(_C.load().st_lora_merge_dora(plan.targets.data_ptr(), plan.n_targets, plan.segments.data_ptr(), plan.n_segments, plan.max_rank,
+                                              plan.tiles.data_ptr(), plan.n_tiles, plan.norm_tiles.data_ptr(), plan.norm_tiles.shape[0],
+                                              scales.data_ptr(), scales.numel(), plan.workspace.data_ptr(), plan.workspace.numel() * 4,
+                                              _C.dtype_code(plan.dtype), _C.stream_ptr()), "lora_merge")
+        return
     _C.check(_C.load().st_lora_merge(plan.targets.data_ptr(), plan.n_targets, _ptr(plan.segments), plan.n_segments, plan.max_rank,
                                      plan.tiles.data_ptr(),
                                      plan.n_tiles, scales.data_ptr(), scales.numel(), _C.dtype_code(plan.dtype), _C.stream_ptr()),

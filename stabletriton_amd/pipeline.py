@@ -30,7 +30,7 @@ draw the same noise and every replay repeats its bits.  `set_seed` writes the se
 also starts any sampler without a host tensor: `denoise(seed=s)` takes the initial noise from the same generator
 (counter word 0).  Euler and DPM++ loops allocate the seed table only when a seed is used, and their graph never reads it.
 
-LoRA adapters (`load_lora`, `set_lora_scale`, `unload_lora`; lora.py) are merged into the UNet's Linear weights in place by
+LoRA adapters (`load_lora`, `set_lora_scale`, `unload_lora`; lora.py) are merged into the UNet's Linear (with `convs=True` also Conv2d) weights in place by
 one grouped kernel launch.  The weights keep their addresses, so the captured graph stays; the loop re-derives, in place,
 what it had computed from them: derived weights, the hoisted text-context K/V and the time tables.
 
@@ -245,11 +245,12 @@ class DenoiseLoop:
         else:
             self.refresh_weights()
 
-    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True):
+    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True, convs: bool = False):
         """Merge a LoRA state dict (PEFT / diffusers / kohya keys, lora.parse_lora_state_dict) into the UNet at `scale`.
+        DoRA magnitudes apply; `convs=True` also takes the adapter's convolution factors (LoCon) on the UNet's Conv2d.
         Returns the keys that were not applied.  A loop that shares its UNet with another owner shares the adapters; the
         other owner re-derives its own per-prompt state (its next set_conditioning does)."""
-        left = self._lora_set().load(name, state_dict, scale, strict)
+        left = self._lora_set().load(name, state_dict, scale, strict, convs)
         self._weights_changed()
         return left
 

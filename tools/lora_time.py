@@ -1,14 +1,19 @@
 """What one LoRA scale change costs on SDXL-base bf16: `DenoiseLoop.set_lora_scale` with a synthetic adapter on every
 transformer-block Linear (attention projections, feed-forward, proj_in / proj_out), at rank 16 and at rank 128.
 
-    python tools/lora_time.py [--ranks 16 128] [--runs 7] [--spec sdxl|tiny] [--out lora_time.json]
+    python tools/lora_time.py [--ranks 16 128] [--runs 7] [--spec sdxl|tiny] [--convs] [--dora] [--out lora_time.json]
+
+`--convs` puts the adapter on EVERY Linear and every Conv2d of the UNet (LoCon; `load_lora(convs=True)`), `--dora` gives every
+adapted module a magnitude, so that the merge is the two-launch DoRA form (row norms, then the merge).
 
 Per rank, one JSON object:
   kernel_ms        the grouped merge launch alone (device events), and `floor_ms`: its own traffic - bytes of base read plus
                    weight written, from the target list - at 6.3 TB/s, the achievable HBM rate
   call_ms          the whole `set_lora_scale` call: scale-table copy, merge, version bumps, derived-weight refresh, and the
                    loop's hoisted text K/V and time tables recomputed in place (`rederive_ms`: that last part alone)
-  torch_merge_ms   the same update the old way: per module `W.copy_(base + s * up @ down)` in torch
+                   with --dora the two launches together; `norm_read_gb` is what the norm pass adds to the traffic (the base
+                   read once more; its partial sums are 1/64 of that), counted in `floor_ms`
+  torch_merge_ms   the same update the old way: per module `W.copy_(base + s * up @ down)` in torch (plain adapters only: null with --dora, as is torch_route_ms)
   torch_route_ms   ... followed by `refresh_weights()`, the surface before load_lora existed (which left the hoisted K/V and
                    the time tables to the next set_conditioning)
 The two routes alternate in one process, host clock around a device synchronise, after one warm-up of each; medians.
@@ -34,15 +39,19 @@ from stabletriton_amd.unet import SDXL_BASE, TINY, UNet2DConditionModel  # noqa:
 HBM_ACHIEVABLE = 6.3e12      # bytes / s
 
 
-def synthetic_adapter(linears, rank, seed, device):
+def synthetic_adapter(targets, rank, seed, device, everything=False, dora=False):
+    """On the transformer-block Linears, or with `everything` on every module of `targets`; with `dora` a magnitude per module."""
     g = torch.Generator(device=device).manual_seed(seed)
     sd = {}
-    for name, lin in linears.items():
-        if "attentions" not in name:
+    for name, mod in targets.items():
+        if not everything and "attentions" not in name:
             continue
-        n, k = lin.weight.shape
-        sd[f"unet.{name}.lora_A.weight"] = torch.randn((rank, k), generator=g, device=device) * 0.02
-        sd[f"unet.{name}.lora_B.weight"] = torch.randn((n, rank), generator=g, device=device) * 0.02
+        shape = tuple(mod.weight.shape)
+        r = min(rank, shape[1] * (shape[2] * shape[3] if len(shape) == 4 else 1))
+        sd[f"unet.{name}.lora_A.weight"] = torch.randn((r, *shape[1:]), generator=g, device=device) * 0.02
+        sd[f"unet.{name}.lora_B.weight"] = torch.randn((shape[0], r, *([1, 1] if len(shape) == 4 else [])), generator=g, device=device) * 0.02
+        if dora:
+            sd[f"unet.{name}.lora_magnitude_vector"] = mod.weight.detach().float().reshape(shape[0], -1).norm(dim=1)
     return sd
 
 
@@ -59,6 +68,8 @@ def main():
     ap.add_argument("--ranks", type=int, nargs="+", default=[16, 128])
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--spec", choices=("sdxl", "tiny"), default="sdxl")
+    ap.add_argument("--convs", action="store_true", help="adapt every Linear and every Conv2d (LoCon)")
+    ap.add_argument("--dora", action="store_true", help="give every adapted module a DoRA magnitude")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -77,12 +88,15 @@ def main():
     with torch.no_grad():
         loop.set_conditioning(*(c[1:2] for c in cond), *(c[0:1] for c in cond))
         for rank in args.ranks:
-            sd = synthetic_adapter(ls.linears, rank, rank, dev)
-            load_ms = timed(lambda: loop.load_lora("probe", sd, 1.0), dev)
+            sd = synthetic_adapter(ls.targets if args.convs else ls.linears, rank, rank, dev, everything=args.convs, dora=args.dora)
+            load_ms = timed(lambda: loop.load_lora("probe", sd, 1.0, convs=args.convs), dev)
             mods = ls.adapted_modules()
-            traffic = sum(2 * ls.linears[n].weight.numel() * ls.linears[n].weight.element_size() for n in mods)
+            weight_bytes = sum(ls.targets[n].weight.numel() * ls.targets[n].weight.element_size() for n in mods)
+            norm_read = weight_bytes if args.dora else 0             # the norm pass reads every base once more
+            traffic = 2 * weight_bytes + norm_read
             ad = ls._adapters["probe"]
-            old_way = [(ls.linears[n].weight, ls._base[n], ad.factors[n][0], ad.factors[n][1].t().contiguous()) for n in mods]
+            old_way = [(lora.weight_rows(ls.targets[n].weight)[0], ls._base[n], ad.factors[n][0], ad.factors[n][1].t().contiguous())
+                       for n in mods]
 
             def torch_merge(s):
                 for w, base, up, down in old_way:
@@ -103,18 +117,21 @@ def main():
                 torch.cuda.synchronize(dev)
                 k = ev[0].elapsed_time(ev[1])
                 r = timed(loop._rederive_conditioning, dev)
-                tm = timed(lambda: torch_merge(s), dev)
-                tr = timed(lambda: torch_route(s), dev)
+                # (no do-it-yourself DoRA route exists to compare with: both figures are null under --dora)
+                tm = None if args.dora else timed(lambda: torch_merge(s), dev)
+                tr = None if args.dora else timed(lambda: torch_route(s), dev)
                 if i:
                     kernel.append(k); call.append(c); rederive.append(r); t_merge.append(tm); t_route.append(tr)
             finite = all(bool(torch.isfinite(t).all()) for t in loop.ctx)
             loop.unload_lora("probe")
             med = statistics.median
-            results.append({"rank": rank, "modules": len(mods), "traffic_gb": round(traffic / 1e9, 3),
+            results.append({"rank": rank, "modules": len(mods), "convs": args.convs, "dora": args.dora,
+                            "traffic_gb": round(traffic / 1e9, 3), "norm_read_gb": round(norm_read / 1e9, 3),
                             "floor_ms": round(traffic / HBM_ACHIEVABLE * 1e3, 3), "kernel_ms": round(med(kernel), 3),
                             "kernel_ms_min": round(min(kernel), 3), "kernel_x_floor": round(med(kernel) / (traffic / HBM_ACHIEVABLE * 1e3), 2),
                             "call_ms": round(med(call), 2), "rederive_ms": round(med(rederive), 2),
-                            "torch_merge_ms": round(med(t_merge), 2), "torch_route_ms": round(med(t_route), 2),
+                            "torch_merge_ms": None if args.dora else round(med(t_merge), 2),
+                            "torch_route_ms": None if args.dora else round(med(t_route), 2),
                             "load_ms": round(load_ms, 1), "finite": finite})
     line = json.dumps({"tool": "lora_time", "spec": args.spec, "dtype": "bf16", "runs": args.runs, "results": results})
     print(line)
