@@ -58,6 +58,7 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
                                               st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
                                               st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then st_lora_merge_dora,
+                                              and then st_lora_merge_forms,
                                               added without a bump: new entry points, no existing signature or contract changed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
@@ -307,6 +308,30 @@ int st_lora_merge(const long long* targets, int n_targets, const long long* segm
 int st_lora_merge_dora(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
                        const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
                        float* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* The same merge with segments of other factorisations (LyCORIS's LoHa and LoKr; Tucker cores are contracted by the caller).
+ * A segment has a kind, which only decides how its fp32 delta acc_j is formed; the rest is st_lora_merge_dora's:
+ *   V_j = fp32(Base_t) + s_j acc_j,  g_j as there,  W_t = round( (1 + sum_j (g_j - 1)) fp32(Base_t) + sum_j g_j s_j acc_j ).
+ *   ST_LORA_KIND_PLAIN  acc[n][k] = sum_r Up[n][r] DownT[k][r]
+ *   ST_LORA_KIND_HADA   acc[n][k] = (sum_r Up1[n][r] DownT1[k][r]) * (sum_r Up2[n][r] DownT2[k][r])      one fp32 product of the two sums
+ *   ST_LORA_KIND_KRON   acc[n][k] = W1[n / c][j] * W2[n % c][col],  W1 (a, b) and W2 (c, d * taps) row-major FP32 tables for
+ *                       every `dtype`, 16-byte aligned, a * c = N and b * d * taps = K.  layout 1 (a channels_last conv weight,
+ *                       K runs tap-major): k = tap * (b d) + j * d + q, col = tap * d + q.  layout 0 (a contiguous conv weight
+ *                       or a Linear, taps = 1): k = (j * d + q) * taps + tap, col = q * taps + tap.  Any scalar (alpha / rank)
+ *                       is folded into W1 by the caller.
+ * Tables as st_lora_merge_dora, except
+ *   segments: n_segments rows of ST_LORA_FORM_WORDS int64
+ *               [kind, scale slot, magnitude or 0, workspace offset,  Up1, DownT1, rp1,  Up2, DownT2, rp2,  0, 0]     PLAIN (pair 2 unused, 0) / HADA
+ *               [kind, scale slot, magnitude or 0, workspace offset,  W1, W2,  a, b, c, d, taps, layout]              KRON
+ *             factor pairs as st_lora_merge's (each padded rank a multiple of 32 / 4, at most ST_LORA_MAX_RANK);
+ *   max_rank: the largest padded rank of any factor pair in the table; 0 when every segment is KRON.
+ * The norm pass runs only when n_norm_tiles > 0 (some segment has a magnitude).  A HADA segment stages its two pairs one
+ * after the other through the same LDS images.  A table of PLAIN segments gives st_lora_merge's bits (st_lora_merge_dora's
+ * with magnitudes).  Scale 0 skips a segment whole; no atomics, a fixed order per element: bitwise deterministic. */
+enum { ST_LORA_KIND_PLAIN = 0, ST_LORA_KIND_HADA = 1, ST_LORA_KIND_KRON = 2, ST_LORA_FORM_WORDS = 12 };
+int st_lora_merge_forms(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
+                        const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
+                        float* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

@@ -57,6 +57,7 @@ SIGNATURES = {
     "st_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_lora_merge": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _i, _i, _p]),
     "st_lora_merge_dora": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _l, _p, _i, _p, _z, _i, _p]),
+    "st_lora_merge_forms": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _l, _p, _i, _p, _z, _i, _p]),
     "st_freeu_workspace_bytes": (_z, [_i, _i, _l]),
     "st_freeu_stat_rows": (_i, [_l]),
     "st_freeu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _i, _p, _z, _p]),

@@ -34,6 +34,19 @@
 // one lane's fixed-order sum followed by a fixed xor-shuffle tree, and the partials of a row are added in the same fixed
 // order by every workgroup that needs them: no atomics, two merges give the same bits.  A segment at scale 0 is skipped whole in both
 // passes, magnitude included, so "all scales zero" still copies the base's bits.
+//
+// Other factorisations (st_lora_merge_forms): a segment has a KIND, and the kind only decides how the segment's fp32 tile
+// `acc` is formed; the scale-0 skip, the DoRA norm and gain, sum = fma(coef, acc, sum) and the final rounding are shared.
+//   PLAIN  acc = Up . Down                                    (the code above)
+//   HADA   acc = (Up_1 . Down_1) (.) (Up_2 . Down_2)          LoHa: two products, multiplied elementwise in fp32.  The two
+//          factor pairs go through the SAME LDS images one after the other (one more barrier pair) and into two accumulator
+//          sets that both stay in registers; both pairs resident at rank 128 would take 102 KiB and one workgroup per CU.
+//   KRON   acc[n][k] = W1[n / c][j(k)] * W2[n % c][col(k)]    LoKr: no matrix product, no staging.  W1 (a, b) and W2
+//          (c, d taps) are small fp32 tables read through the cache.  k = tap I + j d + q for a channels_last conv weight
+//          (layout 1, I = b d), k = (j d + q) taps + tap for a contiguous one (layout 0), a Linear has one tap; col is
+//          tap d + q resp. q taps + tap, so in both layouts W2's row is read contiguously where W1's scalar is constant, and
+//          with d (layout 1) or d taps (layout 0) a multiple of the 16-byte vector one index computation serves the whole vector.
+// The new kinds live in their own kernel instantiations (FORMS); st_lora_merge and st_lora_merge_dora keep theirs.
 #include "common.h"
 
 namespace {
@@ -43,8 +56,71 @@ constexpr int LORA_TN = ST_LORA_TILE_N;      // 64: four waves of 16 rows
 constexpr int LORA_TK = ST_LORA_TILE_K;      // 128: four pairs of MFMA tiles
 constexpr int TGT_WORDS = 6;
 enum { MODE_PLAIN = 0, MODE_DORA = 1, MODE_NORM = 2 };      // st_lora_merge's kernel; the DoRA merge pass; the DoRA norm pass
-// a segment row is [Up, DownT, rp, slot] for st_lora_merge and [Up, DownT, rp, slot, magnitude or 0, workspace offset] for DoRA
-template <int MODE> struct SegRow { static constexpr int WORDS = MODE == MODE_PLAIN ? 4 : 6; };
+enum { KIND_PLAIN = ST_LORA_KIND_PLAIN, KIND_HADA = ST_LORA_KIND_HADA, KIND_KRON = ST_LORA_KIND_KRON };
+// a segment row is [Up, DownT, rp, slot] for st_lora_merge, [Up, DownT, rp, slot, magnitude or 0, workspace offset] for DoRA and
+// the ST_LORA_FORM_WORDS-word row of the header for st_lora_merge_forms
+template <int MODE, bool FORMS> struct SegRow { static constexpr int WORDS = FORMS ? (int)ST_LORA_FORM_WORDS : MODE == MODE_PLAIN ? 4 : 6; };
+
+struct Segment {
+    int kind, slot;
+    long long mag, ws;                    // magnitude (device address of N floats, or 0) and workspace offset in floats
+    const void *p0, *p1;                  // Up_1, DownT_1;  KRON: W1, W2
+    long long x[6];                       // [rp1, Up_2, DownT_2, rp2, 0, 0];  KRON: [a, b, c, d, taps, layout]
+    __device__ __forceinline__ int rp() const { return (int)x[0]; }
+    __device__ __forceinline__ const void* p2() const { return (const void*)x[1]; }
+    __device__ __forceinline__ const void* p3() const { return (const void*)x[2]; }
+    __device__ __forceinline__ int rp2() const { return (int)x[3]; }
+    __device__ __forceinline__ int b() const { return (int)x[1]; }
+    __device__ __forceinline__ int c() const { return (int)x[2]; }
+    __device__ __forceinline__ int d() const { return (int)x[3]; }
+    __device__ __forceinline__ int taps() const { return (int)x[4]; }
+    __device__ __forceinline__ int layout() const { return (int)x[5]; }
+};
+
+template <int MODE, bool FORMS>
+__device__ __forceinline__ Segment load_segment(const long long* __restrict__ segments, int j) {
+    const long long* sg = segments + (long)j * SegRow<MODE, FORMS>::WORDS;
+    Segment s;
+    if constexpr (FORMS) {
+        s.kind = (int)sg[0], s.slot = (int)sg[1], s.mag = sg[2], s.ws = sg[3];
+        s.p0 = (const void*)sg[4], s.p1 = (const void*)sg[5];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) s.x[i] = sg[6 + i];
+    } else {
+        s.kind = KIND_PLAIN;
+        s.p0 = (const void*)sg[0], s.p1 = (const void*)sg[1];
+        s.x[0] = sg[2];
+        s.x[1] = s.x[2] = s.x[3] = s.x[4] = s.x[5] = 0;
+        s.slot = (int)sg[3];
+        s.mag = MODE != MODE_PLAIN ? sg[4] : 0;
+        s.ws = MODE != MODE_PLAIN ? sg[5] : 0;
+    }
+    return s;
+}
+
+// KRON's index map for column k of the weight's (N, K) view: W1's column j and W2's column col (see the header of this file)
+struct KronMap {
+    int I, dd;      // columns per tap; consecutive columns that share W1's scalar
+    __device__ __forceinline__ KronMap(const Segment& s) : I(s.layout() ? s.b() * s.d() : s.b() * s.d() * s.taps()), dd(s.layout() ? s.d() : s.d() * s.taps()) {}
+    __device__ __forceinline__ void at(int k, int& j, int& col) const {
+        const int tap = k / I, ch = k - tap * I;
+        j = ch / dd;
+        col = tap * dd + ch - j * dd;
+    }
+    // (j, col) of column k and of the columns after it: two divisions at the start, compares and adds from there on
+    struct Walk {
+        int j, col, q, ch;
+    };
+    __device__ __forceinline__ Walk start(int k) const {
+        const int tap = k / I, ch = k - tap * I, j = ch / dd, q = ch - j * dd;
+        return Walk{j, tap * dd + q, q, ch};
+    }
+    __device__ __forceinline__ void next(Walk& w) const {
+        ++w.col, ++w.q, ++w.ch;
+        if (w.q == dd) w.q = 0, ++w.j, w.col -= dd;              // W1's next column: W2's row starts over
+        if (w.ch == I) w.ch = 0, w.j = 0, w.col += dd;           // the next tap: W1's row starts over, W2's row runs on
+    }
+};
 
 struct Target {
     char* w;
@@ -133,12 +209,75 @@ template <> struct Mfma16<f16> {
 // image row 32 p + 16 h + 4 a + b - so the 16 lanes of an operand read take 16 consecutive image rows.
 static inline int lora_lds_row(int max_rank) { return (max_rank + 8) * 2; }      // bytes
 
-template <typename T, int MODE>
+// One factor pair's product for the workgroup's tile, acc += DownT . Up^T over the pair's padded rank: the factor rows of the
+// tile are staged in the LDS images (after a barrier when an earlier product still reads them), then multiplied.
+// Both tiles are contiguous in memory (whole rows of row-major factors): coalesced 16-byte copies.  Rows past the
+// weight's edge are not read; what the image holds there only reaches outputs that are never stored.
+template <typename T>
+__device__ __forceinline__ void lora_product16(const T* __restrict__ up, const T* __restrict__ down_t, int rp, int rows_n, int rows_k,
+                                               char* lds_down, char* lds_up, int lds_row, bool& staged, f32x4 (&acc)[8]) {
+    typedef typename V16<T>::x8 frag;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+    const int chunks = rp >> 3;                                  // 16-byte chunks per factor row
+    if (staged) __syncthreads();                                // the previous product's images have been read
+    staged = true;
+    for (int q = threadIdx.x; q < rows_k * chunks; q += LORA_THREADS) {
+        const int row = q / chunks, col = q - row * chunks;
+        const int img = (row & ~31) + 16 * ((row >> 2) & 1) + 4 * ((row >> 3) & 3) + (row & 3);
+        *reinterpret_cast<frag*>(lds_down + img * lds_row + col * 16) = *reinterpret_cast<const frag*>(down_t + (long)q * 8);
+    }
+    for (int q = threadIdx.x; q < rows_n * chunks; q += LORA_THREADS) {
+        const int row = q / chunks, col = q - row * chunks;
+        *reinterpret_cast<frag*>(lds_up + row * lds_row + col * 16) = *reinterpret_cast<const frag*>(up + (long)q * 8);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int r0 = 0; r0 < rp; r0 += 32) {
+        const int col = (r0 + 8 * g) * 2;
+        const frag b = *reinterpret_cast<const frag*>(lds_up + (wave * 16 + c) * lds_row + col);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {                           // i = 2 p + h: image rows 16 i .. 16 i + 15
+            const frag a = *reinterpret_cast<const frag*>(lds_down + (16 * i + c) * lds_row + col);
+            acc[i] = Mfma16<T>::run(a, b, acc[i]);
+        }
+    }
+}
+
+// KRON: the lane's 4 x 8 values of row n (acc[2 p] and acc[2 p + 1] hold k = kb + 32 p .. + 7, as the MFMA layout leaves
+// them).  Rows and columns past the weight's edge are clamped to it: such values are never stored and count as 0 in a norm.
+__device__ __forceinline__ void kron_tile16(const Segment& sg, const Target& tg, int n, int kb, f32x4 (&acc)[8]) {
+    const KronMap map(sg);
+    n = min(n, tg.N - 1);
+    const int i1 = n / sg.c();
+    const float* __restrict__ w1 = (const float*)sg.p0 + (long)i1 * sg.b();
+    const float* __restrict__ w2 = (const float*)sg.p1 + (long)(n - i1 * sg.c()) * (sg.d() * sg.taps());
+    const bool kvec = map.dd % 8 == 0;                          // then I and K are multiples of 8 too: 8 aligned columns share j and the tap
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const int k = kb + 32 * p;
+        if (kvec) {
+            int j, col;
+            map.at(min(k, tg.K - 8), j, col);
+            const float s = w1[j];
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(w2 + col), hi = *reinterpret_cast<const f32x4*>(w2 + col + 4);
+            acc[2 * p] = s * lo;
+            acc[2 * p + 1] = s * hi;
+        } else {
+            KronMap::Walk at = map.start(min(k, tg.K - 1));
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                acc[2 * p + (e >> 2)][e & 3] = w1[at.j] * w2[at.col];
+                if (k + e + 1 < tg.K) map.next(at);
+            }
+        }
+    }
+}
+
+template <typename T, int MODE, bool FORMS>
 __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long long* __restrict__ targets, const long long* __restrict__ segments,
                                                                    const int* __restrict__ tiles, const float* __restrict__ scales, int lds_row,
                                                                    float* __restrict__ workspace) {
-    typedef typename V16<T>::x8 frag;
-    constexpr int SEG_WORDS = SegRow<MODE>::WORDS;
     extern __shared__ __attribute__((aligned(16))) char lds_down[];
     char* lds_up = lds_down + LORA_TK * lds_row;
     const int t = tiles[2 * blockIdx.x], tile = tiles[2 * blockIdx.x + 1];
@@ -165,40 +304,28 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
 #pragma unroll
     for (int i = 0; i < 8; ++i) sum[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bcoef = 1.f;                                          // (DoRA) 1 + sum_j (g_j[n] - 1), what the base is scaled by
-    bool merged = false;
+    bool merged = false, staged = false;
     for (int j = 0; j < tg.nseg; ++j) {
-        const long long* sg = segments + (long)(tg.seg0 + j) * SEG_WORDS;
-        const float s = scales[(int)sg[3]];
+        const Segment sg = load_segment<MODE, FORMS>(segments, tg.seg0 + j);
+        const float s = scales[sg.slot];
         if (s == 0.f) continue;                                 // (uniform) an adapter at scale 0 contributes nothing, whatever it holds
-        if (MODE == MODE_NORM && sg[4] == 0) continue;          // (uniform) a plain segment has no norm
-        const T* up = (const T*)sg[0] + (long)nt * (int)sg[2];
-        const T* down_t = (const T*)sg[1] + (long)k0 * (int)sg[2];
-        const int rp = (int)sg[2], chunks = rp >> 3;             // 16-byte chunks per factor row
-        if ((rp + 8) * 2 > lds_row) continue;                   // (uniform; a table that breaks the max_rank contract: no image overrun)
-        if (merged) __syncthreads();                            // the previous segment's images have been read
+        if (MODE == MODE_NORM && sg.mag == 0) continue;         // (uniform) a plain segment has no norm
+        // (uniform; a table that breaks the max_rank contract: no image overrun)
+        if (sg.kind != KIND_KRON && ((sg.rp() + 8) * 2 > lds_row || (sg.rp2() + 8) * 2 > lds_row)) continue;
         merged = true;
-        // both tiles are contiguous in memory (whole rows of row-major factors): coalesced 16-byte copies.  Rows past the
-        // weight's edge are not read; what the image holds there only reaches outputs that are never stored.
-        for (int q = threadIdx.x; q < rows_k * chunks; q += LORA_THREADS) {
-            const int row = q / chunks, col = q - row * chunks;
-            const int img = (row & ~31) + 16 * ((row >> 2) & 1) + 4 * ((row >> 3) & 3) + (row & 3);
-            *reinterpret_cast<frag*>(lds_down + img * lds_row + col * 16) = *reinterpret_cast<const frag*>(down_t + (long)q * 8);
-        }
-        for (int q = threadIdx.x; q < rows_n * chunks; q += LORA_THREADS) {
-            const int row = q / chunks, col = q - row * chunks;
-            *reinterpret_cast<frag*>(lds_up + row * lds_row + col * 16) = *reinterpret_cast<const frag*>(up + (long)q * 8);
-        }
-        __syncthreads();
+        // ---- the segment's fp32 tile: the only part that knows the kind (every branch is workgroup-uniform) ----
         f32x4 acc[8];
+        if (FORMS && sg.kind == KIND_KRON) {
+            kron_tile16(sg, tg, n0 + c, k0 + 8 * g, acc);
+        } else {
+            lora_product16<T>((const T*)sg.p0 + (long)nt * sg.rp(), (const T*)sg.p1 + (long)k0 * sg.rp(), sg.rp(), rows_n, rows_k, lds_down, lds_up,
+                              lds_row, staged, acc);
+            if (FORMS && sg.kind == KIND_HADA) {
+                f32x4 acc2[8];
+                lora_product16<T>((const T*)sg.p2() + (long)nt * sg.rp2(), (const T*)sg.p3() + (long)k0 * sg.rp2(), sg.rp2(), rows_n, rows_k, lds_down,
+                                  lds_up, lds_row, staged, acc2);
 #pragma unroll
-        for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int r0 = 0; r0 < rp; r0 += 32) {
-            const int col = (r0 + 8 * g) * 2;
-            const frag b = *reinterpret_cast<const frag*>(lds_up + (wave * 16 + c) * lds_row + col);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {                       // i = 2 p + h: image rows 16 i .. 16 i + 15
-                const frag a = *reinterpret_cast<const frag*>(lds_down + (16 * i + c) * lds_row + col);
-                acc[i] = Mfma16<T>::run(a, b, acc[i]);
+                for (int i = 0; i < 8; ++i) acc[i] *= acc2[i];
             }
         }
         if constexpr (MODE == MODE_NORM) {
@@ -215,17 +342,17 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
                 }
             ss += __shfl_xor(ss, 16);
             ss += __shfl_xor(ss, 32);
-            if (g == 0 && n0 + c < tg.N) workspace[sg[5] + (long)(tile % tiles_k) * tg.N + n0 + c] = ss;
+            if (g == 0 && n0 + c < tg.N) workspace[sg.ws + (long)(tile % tiles_k) * tg.N + n0 + c] = ss;
         } else {
             float coef = s;
             if constexpr (MODE == MODE_DORA) {
-                if (sg[4] != 0) {                               // (uniform) rows past the edge take the last row's gain and are never stored
+                if (sg.mag != 0) {                              // (uniform) rows past the edge take the last row's gain and are never stored
                     // a row's four lane groups add one chain of its partials each; the xor tree leaves the same sum in all four
                     const int n = min(n0 + c, tg.N - 1);
-                    float ss = dora_chain(workspace + sg[5], n, tg.N, tiles_k, g, 4);
+                    float ss = dora_chain(workspace + sg.ws, n, tg.N, tiles_k, g, 4);
                     ss += __shfl_xor(ss, 16);
                     ss += __shfl_xor(ss, 32);
-                    const float gain = dora_gain(ss, ((const float*)sg[4])[n]);
+                    const float gain = dora_gain(ss, ((const float*)sg.mag)[n]);
                     bcoef += gain - 1.f;
                     coef = gain * s;
                 }
@@ -260,11 +387,54 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
 }
 
 // fp32: thread (rg, cg) owns rows 8 rg .. 8 rg + 7 and columns 4 cg .. 4 cg + 3 of the tile; factors are read four ranks at a time
-template <int MODE>
+__device__ __forceinline__ void lora_product32(const float* __restrict__ up, const float* __restrict__ down_t, int rp, const Target& tg, int n0,
+                                               int k0, float (&acc)[8][4]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][e] = 0.f;
+    for (int r0 = 0; r0 < rp; r0 += 4) {
+        f32x4 d[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            d[e] = *reinterpret_cast<const f32x4*>(down_t + (long)min(k0 + e, tg.K - 1) * rp + r0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const f32x4 u = *reinterpret_cast<const f32x4*>(up + (long)min(n0 + i, tg.N - 1) * rp + r0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[i][e] = fmaf(u[q], d[e][q], acc[i][e]);
+        }
+    }
+}
+
+// KRON in fp32: the thread's four columns are mapped once, its eight rows then read two small tables through the cache
+__device__ __forceinline__ void kron_tile32(const Segment& sg, const Target& tg, int n0, int k0, float (&acc)[8][4]) {
+    const KronMap map(sg);
+    int jj[4], cc[4];
+    KronMap::Walk at = map.start(min(k0, tg.K - 1));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        jj[e] = at.j, cc[e] = at.col;
+        if (k0 + e + 1 < tg.K) map.next(at);
+    }
+    const float* __restrict__ w1 = (const float*)sg.p0;
+    const float* __restrict__ w2 = (const float*)sg.p1;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int n = min(n0 + i, tg.N - 1), i1 = n / sg.c();
+        const float* r1 = w1 + (long)i1 * sg.b();
+        const float* r2 = w2 + (long)(n - i1 * sg.c()) * (sg.d() * sg.taps());
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[i][e] = r1[jj[e]] * r2[cc[e]];
+    }
+}
+
+template <int MODE, bool FORMS>
 __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long long* __restrict__ targets, const long long* __restrict__ segments,
                                                                    const int* __restrict__ tiles, const float* __restrict__ scales,
                                                                    float* __restrict__ workspace) {
-    constexpr int SEG_WORDS = SegRow<MODE>::WORDS;
     const int t = tiles[2 * blockIdx.x], tile = tiles[2 * blockIdx.x + 1];
     const Target tg = load_target(targets, t);
     const int tiles_k = (tg.K + LORA_TK - 1) / LORA_TK;
@@ -282,31 +452,23 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long l
     }
     bool merged = false;
     for (int j = 0; j < tg.nseg; ++j) {
-        const long long* sg = segments + (long)(tg.seg0 + j) * SEG_WORDS;
-        const float s = scales[(int)sg[3]];
+        const Segment sg = load_segment<MODE, FORMS>(segments, tg.seg0 + j);
+        const float s = scales[sg.slot];
         if (s == 0.f) continue;
-        if (MODE == MODE_NORM && sg[4] == 0) continue;
+        if (MODE == MODE_NORM && sg.mag == 0) continue;
         merged = true;
-        const float* up = (const float*)sg[0];
-        const float* down_t = (const float*)sg[1];
-        const int rp = (int)sg[2];
         float acc[8][4];
+        if (FORMS && sg.kind == KIND_KRON) {
+            kron_tile32(sg, tg, n0, k0, acc);
+        } else {
+            lora_product32((const float*)sg.p0, (const float*)sg.p1, sg.rp(), tg, n0, k0, acc);
+            if (FORMS && sg.kind == KIND_HADA) {
+                float acc2[8][4];
+                lora_product32((const float*)sg.p2(), (const float*)sg.p3(), sg.rp2(), tg, n0, k0, acc2);
 #pragma unroll
-        for (int i = 0; i < 8; ++i)
+                for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][e] = 0.f;
-        for (int r0 = 0; r0 < rp; r0 += 4) {
-            f32x4 d[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                d[e] = *reinterpret_cast<const f32x4*>(down_t + (long)min(k0 + e, tg.K - 1) * rp + r0);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const f32x4 u = *reinterpret_cast<const f32x4*>(up + (long)min(n0 + i, tg.N - 1) * rp + r0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[i][e] = fmaf(u[q], d[e][q], acc[i][e]);
+                    for (int e = 0; e < 4; ++e) acc[i][e] *= acc2[i][e];
             }
         }
         if constexpr (MODE == MODE_NORM) {
@@ -321,26 +483,26 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long l
                 }
 #pragma unroll
                 for (int m = 1; m < 32; m <<= 1) ss += __shfl_xor(ss, m);
-                if ((threadIdx.x & 31) == 0 && n0 + i < tg.N) workspace[sg[5] + (long)(tile % tiles_k) * tg.N + n0 + i] = ss;
+                if ((threadIdx.x & 31) == 0 && n0 + i < tg.N) workspace[sg.ws + (long)(tile % tiles_k) * tg.N + n0 + i] = ss;
             }
         } else {
             // (DoRA) the 32 lanes of a half wave share their 8 rows: lane l adds chain l >> 3 (of four) of row l & 7, an xor tree
             // joins the chains, and every lane then takes row i's gain from lane i of its half
             float mine = 0.f;
             if constexpr (MODE == MODE_DORA) {
-                if (sg[4] != 0) {                               // (uniform)
+                if (sg.mag != 0) {                              // (uniform)
                     const int l = threadIdx.x & 31, n = min(n0 + (l & 7), tg.N - 1);
-                    float ss = dora_chain(workspace + sg[5], n, tg.N, tiles_k, l >> 3, 4);
+                    float ss = dora_chain(workspace + sg.ws, n, tg.N, tiles_k, l >> 3, 4);
                     ss += __shfl_xor(ss, 8);
                     ss += __shfl_xor(ss, 16);
-                    mine = dora_gain(ss, ((const float*)sg[4])[n]);
+                    mine = dora_gain(ss, ((const float*)sg.mag)[n]);
                 }
             }
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 float coef = s;
                 if constexpr (MODE == MODE_DORA) {
-                    if (sg[4] != 0) {                           // (uniform)
+                    if (sg.mag != 0) {                          // (uniform)
                         const float gain = __shfl(mine, (int)(threadIdx.x & 32) + i);
                         bcoef[i] += gain - 1.f;
                         coef = gain * s;
@@ -357,18 +519,18 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long l
         finish_row<float, MODE == MODE_DORA>(tg, n0 + i, k0, sum[i], merged, vec, MODE == MODE_DORA ? bcoef[i] : 1.f);
 }
 
-template <int MODE>
+template <int MODE, bool FORMS = false>
 static int lora_launch(const char* what, const long long* targets, const long long* segments, int max_rank, const int* tiles, long n_tiles,
                        const float* scales, float* workspace, int dtype, hipStream_t st) {
     const dim3 grid((unsigned)n_tiles), block(LORA_THREADS);
     const int lds_row = lora_lds_row((max_rank + 31) / 32 * 32);
     const size_t lds = (size_t)(LORA_TK + LORA_TN) * lds_row;
     if (dtype == ST_BF16)
-        hipLaunchKernelGGL((lora_merge16_kernel<bf16, MODE>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
+        hipLaunchKernelGGL((lora_merge16_kernel<bf16, MODE, FORMS>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
     else if (dtype == ST_F16)
-        hipLaunchKernelGGL((lora_merge16_kernel<f16, MODE>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
+        hipLaunchKernelGGL((lora_merge16_kernel<f16, MODE, FORMS>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
     else if (dtype == ST_F32)
-        hipLaunchKernelGGL(lora_merge32_kernel<MODE>, grid, block, 0, st, targets, segments, tiles, scales, workspace);
+        hipLaunchKernelGGL((lora_merge32_kernel<MODE, FORMS>), grid, block, 0, st, targets, segments, tiles, scales, workspace);
     else
         return st_fail("%s: unsupported dtype %d", what, dtype);
     return st_check_launch(what);
@@ -412,4 +574,29 @@ extern "C" int st_lora_merge_dora(const long long* targets, int n_targets, const
         if (rc) return rc;
     }
     return lora_launch<MODE_DORA>("lora_merge_dora", targets, segments, max_rank, tiles, n_tiles, scales, workspace, dtype, st);
+}
+
+extern "C" int st_lora_merge_forms(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
+                                   const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
+                                   float* workspace, size_t workspace_bytes, int dtype, void* stream) {
+    ST_REQUIRE(targets && tiles && scales && segments, "lora_merge_forms: null pointer");
+    ST_REQUIRE(n_targets > 0 && n_segments > 0 && n_scales > 0, "lora_merge_forms: bad sizes (targets %d, segments %d, scales %d)",
+               n_targets, n_segments, n_scales);
+    ST_REQUIRE(n_tiles > 0 && n_tiles <= 0x7fffffffL && n_norm_tiles >= 0 && n_norm_tiles <= n_tiles,
+               "lora_merge_forms: %ld tiles, %ld norm tiles (a launch takes 1 .. 2^31 - 1; the norm pass covers a subset of the targets)",
+               n_tiles, n_norm_tiles);
+    ST_REQUIRE(n_norm_tiles == 0 || (norm_tiles && workspace && workspace_bytes >= 4),
+               "lora_merge_forms: the norm pass needs its tile list and a workspace");
+    ST_REQUIRE((uintptr_t)targets % 8 == 0 && (uintptr_t)segments % 8 == 0 && (uintptr_t)tiles % 4 == 0 && (uintptr_t)norm_tiles % 4 == 0 &&
+               (uintptr_t)scales % 4 == 0 && (uintptr_t)workspace % 4 == 0, "lora_merge_forms: misaligned table");
+    ST_REQUIRE(max_rank >= 0 && max_rank <= ST_LORA_MAX_RANK,       // (0: every segment is a Kronecker one, nothing is staged)
+               "lora_merge_forms: max_rank %d (the largest padded rank of any factor pair, 0 .. %d)", max_rank, (int)ST_LORA_MAX_RANK);
+    ST_REQUIRE(dtype == ST_BF16 || dtype == ST_F16 || dtype == ST_F32, "lora_merge_forms: unsupported dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_norm_tiles > 0) {                                       // only when some segment has a magnitude
+        const int rc = lora_launch<MODE_NORM, true>("lora_merge_forms (norm pass)", targets, segments, max_rank, norm_tiles, n_norm_tiles,
+                                                    scales, workspace, dtype, st);
+        if (rc) return rc;
+    }
+    return lora_launch<MODE_DORA, true>("lora_merge_forms", targets, segments, max_rank, tiles, n_tiles, scales, workspace, dtype, st);
 }

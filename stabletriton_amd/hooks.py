@@ -67,10 +67,11 @@ class _HoistedUNet(nn.Module):
         from . import lora
         return lora.attach(self.compiled)
 
-    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True, convs: bool = False):
+    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True, convs: bool = False, lycoris: bool = False):
         """Merge a LoRA state dict (PEFT / diffusers / kohya keys; DoRA magnitudes apply) into the compiled UNet; `convs=True`
-        also takes its convolution factors (LoCon).  Returns the keys not applied."""
-        left = self._lora_set().load(name, state_dict, scale, strict, convs)
+        also takes its convolution factors (LoCon), `lycoris=True` its Tucker cores, LoHa and LoKr factors.  Returns the keys
+        not applied."""
+        left = self._lora_set().load(name, state_dict, scale, strict, convs, lycoris)
         self.refresh_weights()
         return left
 

@@ -30,9 +30,33 @@ Scope: `nn.Linear` targets (attention projections, feed-forward, proj_in / proj_
 adapter names them) and, with `convs=True`, `nn.Conv2d` targets (LoCon: conv_in / conv_out, the resnets' conv1 / conv2 /
 conv_shortcut, the samplers' conv).  A conv weight (O, I, R, S) is merged through the 2-D view of its own memory - (O, R S I)
 for the channels_last weights of an `optimize_model` result, (O, I R S) for a contiguous one - so the kernel sees it as it
-sees a Linear.  Conv factors are down (r, I, R, S) with the target's kernel size and up (O, r, 1, 1).  Tucker (`lora_mid`),
-LoHa and LoKr factors, DoRA magnitudes along the input axis, grouped or dilated targets are refused; text-encoder adapters
-are reported, not applied.
+sees a Linear.  Conv factors are down (r, I, R, S) with the target's kernel size and up (O, r, 1, 1).
+
+With `lycoris=True` the other factorisations LyCORIS trainers write are applied too (conv targets still need `convs=True`).
+Shapes as the trainers store them; a missing alpha makes the scalar in front 1; N x K stands for O x (I R S) on a conv:
+
+    Tucker LoCon  lora_down (r, I, 1, 1), lora_mid (r, r, R, S), lora_up (O, r, 1, 1)
+                  D[o,i,y,x] = (alpha / r) sum_ab up[o,a] mid[a,b,y,x] down[b,i]
+    LoHa          hada_w1_a (N, r), hada_w1_b (r, K), hada_w2_a (N, r), hada_w2_b (r, K), K = I R S flattened in that order
+                  D = (alpha / r) (w1_a w1_b) (.) (w2_a w2_b),   r = hada_w1_b.shape[0]
+    Tucker LoHa   adds hada_t1, hada_t2 (r, r, R, S); hada_w?_a is (r, O), hada_w?_b (r, I)
+                  W_m[o,i,y,x] = sum_pq t_m[p,q,y,x] w_m_a[p,o] w_m_b[q,i],   D = (alpha / r) W_1 (.) W_2
+    LoKr          w1 = lokr_w1 (a, b) or lokr_w1_a (a, r) lokr_w1_b (r, b);
+                  w2 = lokr_w2 (c, d[, R, S]), or lokr_w2_a (c, r) lokr_w2_b (r, d R S), or - Tucker - lokr_t2 (r, r, R, S) with
+                  lokr_w2_a (r, c) and lokr_w2_b (r, d) contracted like a Tucker LoHa pair;   a c = O, b d = I
+                  D[i c + p, j d + q, y, x] = sigma w1[i,j] w2[p,q,y,x];  sigma = alpha / r with r the rank of a factorised w2,
+                  else of a factorised w1; sigma = 1 when both are stored full
+
+What is scale-independent is done once at load, in fp32 on the weight's device (`build_factors`): a Tucker core is
+contracted into its down factor (`contract_core`) and rounded to the storage dtype once, which leaves an ordinary factor
+pair; LoKr's w1 (sigma folded in) and w2 become small fp32 tables that are never rounded to a 16-bit dtype; LoHa's
+alpha / r is folded into its first up factor before rounding.  The kernel then forms each segment's delta by kind - a
+product, the elementwise product of two products, or a Kronecker product - and everything after that (scales, DoRA,
+stacking in load order, the final rounding) is shared, so a `dora_scale` along the output axis composes with every form and
+the kinds mix on one weight.
+
+Still refused: DoRA magnitudes along the input axis, full `diff` matrices, norm / bias adapters, (IA)^3, GLoRA, grouped or
+dilated targets; text-encoder adapters are reported, not applied.
 """
 from __future__ import annotations
 
@@ -52,7 +76,7 @@ _OLD_PROC = re.compile(r"^(?P<attn>.+?)\.(?:processor\.)?(?P<proj>to_q|to_k|to_v
 _OLD_LAYER = re.compile(r"^(?P<path>.+)\.lora(?:_layer)?\.(?P<du>down|up)\.weight$")
 _KOHYA = re.compile(r"^(?P<stem>lora_unet_[^.]+)\.(?P<what>lora_down\.weight|lora_up\.weight|alpha|dora_scale)$")
 _PEFT_MAGNITUDE = re.compile(r"^(?P<path>.+)\.lora_magnitude_vector(?:\.[^.]+)?(?:\.weight)?$")
-# factorisations this merge does not implement: Tucker's core (`lora_mid`), LoHa (`hada_*`), LoKr (`lokr_*`)
+# factorisations that are applied only with `lycoris=True`: Tucker's core (`lora_mid`), LoHa (`hada_*`), LoKr (`lokr_*`)
 _OTHER_FORMS = re.compile(r"^(?P<stem>.+?)\.(?P<what>lora_mid|hada_(?:w[12]_[ab]|t[12])|lokr_(?:w[12](?:_[ab])?|t2))(?:\.weight)?$")
 
 
@@ -60,14 +84,18 @@ def is_text_encoder_key(key: str) -> bool:
     return _TEXT_ENCODER.match(key) is not None
 
 
-def _place(key: str, flat: Mapping[str, str], names) -> Optional[Tuple[str, str]]:
-    """(module name, 'down' | 'up' | 'alpha' | 'magnitude') for one state-dict key, or None when the key names no target."""
+def _place(key: str, flat: Mapping[str, str], names, lycoris: bool = False) -> Optional[Tuple[str, str]]:
+    """(module name, 'down' | 'up' | 'alpha' | 'magnitude') for one state-dict key, or None when the key names no target.  With
+    `lycoris` also (module name, 'lora_mid' | 'hada_w1_a' | ... | 'lokr_t2'); without it such a key on a listed module raises."""
     m = _OTHER_FORMS.match(key)
     if m:
         stem = m["stem"]
         name = flat.get(stem[len("lora_unet_"):]) if stem.startswith("lora_unet_") else stem[len("unet."):] if stem.startswith("unet.") else stem
         if name in names:
-            raise ValueError(f"{name}: {key!r} belongs to a Tucker (lora_mid), LoHa or LoKr factorisation, which is not supported")
+            if lycoris:
+                return name, m["what"]
+            raise ValueError(f"{name}: {key!r} belongs to a Tucker (lora_mid), LoHa or LoKr factorisation, which is not supported "
+                             "unless it is asked for: pass lycoris=True")
         return None
     m = _KOHYA.match(key)
     if m:
@@ -96,27 +124,62 @@ def _place(key: str, flat: Mapping[str, str], names) -> Optional[Tuple[str, str]
 
 class Placed(NamedTuple):
     """What an adapter holds for one module: down (r, K) and up (N, r) - (r, I, R, S) and (O, r, 1, 1) for a convolution - its
-    alpha, and its DoRA magnitude as the file holds it (None for a plain adapter)."""
-    down: torch.Tensor
-    up: torch.Tensor
-    alpha: float
+    alpha, and its DoRA magnitude as the file holds it (None for a plain adapter).  `form` is "lora", or with `lycoris=True`
+    "tucker" (down and up as usual, the core in `parts["lora_mid"]`), "loha" or "lokr" (down and up None, the file's tensors in
+    `parts` under their key names, alpha None when the file has none)."""
+    down: Optional[torch.Tensor]
+    up: Optional[torch.Tensor]
+    alpha: Optional[float]
     magnitude: Optional[torch.Tensor] = None
+    form: str = "lora"
+    parts: Optional[Dict[str, torch.Tensor]] = None
 
 
-def parse_lora_state_dict(sd: Mapping[str, torch.Tensor], module_names):
+def parse_lora_state_dict(sd: Mapping[str, torch.Tensor], module_names, lycoris: bool = False):
     """`parse_adapter` in the form this function has always had: `placed[name] = (down, up, alpha)`.  DoRA magnitudes are placed
     and checked like everything else but are not part of the triples; `parse_adapter` returns them.
 
     Keys that name a listed module in a form the merge cannot apply RAISE ValueError; they are no longer reported as unplaced:
-    Tucker (`lora_mid`), LoHa (`hada_*`) and LoKr (`lokr_*`) factors, a `dora_scale` along the input axis or with the wrong first
+    Tucker (`lora_mid`), LoHa (`hada_*`) and LoKr (`lokr_*`) factors unless `lycoris=True` asks for them (their triples then
+    hold None for the factors, see `Placed`), a `dora_scale` along the input axis or with the wrong first
     dimension, a magnitude without its factors.  Applying the rest of such a file would merge something its author never
     trained, so `strict=False` in `LoraSet.load` does not turn these into a list either; the same keys on modules that are
     not listed (a conv key with the Linear names alone) stay in `unplaced` as before."""
-    placed, unplaced = parse_adapter(sd, module_names)
+    placed, unplaced = parse_adapter(sd, module_names, lycoris=lycoris)
     return {n: (p.down, p.up, p.alpha) for n, p in placed.items()}, unplaced
 
 
-def parse_adapter(sd: Mapping[str, torch.Tensor], module_names) -> Tuple[Dict[str, Placed], List[str]]:
+_HADA = ("hada_w1_a", "hada_w1_b", "hada_w2_a", "hada_w2_b")
+
+
+def _form_of(name: str, p: Mapping[str, torch.Tensor]) -> str:
+    """Which factorisation the parts of one module are, complete and unmixed, or ValueError."""
+    hada = sorted(k for k in p if k.startswith("hada_"))
+    lokr = sorted(k for k in p if k.startswith("lokr_"))
+    lora = sorted(k for k in p if k in ("down", "up", "lora_mid"))
+    if sum(bool(x) for x in (hada, lokr, lora)) > 1:
+        raise ValueError(f"{name}: the state dict mixes factorisations on one module: {hada + lokr + lora}")
+    if hada:
+        missing = [k for k in _HADA if k not in p]
+        if missing or ("hada_t1" in p) != ("hada_t2" in p):
+            raise ValueError(f"{name}: incomplete LoHa adapter, found only {hada} (it takes hada_w1_a/b and hada_w2_a/b, and "
+                             "hada_t1 with hada_t2 or neither)")
+        return "loha"
+    if lokr:
+        w1_full, w1_fac = "lokr_w1" in p, "lokr_w1_a" in p or "lokr_w1_b" in p
+        w2_full, w2_fac = "lokr_w2" in p, "lokr_w2_a" in p or "lokr_w2_b" in p
+        ok = (w1_full != w1_fac and w2_full != w2_fac and (not w1_fac or ("lokr_w1_a" in p and "lokr_w1_b" in p))
+              and (not w2_fac or ("lokr_w2_a" in p and "lokr_w2_b" in p)) and ("lokr_t2" not in p or w2_fac))
+        if not ok:
+            raise ValueError(f"{name}: incomplete LoKr adapter, found only {lokr} (it takes lokr_w1 or lokr_w1_a/b, and lokr_w2 or "
+                             "lokr_w2_a/b, the latter with or without lokr_t2)")
+        return "lokr"
+    if "down" not in p or "up" not in p:
+        raise ValueError(f"{name}: incomplete adapter, found only {sorted(k for k in p if k != 'kohya_magnitude')}")
+    return "tucker" if "lora_mid" in p else "lora"
+
+
+def parse_adapter(sd: Mapping[str, torch.Tensor], module_names, lycoris: bool = False) -> Tuple[Dict[str, Placed], List[str]]:
     """Place a LoRA state dict on the modules named by `module_names`: the model's own `nn.Linear` (and, for conv adapters,
     `nn.Conv2d`) names, or a mapping from those names to the weights' shapes, with which every placed adapter is also checked
     against its target (`check_shapes`).
@@ -128,9 +191,13 @@ def parse_adapter(sd: Mapping[str, torch.Tensor], module_names) -> Tuple[Dict[st
                             <path>.lora_magnitude_vector[.<adapter>][.weight]
       older diffusers       <attn>.to_q_lora.down.weight / .up.weight, with or without `.processor`; <path>.lora.down.weight
       kohya / LyCORIS       lora_unet_<path with underscores>.lora_down.weight / .lora_up.weight / .alpha / .dora_scale
+      LyCORIS, `lycoris`    <stem>.lora_mid, <stem>.hada_w1_a / _w1_b / _w2_a / _w2_b / _t1 / _t2,
+                            <stem>.lokr_w1 / _w1_a / _w1_b / _w2 / _w2_a / _w2_b / _t2  (each with or without `.weight`)
     An optional `unet.` prefix is dropped.  kohya's underscores are resolved against the module names themselves
     (`name.replace(".", "_")`), never by guessing where the dots were.  `alpha` defaults to the rank.  A `dora_scale` along
-    the input axis (first dimension 1, more than one element) and Tucker / LoHa / LoKr keys on a listed module are errors.
+    the input axis (first dimension 1, more than one element) and - unless `lycoris=True` - Tucker / LoHa / LoKr keys on a
+    listed module are errors; with it they are placed (`Placed.form`, `Placed.parts`), and a set that is incomplete or mixes
+    forms on one module is an error.
     A PEFT magnitude may have any shape of N elements; a kohya `dora_scale` has N (the rows of its up factor) as its first
     dimension, anything else is an error."""
     shapes = module_names if isinstance(module_names, Mapping) else None
@@ -144,7 +211,7 @@ def parse_adapter(sd: Mapping[str, torch.Tensor], module_names) -> Tuple[Dict[st
     parts: Dict[str, Dict[str, torch.Tensor]] = {}
     unplaced: List[str] = []
     for key, val in sd.items():
-        hit = None if is_text_encoder_key(key) else _place(key, flat, names)
+        hit = None if is_text_encoder_key(key) else _place(key, flat, names, lycoris)
         if hit is None:
             unplaced.append(key)
             continue
@@ -160,25 +227,123 @@ def parse_adapter(sd: Mapping[str, torch.Tensor], module_names) -> Tuple[Dict[st
             slot["kohya_magnitude"] = key.endswith(".dora_scale")
     placed = {}
     for name, p in parts.items():
-        if "down" not in p or "up" not in p:
-            raise ValueError(f"{name}: incomplete adapter, found only {sorted(p)}")
+        form = _form_of(name, p)
+        if form in ("loha", "lokr"):
+            held = {k: v for k, v in p.items() if k.startswith(("hada_", "lokr_"))}
+            placed[name] = Placed(None, None, float(p["alpha"]) if "alpha" in p else None, p.get("magnitude"), form, held)
+            if p.get("kohya_magnitude") and p["magnitude"].dim() == 0:
+                raise ValueError(f"{name}: a dora_scale has the output rows / channels as its first dimension; got a scalar")
+            if shapes is not None:
+                check_shapes(name, tuple(shapes[name]), None, None, p.get("magnitude"), form, held)
+            continue
         down, up = p["down"], p["up"]
-        if down.dim() == 4 and tuple(down.shape[2:]) == (1, 1) and up.dim() == 4 and tuple(up.shape[2:]) == (1, 1):
+        if (form == "lora" and down.dim() == 4 and tuple(down.shape[2:]) == (1, 1) and up.dim() == 4
+                and tuple(up.shape[2:]) == (1, 1)):
             down, up = down[:, :, 0, 0], up[:, :, 0, 0]          # a Linear that another exporter wrote as a 1x1 convolution
         alpha = float(p["alpha"]) if "alpha" in p else float(down.shape[0])
-        placed[name] = Placed(down, up, alpha, p.get("magnitude"))
+        held = {"lora_mid": p["lora_mid"]} if form == "tucker" else None
+        placed[name] = Placed(down, up, alpha, p.get("magnitude"), form, held)
         if p.get("kohya_magnitude") and (p["magnitude"].dim() == 0 or p["magnitude"].shape[0] != up.shape[0]):
             raise ValueError(f"{name}: a dora_scale has the output rows / channels ({up.shape[0]}) as its first dimension; "
                              f"got shape {tuple(p['magnitude'].shape)}")
         if shapes is not None:
-            check_shapes(name, tuple(shapes[name]), down, up, p.get("magnitude"))
+            check_shapes(name, tuple(shapes[name]), down, up, p.get("magnitude"), form, held)
     return placed, unplaced
 
 
-def check_shapes(name: str, weight_shape, down: torch.Tensor, up: torch.Tensor, magnitude: Optional[torch.Tensor] = None) -> int:
+def _check_rank(name: str, r: int) -> None:
+    if r < 1 or r > MAX_RANK:
+        raise ValueError(f"{name}: rank {r} is outside 1 .. {MAX_RANK}")
+
+
+def _check_forms(name: str, weight_shape, form: str, down, up, parts) -> int:
+    """The shape rules of the LyCORIS forms (the module docstring); returns the largest rank of any factor pair."""
+    if len(weight_shape) == 4:
+        o, i, kr, ks = weight_shape
+    else:
+        (o, i), kr, ks = weight_shape, 1, 1
+    taps = kr * ks
+    sh = lambda t: tuple(t.shape)                                             # noqa: E731
+
+    def need(ok: bool, what: str, want: str):
+        if not ok:
+            got = ", ".join(f"{k} {sh(v)}" for k, v in sorted(parts.items()))
+            raise ValueError(f"{name}: {what} of a {tuple(weight_shape)} weight takes {want}; got {got}")
+
+    def tucker_pair(t, wa, wb, rows, cols, label):
+        """core (p, q, R, S) with wa (p, rows) and wb (q, cols)"""
+        need(t.dim() == 4 and wa.dim() == 2 and wb.dim() == 2 and sh(t) == (wa.shape[0], wb.shape[0], kr, ks)
+             and wa.shape[1] == rows and wb.shape[1] == cols, label,
+             f"a core (r, r, {kr}, {ks}) with factors (r, {rows}) and (r, {cols})")
+        _check_rank(name, wa.shape[0])
+        _check_rank(name, wb.shape[0])
+        return max(wa.shape[0], wb.shape[0])
+
+    if form == "tucker":
+        mid = parts["lora_mid"]
+        if len(weight_shape) != 4:
+            raise ValueError(f"{name}: a Tucker core (lora_mid) belongs to a convolution, not to a {tuple(weight_shape)} weight")
+        down2 = down[:, :, 0, 0] if down.dim() == 4 and sh(down)[2:] == (1, 1) else down
+        up2 = up[:, :, 0, 0] if up.dim() == 4 and sh(up)[2:] == (1, 1) else up
+        ok = down2.dim() == 2 and up2.dim() == 2 and mid.dim() == 4 and sh(mid) == (up2.shape[1], down2.shape[0], kr, ks) \
+            and down2.shape[1] == i and up2.shape[0] == o and mid.shape[0] == mid.shape[1]
+        if not ok:
+            raise ValueError(f"{name}: a Tucker LoCon on a {(o, i, kr, ks)} conv weight takes down (r, {i}, 1, 1), mid (r, r, {kr}, {ks}) "
+                             f"and up ({o}, r, 1, 1); got down {sh(down)}, mid {sh(mid)} and up {sh(up)}")
+        _check_rank(name, down2.shape[0])
+        return down2.shape[0]
+    if form == "loha":
+        rank = 0
+        for m in "12":
+            wa, wb, t = parts[f"hada_w{m}_a"], parts[f"hada_w{m}_b"], parts.get(f"hada_t{m}")
+            if t is not None:
+                rank = max(rank, tucker_pair(t, wa, wb, o, i, "a Tucker LoHa pair"))
+            else:
+                need(wa.dim() == 2 and wb.dim() == 2 and wa.shape[0] == o and wb.shape[1] == i * taps and wa.shape[1] == wb.shape[0],
+                     "a LoHa pair", f"hada_w?_a ({o}, r) and hada_w?_b (r, {i * taps})")
+                _check_rank(name, wb.shape[0])
+                rank = max(rank, wb.shape[0])
+        return rank
+    if form == "lokr":
+        rank = 0
+        if "lokr_w1" in parts:
+            w1 = parts["lokr_w1"]
+            need(w1.dim() == 2, "LoKr", "a 2-D lokr_w1 (a, b)")
+            a, b = sh(w1)
+        else:
+            wa, wb = parts["lokr_w1_a"], parts["lokr_w1_b"]
+            need(wa.dim() == 2 and wb.dim() == 2 and wa.shape[1] == wb.shape[0], "LoKr", "lokr_w1_a (a, r) and lokr_w1_b (r, b)")
+            _check_rank(name, wb.shape[0])
+            (a, rank), b = sh(wa), wb.shape[1]
+        need(a >= 1 and b >= 1 and o % a == 0 and i % b == 0, "LoKr", f"w1 (a, b) with a dividing {o} and b dividing {i}")
+        c, d = o // a, i // b
+        if "lokr_w2" in parts:
+            w2 = parts["lokr_w2"]
+            need(sh(w2) == (c, d, kr, ks) or (taps == 1 and sh(w2) == (c, d)), "LoKr", f"lokr_w2 ({c}, {d}, {kr}, {ks}) beside a w1 {(a, b)}")
+        elif "lokr_t2" in parts:
+            rank = max(rank, tucker_pair(parts["lokr_t2"], parts["lokr_w2_a"], parts["lokr_w2_b"], c, d, f"a Tucker LoKr w2 beside a w1 {(a, b)}"))
+        else:
+            wa, wb = parts["lokr_w2_a"], parts["lokr_w2_b"]
+            need(wa.dim() == 2 and wb.dim() == 2 and wa.shape[1] == wb.shape[0] and wa.shape[0] == c and wb.shape[1] == d * taps,
+                 "LoKr", f"lokr_w2_a ({c}, r) and lokr_w2_b (r, {d * taps}) beside a w1 {(a, b)}")
+            _check_rank(name, wb.shape[0])
+            rank = max(rank, wb.shape[0])
+        return rank
+    raise ValueError(f"{name}: unknown adapter form {form!r}")
+
+
+def check_shapes(name: str, weight_shape, down: Optional[torch.Tensor], up: Optional[torch.Tensor],
+                 magnitude: Optional[torch.Tensor] = None, form: str = "lora", parts: Optional[Mapping[str, torch.Tensor]] = None) -> int:
     """A Linear weight (N, K) takes up (N, r) and down (r, K); a conv weight (O, I, R, S) takes up (O, r, 1, 1) and down
     (r, I, R, S) (2-D factors stand for 1x1 ones); r at most MAX_RANK; a magnitude has N (O) elements (the parser
-    also holds kohya's `dora_scale` to N as its first dimension).  Returns r."""
+    also holds kohya's `dora_scale` to N as its first dimension).  Returns r.  The LyCORIS forms (`form`, `parts` of a
+    `Placed`) follow the module docstring's shapes, every factor pair at most MAX_RANK; returns the largest rank."""
+    if form != "lora":
+        r = _check_forms(name, tuple(weight_shape), form, down, up, parts or {})
+        n = weight_shape[0]
+        if magnitude is not None and (magnitude.numel() != n or (magnitude.dim() > 1 and magnitude.shape[0] != n)):
+            raise ValueError(f"{name}: a DoRA magnitude has one value per output row ({n}); got shape {tuple(magnitude.shape)}")
+        return r
     if len(weight_shape) == 4:
         o, i, kr, ks = weight_shape
         down4 = down[:, :, None, None] if down.dim() == 2 else down
@@ -204,6 +369,95 @@ def check_shapes(name: str, weight_shape, down: torch.Tensor, up: torch.Tensor, 
     if magnitude is not None and magnitude.numel() != n:
         raise ValueError(f"{name}: a DoRA magnitude has one value per output row ({n}); got shape {tuple(magnitude.shape)}")
     return r
+
+
+def contract_core(core: torch.Tensor, down: torch.Tensor, nhwc: bool) -> torch.Tensor:
+    """A Tucker core (p, q, R, S) contracted into its down factor (q, I), in fp32: down'[p, .] = sum_q core[p, q, y, x] down[q, i]
+    as a (p, K) matrix whose K runs (y, x, i) for a channels_last conv weight (`nhwc`) and (i, y, x) for a contiguous one."""
+    out = torch.einsum("pqyx,qi->pyxi" if nhwc else "pqyx,qi->piyx", core.float(), down.float())
+    return out.reshape(core.shape[0], -1)
+
+
+def _k_order(m: torch.Tensor, weight_shape, nhwc: bool) -> torch.Tensor:
+    """A (rows, I R S) matrix with its columns in the K order of the weight's memory."""
+    if len(weight_shape) == 4 and nhwc:
+        _, i, kr, ks = weight_shape
+        return m.reshape(m.shape[0], i, kr, ks).permute(0, 2, 3, 1).reshape(m.shape[0], -1)
+    return m
+
+
+def _padded_pair(up: torch.Tensor, down: torch.Tensor, like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(Up (N, rp), DownT (K, rp)) as the kernel takes them, from fp32 up (N, r) and down (r, K): each rounded to the storage
+    dtype once, the rank zero-padded to the kernel's multiple."""
+    r = down.shape[0]
+    mult = 4 if like.dtype == torch.float32 else 32
+    rp = -(-r // mult) * mult
+    up_p = torch.zeros((up.shape[0], rp), dtype=like.dtype, device=like.device)
+    down_t = torch.zeros((down.shape[1], rp), dtype=like.dtype, device=like.device)
+    up_p[:, :r] = up.to(like.dtype)
+    down_t[:, :r] = down.to(like.dtype).t()
+    return up_p, down_t
+
+
+def build_factors(p: Placed, w: torch.Tensor, weight_shape, nhwc: bool) -> tuple:
+    """What the merge holds for one adapter on one weight, everything scale-independent done: `w` is the weight's (N, K) view,
+    `weight_shape` the parameter's own shape.  Returns (Up, DownT) for "lora" and "tucker", ("hada", Up1, DownT1, Up2, DownT2)
+    for "loha" and ("kron", W1, W2, taps, layout) for "lokr" (`ops.lora_plan` without the slot and the magnitude)."""
+    f32 = lambda t: t.detach().to(device=w.device, dtype=torch.float32)         # noqa: E731
+    conv = len(weight_shape) == 4
+    taps = weight_shape[2] * weight_shape[3] if conv else 1
+    if p.form in ("lora", "tucker"):
+        down, up = f32(p.down), f32(p.up)
+        r = down.shape[0]
+        up = up.reshape(up.shape[0], -1)
+        if p.form == "tucker":
+            down = contract_core(f32(p.parts["lora_mid"]), down.reshape(r, -1), nhwc)
+        elif conv:                                                           # the down factor in the K order of the weight's memory
+            down = down[:, :, None, None] if down.dim() == 2 else down
+            down = (down.permute(0, 2, 3, 1) if nhwc else down).reshape(r, -1)
+        return _padded_pair(up * (p.alpha / r), down, w)
+    parts = {k: f32(v) for k, v in p.parts.items()}
+    if p.form == "loha":
+        sigma = 1.0 if p.alpha is None else p.alpha / parts["hada_w1_b"].shape[0]
+        pairs = []
+        for m in "12":
+            wa, wb, t = parts[f"hada_w{m}_a"], parts[f"hada_w{m}_b"], parts.get(f"hada_t{m}")
+            up, down = (wa.t(), contract_core(t, wb, nhwc)) if t is not None else (wa, _k_order(wb, weight_shape, nhwc))
+            pairs += _padded_pair(up * sigma if m == "1" else up, down, w)
+        return ("hada", *pairs)
+    # LoKr
+    rank = None
+    if "lokr_w1" in parts:
+        w1 = parts["lokr_w1"]
+    else:
+        w1, rank = parts["lokr_w1_a"] @ parts["lokr_w1_b"], parts["lokr_w1_b"].shape[0]
+    a, b = w1.shape
+    c, d = weight_shape[0] // a, weight_shape[1] // b
+    if "lokr_w2" in parts:
+        w2 = parts["lokr_w2"]
+    elif "lokr_t2" in parts:
+        w2, rank = torch.einsum("pqyx,pc,qd->cdyx", parts["lokr_t2"], parts["lokr_w2_a"], parts["lokr_w2_b"]), parts["lokr_w2_b"].shape[0]
+    else:
+        w2, rank = parts["lokr_w2_a"] @ parts["lokr_w2_b"], parts["lokr_w2_b"].shape[0]
+    w2 = w2.reshape(c, d, *(weight_shape[2:] if conv else (1, 1)))
+    sigma = 1.0 if p.alpha is None or rank is None else p.alpha / rank
+    layout = 1 if conv and nhwc else 0
+    w2 = (w2.permute(0, 2, 3, 1) if layout else w2).reshape(c, -1)
+    return ("kron", (w1 * sigma).contiguous(), w2.contiguous(), taps, layout)
+
+
+def factor_delta(f: tuple) -> torch.Tensor:
+    """The fp32 delta (N, K) of one factor tuple as the kernel forms it (torch, any device): a product, the elementwise product
+    of two products, or a Kronecker product in the column order of the tuple's layout."""
+    if f[0] == "hada":
+        return (f[1].float() @ f[2].float().t()) * (f[3].float() @ f[4].float().t())
+    if f[0] == "kron":
+        w1, w2, taps, layout = f[1:5]
+        if not layout:
+            return torch.kron(w1, w2)                                        # [i c + p, j (d taps) + col]
+        (a, b), c, d = w1.shape, w2.shape[0], w2.shape[1] // taps
+        return torch.einsum("ij,ptq->iptjq", w1, w2.reshape(c, taps, d)).reshape(a * c, taps * b * d)
+    return f[0].float() @ f[1].float().t()
 
 
 def target_linears(module: nn.Module) -> "OrderedDict[str, nn.Linear]":
@@ -239,7 +493,9 @@ def weight_rows(w: torch.Tensor) -> Tuple[torch.Tensor, bool]:
 class _Adapter:
     def __init__(self, slot: int, scale: float):
         self.slot, self.scale = slot, scale
-        self.factors: Dict[str, tuple] = {}      # module -> (Up (N, rp), DownT (K, rp)[, magnitude (N,) fp32]), zero-padded ranks
+        # module -> (Up (N, rp), DownT (K, rp)[, magnitude (N,) fp32]), zero-padded ranks; ("hada", Up1, DownT1, Up2, DownT2[, magnitude])
+        # for LoHa; ("kron", W1, W2, taps, layout[, magnitude]) for LoKr (`build_factors`)
+        self.factors: Dict[str, tuple] = {}
 
 
 class LoraSet:
@@ -285,19 +541,20 @@ class LoraSet:
 
     # ---- changes -------------------------------------------------------------------------------
     def load(self, name: str, state_dict: Mapping[str, torch.Tensor], scale: float = 1.0, strict: bool = True,
-             convs: bool = False) -> List[str]:
+             convs: bool = False, lycoris: bool = False) -> List[str]:
         """Merge the adapter `state_dict` under `name` at `scale`.  Everything is checked before anything is written.
         `convs=True` also takes the adapter's convolution factors (LoCon) on this module's `nn.Conv2d`; DoRA magnitudes are
-        applied wherever their module is a target.  Returns the keys that were not applied (text-encoder keys always; with
-        strict=False also keys that name no target of this module, which strict=True refuses).  Tucker / LoHa / LoKr keys and
-        input-axis magnitudes ON a target raise whatever `strict` says (`parse_lora_state_dict`)."""
+        applied wherever their module is a target.  `lycoris=True` also takes Tucker cores, LoHa and LoKr factors (the module
+        docstring) on those targets.  Returns the keys that were not applied (text-encoder keys always; with
+        strict=False also keys that name no target of this module, which strict=True refuses).  Input-axis magnitudes ON a
+        target, and without `lycoris=True` Tucker / LoHa / LoKr keys, raise whatever `strict` says (`parse_lora_state_dict`)."""
         if name in self._adapters:
             raise ValueError(f"a LoRA named {name!r} is already loaded (unload it first)")
         if len(self._adapters) >= MAX_ADAPTERS:
             raise ValueError(f"at most {MAX_ADAPTERS} adapters can be loaded at once")
         targets = self.targets if convs else self.linears
         kind = "nn.Linear or nn.Conv2d" if convs else "nn.Linear"
-        placed, unplaced = parse_adapter(state_dict, targets.keys())
+        placed, unplaced = parse_adapter(state_dict, targets.keys(), lycoris=lycoris)
         foreign = [k for k in unplaced if not is_text_encoder_key(k)]
         if strict and foreign:
             hint = "" if convs else "convolution adapters are only applied on request: pass convs=True; "
@@ -309,7 +566,7 @@ class LoraSet:
             m = targets[mod]
             if isinstance(m, nn.Conv2d) and (m.groups != 1 or tuple(m.dilation) != (1, 1)):
                 raise ValueError(f"{mod}: a grouped or dilated convolution (groups {m.groups}, dilation {tuple(m.dilation)}) takes no adapter")
-            check_shapes(mod, tuple(m.weight.shape), p.down, p.up, p.magnitude)
+            check_shapes(mod, tuple(m.weight.shape), p.down, p.up, p.magnitude, p.form, p.parts)
             if isinstance(m, nn.Conv2d):
                 weight_rows(m.weight)                                  # (refuses a weight that is not dense)
         scale = float(scale)
@@ -317,20 +574,8 @@ class LoraSet:
         ad = _Adapter(slot, scale)
         with torch.no_grad():
             for mod, p in placed.items():
-                down, up, alpha = p.down, p.up, p.alpha
                 w, nhwc = weight_rows(targets[mod].weight.detach())
-                r = down.shape[0]
-                if len(targets[mod].weight.shape) == 4:               # the down factor in the K order of the weight's memory
-                    down = down[:, :, None, None] if down.dim() == 2 else down
-                    down = (down.permute(0, 2, 3, 1) if nhwc else down).reshape(r, -1)
-                    up = up.reshape(up.shape[0], r)
-                mult = 4 if w.dtype == torch.float32 else 32
-                rp = -(-r // mult) * mult
-                up_p = torch.zeros((w.shape[0], rp), dtype=w.dtype, device=w.device)
-                down_t = torch.zeros((w.shape[1], rp), dtype=w.dtype, device=w.device)
-                up_p[:, :r] = (up.to(device=w.device, dtype=torch.float32) * (alpha / r)).to(w.dtype)
-                down_t[:, :r] = down.to(device=w.device, dtype=w.dtype).t()
-                ad.factors[mod] = (up_p, down_t)
+                ad.factors[mod] = build_factors(p, w, tuple(targets[mod].weight.shape), nhwc)
                 if p.magnitude is not None:
                     ad.factors[mod] += (p.magnitude.detach().to(device=w.device, dtype=torch.float32).reshape(-1).contiguous(),)
                 if mod not in self._base:
@@ -395,10 +640,15 @@ class LoraSet:
 
     def _entries(self):
         """Per snapshotted module: (parameter, its (N, K) view, base, [(Up, DownT, slot[, magnitude]), ...]) in load order (the
-        kernel's summation order)."""
+        kernel's summation order); LoHa and LoKr tuples as `ops.lora_plan` takes them, the slot after their five leading items."""
         out = []
         for mod, base in self._base.items():
-            facs = [(*a.factors[mod][:2], a.slot, *a.factors[mod][2:]) for a in self._adapters.values() if mod in a.factors]
+            facs = []
+            for a in self._adapters.values():
+                if mod in a.factors:
+                    f = a.factors[mod]
+                    lead = 5 if isinstance(f[0], str) else 2
+                    facs.append((*f[:lead], a.slot, *f[lead:]))
             param = self.targets[mod].weight
             out.append((param, weight_rows(param.detach())[0], base, facs))
         return out
@@ -431,21 +681,26 @@ class LoraSet:
 
 def _merge_torch(w: torch.Tensor, base: torch.Tensor, facs, eff) -> None:
     """The kernel's formula in torch (CPU): fp32 products and sums, one rounding to the storage dtype, base bits when every
-    scale is zero.  `w` is the weight's (N, K) view; a factor tuple is (Up, DownT, slot) or (Up, DownT, slot, magnitude)."""
-    live = [(f[0], f[1], eff[f[2]], f[3] if len(f) > 3 else None) for f in facs if eff[f[2]] != 0.0]
+    scale is zero.  `w` is the weight's (N, K) view; a factor tuple is (Up, DownT, slot[, magnitude]), ("hada", Up1, DownT1, Up2,
+    DownT2, slot[, magnitude]) or ("kron", W1, W2, taps, layout, slot[, magnitude]); `factor_delta` forms each one's delta."""
+    live = []
+    for f in facs:
+        at = 5 if isinstance(f[0], str) else 2                      # where the slot sits
+        if eff[f[at]] != 0.0:
+            live.append((f, eff[f[at]], f[at + 1] if len(f) > at + 1 else None))
     if not live:
         w.detach().copy_(base)
         return
     delta = torch.zeros(w.shape, dtype=torch.float32)
-    if all(mag is None for _, _, _, mag in live):
-        for up, down_t, s, _ in live:
-            delta.add_(up.float() @ down_t.float().t(), alpha=s)
+    if all(mag is None for _, _, mag in live):
+        for f, s, _ in live:
+            delta.add_(factor_delta(f), alpha=s)
         w.detach().copy_((base.float() + delta).to(w.dtype))
         return
     b = base.float()
     bcoef = torch.ones((w.shape[0], 1), dtype=torch.float32)
-    for up, down_t, s, mag in live:
-        acc = up.float() @ down_t.float().t()
+    for f, s, mag in live:
+        acc = factor_delta(f)
         if mag is None:
             delta.add_(acc, alpha=s)
             continue

@@ -1468,15 +1468,17 @@ def lora_rank_multiple(dtype: torch.dtype) -> int:
 class LoraPlan:
     """Descriptor table, segment table and flat tile list of one set of targets, on the device.  Built once per load / unload;
     a scale change reuses it.  Holds every tensor the tables point at.  `dora`: some segment carries a magnitude; the plan then
-    has 6-word segment rows, the tile list of the norm pass and its workspace (st_lora_merge_dora)."""
+    has 6-word segment rows, the tile list of the norm pass and its workspace (st_lora_merge_dora).  `forms`: some segment is a
+    LoHa or LoKr one; the plan then has the wide rows of st_lora_merge_forms (and a norm pass only with `dora`)."""
 
     def __init__(self, targets, segments, tiles, n_targets, n_segments, n_tiles, n_slots, max_rank, dtype, keep,
-                 norm_tiles=None, workspace=None):
+                 norm_tiles=None, workspace=None, forms=False):
         self.targets, self.segments, self.tiles = targets, segments, tiles
         self.n_targets, self.n_segments, self.n_tiles, self.n_slots, self.max_rank = n_targets, n_segments, n_tiles, n_slots, max_rank
         self.dtype, self.keep = dtype, keep
         self.norm_tiles, self.workspace = norm_tiles, workspace
         self.dora = workspace is not None
+        self.forms = forms
 
 
 def _lora_tiles(counts, which) -> torch.Tensor:
@@ -1488,19 +1490,43 @@ def _lora_tiles(counts, which) -> torch.Tensor:
     return torch.stack([tgt, torch.arange(int(cnt.sum()), dtype=torch.int64) - first[idx]], dim=1).to(torch.int32).contiguous()
 
 
-def lora_plan(entries) -> LoraPlan:
-    """`entries`: one (weight, base, [(up, down_t, slot) or (up, down_t, slot, magnitude), ...]) per target.  weight / base:
-    (N, K) contiguous, same dtype, distinct storage; up: (N, rp), down_t: (K, rp) - the down factor transposed - contiguous in
-    the weight's dtype with rp a multiple of lora_rank_multiple(dtype) (zero padding); magnitude: None, or the DoRA magnitude
-    of the segment, N fp32 values on the device (any shape).  A target with no factors is restored to its base by the launch."""
+LORA_KIND_PLAIN, LORA_KIND_HADA, LORA_KIND_KRON = 0, 1, 2      # ST_LORA_KIND_*
+LORA_FORM_WORDS = 12                                           # ST_LORA_FORM_WORDS
+
+
+def _lora_pair(up, down_t, n, k, dtype, device, mult) -> int:
+    """Checks one factor pair of a (n, k) weight; returns its padded rank."""
+    _C.require_device(up, down_t)
+    rp = up.shape[-1]
+    if (tuple(up.shape) != (n, rp) or tuple(down_t.shape) != (k, rp) or rp == 0 or rp % mult or up.dtype != dtype
+            or down_t.dtype != dtype or not up.is_contiguous() or not down_t.is_contiguous()
+            or up.data_ptr() % 16 or down_t.data_ptr() % 16 or up.device != device or down_t.device != device):
+        raise BackendError(f"lora_plan: factors of a {(n, k)} weight must be up ({n}, rp) and down_t ({k}, rp), contiguous "
+                           f"{dtype}, rp a multiple of {mult}; got {tuple(up.shape)} {up.dtype} and {tuple(down_t.shape)} {down_t.dtype}")
+    return rp
+
+
+def lora_plan(entries, forms: bool = False) -> LoraPlan:
+    """`entries`: one (weight, base, [factors, ...]) per target.  weight / base: (N, K) contiguous, same dtype, distinct
+    storage.  A factor tuple is one of
+        (up, down_t, slot[, magnitude])                                  up: (N, rp), down_t: (K, rp) - the down factor transposed
+        ("hada", up1, down1_t, up2, down2_t, slot[, magnitude])          LoHa: (up1 @ down1) * (up2 @ down2), two such pairs
+        ("kron", w1, w2, taps, layout, slot[, magnitude])                LoKr: w1 (a, b), w2 (c, d * taps), fp32 for every dtype,
+                                                                         a c = N, b d taps = K; layout 1: K runs (tap, channel) -
+                                                                         a channels_last conv weight - and w2's columns (tap, q);
+                                                                         layout 0: K runs (channel, tap) and w2's columns (q, tap)
+    Factor pairs are contiguous in the weight's dtype with rp a multiple of lora_rank_multiple(dtype) (zero padding);
+    magnitude: None, or the DoRA magnitude of the segment, N fp32 values on the device (any shape).  A target with no factors
+    is restored to its base by the launch.  Plans without a "hada" / "kron" tuple keep the tables and entry points they had;
+    `forms=True` gives such a plan the wide rows too (the same bits through st_lora_merge_forms: what the tests compare)."""
     if not entries:
         raise BackendError("lora_plan: no targets")
     w0 = entries[0][0]
     dtype, device = w0.dtype, w0.device
     _C.dtype_code(dtype)
     mult = lora_rank_multiple(dtype)
-    trows, srows, counts, keep, slots = [], [], [], [], 0
-    ws_floats, norm_targets = 0, []
+    trows, srows, wide, counts, keep, slots = [], [], [], [], [], 0
+    ws_floats, norm_targets, forms, max_rank = 0, [], bool(forms), 0
     for w, base, factors in entries:
         _C.require_device(w, base)
         if w.dim() != 2 or not w.is_contiguous() or w.dtype != dtype or w.device != device:
@@ -1513,18 +1539,43 @@ def lora_plan(entries) -> LoraPlan:
         tiles_k = -(-k // _C.LORA_TILE_K)
         trows.append([w.data_ptr(), base.data_ptr(), n, k, len(srows), len(factors)])
         for fac in factors:
-            up, down_t, slot = fac[:3]
-            mag = fac[3] if len(fac) > 3 else None
-            _C.require_device(up, down_t)
-            rp = up.shape[-1]
-            if (tuple(up.shape) != (n, rp) or tuple(down_t.shape) != (k, rp) or rp == 0 or rp % mult or up.dtype != dtype
-                    or down_t.dtype != dtype or not up.is_contiguous() or not down_t.is_contiguous()
-                    or up.data_ptr() % 16 or down_t.data_ptr() % 16 or up.device != device or down_t.device != device):
-                raise BackendError(f"lora_plan: factors of a {(n, k)} weight must be up ({n}, rp) and down_t ({k}, rp), contiguous "
-                                   f"{dtype}, rp a multiple of {mult}; got {tuple(up.shape)} {up.dtype} and {tuple(down_t.shape)} {down_t.dtype}")
-            if rp > LORA_MAX_RANK or slot < 0:
-                raise BackendError(f"lora_plan: padded rank {rp} (at most {LORA_MAX_RANK}) / scale slot {slot}")
-            row = [up.data_ptr(), down_t.data_ptr(), rp, slot, 0, 0]
+            kind = fac[0] if isinstance(fac[0], str) else "plain"
+            if kind == "plain":
+                up, down_t, slot = fac[:3]
+                mag = fac[3] if len(fac) > 3 else None
+                rp = _lora_pair(up, down_t, n, k, dtype, device, mult)
+                body = [up.data_ptr(), down_t.data_ptr(), rp, 0, 0, 0, 0, 0]
+                code, held, ranks = LORA_KIND_PLAIN, [up, down_t], [rp]
+            elif kind == "hada" and len(fac) in (6, 7):
+                up, down_t, up2, down2_t, slot = fac[1:6]
+                mag = fac[6] if len(fac) > 6 else None
+                rp, rp2 = _lora_pair(up, down_t, n, k, dtype, device, mult), _lora_pair(up2, down2_t, n, k, dtype, device, mult)
+                body = [up.data_ptr(), down_t.data_ptr(), rp, up2.data_ptr(), down2_t.data_ptr(), rp2, 0, 0]
+                code, held, ranks, forms = LORA_KIND_HADA, [up, down_t, up2, down2_t], [rp, rp2], True
+            elif kind == "kron" and len(fac) in (6, 7):
+                w1, w2, taps, layout, slot = fac[1:6]
+                mag = fac[6] if len(fac) > 6 else None
+                _C.require_device(w1, w2)
+                taps, layout = int(taps), int(layout)
+                ok = (w1.dim() == 2 and w2.dim() == 2 and w1.dtype == torch.float32 and w2.dtype == torch.float32 and w1.is_contiguous()
+                      and w2.is_contiguous() and w1.device == device and w2.device == device and w1.data_ptr() % 16 == 0
+                      and w2.data_ptr() % 16 == 0 and w1.numel() > 0 and w2.numel() > 0 and taps >= 1 and layout in (0, 1)
+                      and w2.shape[1] % taps == 0 and (layout == 0 or k % taps == 0))
+                if ok:
+                    (a, b), c, d = w1.shape, w2.shape[0], w2.shape[1] // taps
+                    ok = a * c == n and b * d * taps == k
+                if not ok:
+                    raise BackendError(f"lora_plan: the Kronecker tables of a {(n, k)} weight must be w1 (a, b) and w2 (c, d * taps), "
+                                       f"contiguous 16-byte aligned fp32 on {device}, with a * c == {n} and b * d * taps == {k}, layout 0 or 1; "
+                                       f"got {tuple(w1.shape)} {w1.dtype}, {tuple(w2.shape)} {w2.dtype}, taps {taps}, layout {layout}")
+                body = [w1.data_ptr(), w2.data_ptr(), a, b, c, d, taps, layout]
+                code, held, ranks, forms = LORA_KIND_KRON, [w1, w2], [], True
+            else:
+                raise BackendError(f"lora_plan: unknown factor tuple {kind!r} of {len(fac)} items")
+            slot = int(slot)
+            if any(r > LORA_MAX_RANK for r in ranks) or slot < 0:
+                raise BackendError(f"lora_plan: padded rank {max(ranks, default=0)} (at most {LORA_MAX_RANK}) / scale slot {slot}")
+            row = [body[0], body[1], body[2], slot, 0, 0]
             if mag is not None:
                 _C.require_device(mag)
                 if mag.dtype != torch.float32 or mag.numel() != n or not mag.is_contiguous() or mag.device != device:
@@ -1536,29 +1587,44 @@ def lora_plan(entries) -> LoraPlan:
                     norm_targets.append(len(trows) - 1)
                 keep.append(mag)
             srows.append(row)
+            wide.append([code, slot, row[4], row[5], *body])
+            max_rank = max([max_rank, *ranks])
             slots = max(slots, slot + 1)
-            keep += [up, down_t]
+            keep += held
         counts.append(-(-n // _C.LORA_TILE_N) * tiles_k)
         keep += [w, base]
     tiles = _lora_tiles(counts, list(range(len(counts))))
-    args = (len(trows), len(srows), tiles.shape[0], slots, max((r[2] for r in srows), default=0), dtype, keep)
+    args = (len(trows), len(srows), tiles.shape[0], slots, max_rank, dtype, keep)
     targets = torch.tensor(trows, dtype=torch.int64).to(device)
+    dora = dict(norm_tiles=_lora_tiles(counts, norm_targets).to(device),
+                workspace=torch.empty(ws_floats, dtype=torch.float32, device=device)) if norm_targets else {}
+    if forms and srows:            # a LoHa or LoKr segment: the wide rows of st_lora_merge_forms
+        segments = torch.tensor(wide, dtype=torch.int64).reshape(-1, LORA_FORM_WORDS).to(device)
+        return LoraPlan(targets, segments, tiles.to(device), *args, forms=True, **dora)
     if not norm_targets:           # no DoRA segment: the 4-word rows of st_lora_merge
         segments = torch.tensor([r[:4] for r in srows], dtype=torch.int64).reshape(-1, 4).to(device) if srows else None
         return LoraPlan(targets, segments, tiles.to(device), *args)
     segments = torch.tensor(srows, dtype=torch.int64).reshape(-1, 6).to(device)
-    return LoraPlan(targets, segments, tiles.to(device), *args, norm_tiles=_lora_tiles(counts, norm_targets).to(device),
-                    workspace=torch.empty(ws_floats, dtype=torch.float32, device=device))
+    return LoraPlan(targets, segments, tiles.to(device), *args, **dora)
 
 
 def lora_merge(plan: LoraPlan, scales: torch.Tensor) -> None:
     """Rebuild every target of `plan` from its base: W = round(base + sum_j scales[slot_j] * up_j @ down_j), one launch; with
     DoRA segments in the plan W = round(base + sum_j (g_j V_j - base)), V_j = base + scales[slot_j] * up_j @ down_j and
-    g_j[n] = magnitude_j[n] / ||V_j[n]|| (1 for a plain segment), two launches (row norms, then the merge).
+    g_j[n] = magnitude_j[n] / ||V_j[n]|| (1 for a plain segment), two launches (row norms, then the merge).  A plan with LoHa
+    or LoKr segments forms their deltas as `lora_plan` states them and is otherwise the same (st_lora_merge_forms).
     Writes through raw pointers: the caller bumps the version counters of the rewritten parameters."""
     _C.require_device(scales)
     if scales.dtype != torch.float32 or not scales.is_contiguous() or scales.numel() < max(plan.n_slots, 1) or scales.device != plan.targets.device:
         raise BackendError(f"lora_merge: scales must be a contiguous fp32 device table of at least {max(plan.n_slots, 1)} slots")
+    if plan.forms:
+        norm = plan.norm_tiles
+        _C.check(_C.load().st_lora_merge_forms(plan.targets.data_ptr(), plan.n_targets, plan.segments.data_ptr(), plan.n_segments, plan.max_rank,
+                                               plan.tiles.data_ptr(), plan.n_tiles, _ptr(norm), 0 if norm is None else norm.shape[0],
+                                               scales.data_ptr(), scales.numel(), _ptr(plan.workspace),
+                                               0 if plan.workspace is None else plan.workspace.numel() * 4,
+                                               _C.dtype_code(plan.dtype), _C.stream_ptr()), "lora_merge")
+        return
     if plan.dora:
         _C.check(_C.load().st_lora_merge_dora(plan.targets.data_ptr(), plan.n_targets, plan.segments.data_ptr(), plan.n_segments, plan.max_rank,
                                               plan.tiles.data_ptr(), plan.n_tiles, plan.norm_tiles.data_ptr(), plan.norm_tiles.shape[0],

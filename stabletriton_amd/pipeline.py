@@ -245,12 +245,13 @@ class DenoiseLoop:
         else:
             self.refresh_weights()
 
-    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True, convs: bool = False):
+    def load_lora(self, name: str, state_dict, scale: float = 1.0, strict: bool = True, convs: bool = False, lycoris: bool = False):
         """Merge a LoRA state dict (PEFT / diffusers / kohya keys, lora.parse_lora_state_dict) into the UNet at `scale`.
-        DoRA magnitudes apply; `convs=True` also takes the adapter's convolution factors (LoCon) on the UNet's Conv2d.
+        DoRA magnitudes apply; `convs=True` also takes the adapter's convolution factors (LoCon) on the UNet's Conv2d,
+        `lycoris=True` its Tucker cores, LoHa and LoKr factors (lora.py).
         Returns the keys that were not applied.  A loop that shares its UNet with another owner shares the adapters; the
         other owner re-derives its own per-prompt state (its next set_conditioning does)."""
-        left = self._lora_set().load(name, state_dict, scale, strict, convs)
+        left = self._lora_set().load(name, state_dict, scale, strict, convs, lycoris)
         self._weights_changed()
         return left
 
