@@ -46,7 +46,7 @@ enum {
     ST_EPI_ROWBIAS   = 16   /* + rowbias[batch(m)][n]     (time-embedding add)    */
 };
 
-int         st_abi_version(void);          /* bumps on any signature or contract change; this header is ABI 17
+int         st_abi_version(void);          /* bumps on any signature or contract change; this header is ABI 18
                                               (6: next-weights hint passed per call, st_timestep_sincos; 7: fp8 entry points; 8: GroupNorm partials from the
                                               producer; 9: st_ln_linear_xattn; 10: ST_F16 accepted by every entry point
                                               that takes a dtype, st_ln_linear_xattn takes a dtype; 11: fp8 plan with
@@ -57,9 +57,10 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               17: st_cfg_euler_step, st_cfg_step_workspace_bytes; also st_dpmpp2m_step, and then
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
                                               st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
-                                              st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then st_lora_merge_dora,
-                                              and then st_lora_merge_forms,
-                                              added without a bump: new entry points, no existing signature or contract changed) */
+                                              st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then a DoRA and a LoHa / LoKr entry point beside
+                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed;
+                                              18: st_lora_merge takes one ST_LORA_FORM_WORDS segment row, the norm pass's tables and `forms`, and is
+                                              the only LoRA entry point again: the two beside it are removed) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -269,69 +270,53 @@ int st_sde_step(float* latent, const void* eps, void* next_in, float* history, c
                 int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
 
 /* LoRA merge: one grouped launch rebuilds every adapted weight from its base snapshot (stabletriton_amd/lora.py owns the
- * tables).  For every target t, elementwise over its row-major (N_t, K_t) weight of `dtype`:
- *   W_t[n][k] = round( fp32(Base_t[n][k]) + sum_j scales[slot_j] * sum_r Up_tj[n][r] * DownT_tj[k][r] ),  fp32 throughout,
- * written in place (W keeps its address).  All tables are on the device:
- *   targets:  n_targets rows of 6 int64  [W, Base, N, K, first segment, segments]   (Base never aliases W);
- *   segments: n_segments rows of 4 int64 [Up, DownT, padded rank rp, scale slot]: Up is (N, rp) and DownT - the down factor
- *             TRANSPOSED - (K, rp), both row-major in `dtype`, 16-byte aligned, the ranks zero-padded to rp, a multiple of
- *             32 (16-bit dtypes: one MFMA k) or of 4 (ST_F32), at most ST_LORA_MAX_RANK; alpha / rank is folded into Up
- *             by the caller;
- *             max_rank is the largest rp in the table (it sizes the kernel's LDS images; a larger segment is skipped);
- *   tiles:    n_tiles rows of 2 int32 [target, tile]: one workgroup each, tile = row_tile * ceil(K / ST_LORA_TILE_K) +
- *             column_tile over ST_LORA_TILE_N x ST_LORA_TILE_K tiles; a target is rebuilt where its tiles are listed;
- *   scales:   n_scales floats, one slot per loaded adapter: changing a scale is a copy into this table and one launch.
- * A segment whose scale is 0 is skipped, and a weight with no non-zero scale receives its base's bits.  16-byte accesses
- * where K is a multiple of 16 bytes of elements and W / Base are 16-byte aligned, elementwise otherwise; N and K need not be
- * tile multiples.  No atomics, nothing split over the rank: bitwise deterministic.  The tables' contents are the caller's
- * contract (they cannot be checked from the host). */
-enum { ST_LORA_TILE_N = 64, ST_LORA_TILE_K = 128, ST_LORA_MAX_RANK = 128 };
-int st_lora_merge(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
-                  const int* tiles, long n_tiles, const float* scales, int n_scales, int dtype, void* stream);
-
-/* The same merge with DoRA segments: a segment may carry a magnitude m (N floats), and its rows are renormalised,
- *   V_j = fp32(Base_t) + s_j Up_tj DownT_tj^T,   g_j[n] = m_j[n] / ||V_j[n, :]||_2   (g_j = 1 without a magnitude),
- *   W_t[n][k] = round( (1 + sum_j (g_j[n] - 1)) fp32(Base_t[n][k]) + sum_j g_j[n] s_j sum_r Up_tj[n][r] DownT_tj[k][r] ),
+ * tables).  For every target t, elementwise over its row-major (N_t, K_t) weight of `dtype`, fp32 throughout, written in
+ * place (W keeps its address), with s_j = scales[slot_j] and acc_j segment j's fp32 delta:
+ *   W_t[n][k] = round( (1 + sum_j (g_j[n] - 1)) fp32(Base_t[n][k]) + sum_j g_j[n] s_j acc_j[n][k] )
+ *   V_j = fp32(Base_t) + s_j acc_j,   g_j[n] = m_j[n] / ||V_j[n, :]||_2  for a segment with a magnitude m_j (DoRA), else g_j = 1,
  * which is Base + sum_j (g_j (.) V_j - Base): PEFT's DoRA, the scale inside the norm, each adapter normalised against the
- * base alone.  Tables as st_lora_merge, except
- *   segments:   n_segments rows of 6 int64 [Up, DownT, rp, scale slot, magnitude, workspace offset]: magnitude is the device
- *               address of N fp32 values, or 0 for a plain segment; the offset (in floats) is where the segment's
- *               N * ceil(K / ST_LORA_TILE_K) partial sums of squares live in `workspace` (unused for a plain segment);
- *   norm_tiles: n_norm_tiles rows of [target, tile] listing EVERY tile of every target that has a DoRA segment (a subset of
- *               `tiles`, possibly empty);
- *   workspace:  fp32, device, at least the largest offset + its segment's size; written by the first launch, read by the second.
- * Two launches on `stream` (one when n_norm_tiles == 0): the norm pass writes, per DoRA segment with a non-zero scale, each
- * row's sum of squares of V over one K-tile (V from the unrounded fp32 product); the merge pass adds a row's partials in a
- * fixed order.  A segment whose scale is 0 is skipped whole, magnitude included: a weight with no non-zero scale receives
- * its base's bits.  A row of V_j whose sum of squares is exactly 0 takes g_j[n] = 0 (its g V is the zero it was; no inf or
- * NaN is produced).  A table without any magnitude gives st_lora_merge's bits.  No atomics: bitwise deterministic. */
-int st_lora_merge_dora(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
-                       const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
-                       float* workspace, size_t workspace_bytes, int dtype, void* stream);
-
-/* The same merge with segments of other factorisations (LyCORIS's LoHa and LoKr; Tucker cores are contracted by the caller).
- * A segment has a kind, which only decides how its fp32 delta acc_j is formed; the rest is st_lora_merge_dora's:
- *   V_j = fp32(Base_t) + s_j acc_j,  g_j as there,  W_t = round( (1 + sum_j (g_j - 1)) fp32(Base_t) + sum_j g_j s_j acc_j ).
+ * base alone; without any magnitude it is round( fp32(Base) + sum_j s_j acc_j ).  A segment's kind only decides how acc_j is formed:
  *   ST_LORA_KIND_PLAIN  acc[n][k] = sum_r Up[n][r] DownT[k][r]
- *   ST_LORA_KIND_HADA   acc[n][k] = (sum_r Up1[n][r] DownT1[k][r]) * (sum_r Up2[n][r] DownT2[k][r])      one fp32 product of the two sums
- *   ST_LORA_KIND_KRON   acc[n][k] = W1[n / c][j] * W2[n % c][col],  W1 (a, b) and W2 (c, d * taps) row-major FP32 tables for
+ *   ST_LORA_KIND_HADA   acc[n][k] = (sum_r Up1[n][r] DownT1[k][r]) * (sum_r Up2[n][r] DownT2[k][r])      LoHa: one fp32 product of the two sums
+ *   ST_LORA_KIND_KRON   acc[n][k] = W1[n / c][j] * W2[n % c][col],  LoKr: W1 (a, b) and W2 (c, d * taps) row-major FP32 tables for
  *                       every `dtype`, 16-byte aligned, a * c = N and b * d * taps = K.  layout 1 (a channels_last conv weight,
  *                       K runs tap-major): k = tap * (b d) + j * d + q, col = tap * d + q.  layout 0 (a contiguous conv weight
  *                       or a Linear, taps = 1): k = (j * d + q) * taps + tap, col = q * taps + tap.  Any scalar (alpha / rank)
- *                       is folded into W1 by the caller.
- * Tables as st_lora_merge_dora, except
- *   segments: n_segments rows of ST_LORA_FORM_WORDS int64
- *               [kind, scale slot, magnitude or 0, workspace offset,  Up1, DownT1, rp1,  Up2, DownT2, rp2,  0, 0]     PLAIN (pair 2 unused, 0) / HADA
- *               [kind, scale slot, magnitude or 0, workspace offset,  W1, W2,  a, b, c, d, taps, layout]              KRON
- *             factor pairs as st_lora_merge's (each padded rank a multiple of 32 / 4, at most ST_LORA_MAX_RANK);
- *   max_rank: the largest padded rank of any factor pair in the table; 0 when every segment is KRON.
- * The norm pass runs only when n_norm_tiles > 0 (some segment has a magnitude).  A HADA segment stages its two pairs one
- * after the other through the same LDS images.  A table of PLAIN segments gives st_lora_merge's bits (st_lora_merge_dora's
- * with magnitudes).  Scale 0 skips a segment whole; no atomics, a fixed order per element: bitwise deterministic. */
+ *                       is folded into W1 by the caller.  (Tucker cores are contracted by the caller.)
+ * All tables are on the device:
+ *   targets:    n_targets rows of 6 int64  [W, Base, N, K, first segment, segments]   (Base never aliases W);
+ *   segments:   n_segments rows of ST_LORA_FORM_WORDS int64
+ *                 [kind, scale slot, magnitude or 0, workspace offset,  Up1, DownT1, rp1,  Up2, DownT2, rp2,  0, 0]     PLAIN (pair 2 unused, 0) / HADA
+ *                 [kind, scale slot, magnitude or 0, workspace offset,  W1, W2,  a, b, c, d, taps, layout]              KRON
+ *               Up is (N, rp) and DownT - the down factor TRANSPOSED - (K, rp), both row-major in `dtype`, 16-byte aligned, the
+ *               ranks zero-padded to rp, a multiple of 32 (16-bit dtypes: one MFMA k) or of 4 (ST_F32), at most
+ *               ST_LORA_MAX_RANK; alpha / rank is folded into Up by the caller.  magnitude is the device address of N fp32
+ *               values; the offset (in floats) is where the segment's N * ceil(K / ST_LORA_TILE_K) partial sums of squares
+ *               live in `workspace` (unused without a magnitude);
+ *   max_rank:   the largest rp of any factor pair in the table (it sizes the kernel's LDS images; a larger segment is
+ *               skipped); 0 when nothing is staged: no segment, or every segment is KRON;
+ *   tiles:      n_tiles rows of 2 int32 [target, tile]: one workgroup each, tile = row_tile * ceil(K / ST_LORA_TILE_K) +
+ *               column_tile over ST_LORA_TILE_N x ST_LORA_TILE_K tiles; a target is rebuilt where its tiles are listed;
+ *   norm_tiles: n_norm_tiles rows of [target, tile] listing EVERY tile of every target that has a segment with a magnitude (a
+ *               subset of `tiles`; empty, and then NULL is fine, when there is none);
+ *   scales:     n_scales floats, one slot per loaded adapter: changing a scale is a copy into this table and one launch;
+ *   workspace:  fp32, at least the largest offset + its segment's size (NULL / 0 with n_norm_tiles == 0);
+ *   forms:      non-zero when some segment's kind is not PLAIN.  It selects the kernels that can form every kind; they hold
+ *               more registers, so a table of PLAIN segments should state 0.  With 0 a segment of another kind is SKIPPED
+ *               (never read as a factor pair).  Either value gives a PLAIN table the same bits.
+ * One launch on `stream`, or two when n_norm_tiles > 0: the norm pass writes, per segment with a magnitude and a non-zero
+ * scale, each row's sum of squares of V over one K-tile (V from the unrounded fp32 product); the merge pass adds a row's
+ * partials in a fixed order.  A segment whose scale is 0 is skipped whole, magnitude included, and a weight with no non-zero
+ * scale (or no segment) receives its base's bits.  A row of V_j whose sum of squares is exactly 0 takes g_j[n] = 0 (its g V
+ * is the zero it was; no inf or NaN is produced).  A HADA segment stages its two pairs one after the other through the same
+ * LDS images.  16-byte accesses where K is a multiple of 16 bytes of elements and W / Base are 16-byte aligned, elementwise
+ * otherwise; N and K need not be tile multiples.  No atomics, nothing split over the rank, a fixed order per element:
+ * bitwise deterministic.  The tables' contents are the caller's contract (they cannot be checked from the host). */
+enum { ST_LORA_TILE_N = 64, ST_LORA_TILE_K = 128, ST_LORA_MAX_RANK = 128 };
 enum { ST_LORA_KIND_PLAIN = 0, ST_LORA_KIND_HADA = 1, ST_LORA_KIND_KRON = 2, ST_LORA_FORM_WORDS = 12 };
-int st_lora_merge_forms(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
-                        const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
-                        float* workspace, size_t workspace_bytes, int dtype, void* stream);
+int st_lora_merge(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
+                  const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
+                  float* workspace, size_t workspace_bytes, int dtype, int forms, void* stream);
 
 /* Sinusoidal timestep features (unet_pt.py:17-36; target of the reference's
  * fuse_timesteps pass, optimizers/replace_timesteps.py:33-58):

@@ -17,7 +17,7 @@ ST_F32, ST_BF16, ST_F16, ST_F32S = 0, 1, 2, 3
 ST_NCHW, ST_NHWC = 0, 1
 LORA_TILE_N, LORA_TILE_K = 64, 128      # st_lora_merge's tile (ST_LORA_TILE_N / _K)
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_RESIDUAL, EPI_ROWBIAS = 1, 2, 4, 8, 16
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _p, _i, _l, _f, _z = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_size_t
 
@@ -55,9 +55,7 @@ SIGNATURES = {
     "st_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_philox_normal": (_i, [_p, _p, _i, _l, C.c_uint, _p]),
     "st_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
-    "st_lora_merge": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _i, _i, _p]),
-    "st_lora_merge_dora": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _l, _p, _i, _p, _z, _i, _p]),
-    "st_lora_merge_forms": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _l, _p, _i, _p, _z, _i, _p]),
+    "st_lora_merge": (_i, [_p, _i, _p, _i, _i, _p, _l, _p, _l, _p, _i, _p, _z, _i, _i, _p]),
     "st_freeu_workspace_bytes": (_z, [_i, _i, _l]),
     "st_freeu_stat_rows": (_i, [_l]),
     "st_freeu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _i, _p, _z, _p]),

@@ -16,7 +16,7 @@
 // (measured on SDXL-base at rank 128: 5.4 ms against this form's figure in DESIGN.md).  The ranks are zero-padded to the
 // MFMA's k = 32 by the host, which is exact and leaves no remainder path.  fp32 models use plain fp32 FMAs, ranks padded to 4.
 //
-// DoRA (st_lora_merge_dora) renormalises a segment's rows: V_j = Base + s_j Up_j Down_j, g_j[n] = m_j[n] / ||V_j[n, :]||,
+// DoRA renormalises a segment's rows: V_j = Base + s_j Up_j Down_j, g_j[n] = m_j[n] / ||V_j[n, :]||,
 //
 //   W_t[n][k] = round_to_dtype( (1 + sum_j (g_j[n] - 1)) fp32(Base_t[n][k]) + sum_j g_j[n] s_j sum_r Up_tj[n][r] DownT_tj[k][r] )
 //
@@ -35,7 +35,7 @@
 // order by every workgroup that needs them: no atomics, two merges give the same bits.  A segment at scale 0 is skipped whole in both
 // passes, magnitude included, so "all scales zero" still copies the base's bits.
 //
-// Other factorisations (st_lora_merge_forms): a segment has a KIND, and the kind only decides how the segment's fp32 tile
+// Other factorisations: a segment has a KIND, and the kind only decides how the segment's fp32 tile
 // `acc` is formed; the scale-0 skip, the DoRA norm and gain, sum = fma(coef, acc, sum) and the final rounding are shared.
 //   PLAIN  acc = Up . Down                                    (the code above)
 //   HADA   acc = (Up_1 . Down_1) (.) (Up_2 . Down_2)          LoHa: two products, multiplied elementwise in fp32.  The two
@@ -46,7 +46,8 @@
 //          (layout 1, I = b d), k = (j d + q) taps + tap for a contiguous one (layout 0), a Linear has one tap; col is
 //          tap d + q resp. q taps + tap, so in both layouts W2's row is read contiguously where W1's scalar is constant, and
 //          with d (layout 1) or d taps (layout 0) a multiple of the 16-byte vector one index computation serves the whole vector.
-// The new kinds live in their own kernel instantiations (FORMS); st_lora_merge and st_lora_merge_dora keep theirs.
+// HADA and KRON live in their own kernel instantiations (FORMS): they cost registers - an occupancy step - that a table of
+// PLAIN segments, the common case, does not pay.  The host states which a table needs; the lean kernels skip what they cannot form.
 #include "common.h"
 
 namespace {
@@ -55,11 +56,9 @@ constexpr int LORA_THREADS = 256;
 constexpr int LORA_TN = ST_LORA_TILE_N;      // 64: four waves of 16 rows
 constexpr int LORA_TK = ST_LORA_TILE_K;      // 128: four pairs of MFMA tiles
 constexpr int TGT_WORDS = 6;
-enum { MODE_PLAIN = 0, MODE_DORA = 1, MODE_NORM = 2 };      // st_lora_merge's kernel; the DoRA merge pass; the DoRA norm pass
+enum { MODE_PLAIN = 0, MODE_DORA = 1, MODE_NORM = 2 };      // the merge without magnitudes; the DoRA merge pass; the DoRA norm pass
 enum { KIND_PLAIN = ST_LORA_KIND_PLAIN, KIND_HADA = ST_LORA_KIND_HADA, KIND_KRON = ST_LORA_KIND_KRON };
-// a segment row is [Up, DownT, rp, slot] for st_lora_merge, [Up, DownT, rp, slot, magnitude or 0, workspace offset] for DoRA and
-// the ST_LORA_FORM_WORDS-word row of the header for st_lora_merge_forms
-template <int MODE, bool FORMS> struct SegRow { static constexpr int WORDS = FORMS ? (int)ST_LORA_FORM_WORDS : MODE == MODE_PLAIN ? 4 : 6; };
+constexpr int SEG_WORDS = ST_LORA_FORM_WORDS;      // one row format (the header's) for every kernel
 
 struct Segment {
     int kind, slot;
@@ -77,24 +76,13 @@ struct Segment {
     __device__ __forceinline__ int layout() const { return (int)x[5]; }
 };
 
-template <int MODE, bool FORMS>
 __device__ __forceinline__ Segment load_segment(const long long* __restrict__ segments, int j) {
-    const long long* sg = segments + (long)j * SegRow<MODE, FORMS>::WORDS;
+    const long long* sg = segments + (long)j * SEG_WORDS;
     Segment s;
-    if constexpr (FORMS) {
-        s.kind = (int)sg[0], s.slot = (int)sg[1], s.mag = sg[2], s.ws = sg[3];
-        s.p0 = (const void*)sg[4], s.p1 = (const void*)sg[5];
+    s.kind = (int)sg[0], s.slot = (int)sg[1], s.mag = sg[2], s.ws = sg[3];
+    s.p0 = (const void*)sg[4], s.p1 = (const void*)sg[5];
 #pragma unroll
-        for (int i = 0; i < 6; ++i) s.x[i] = sg[6 + i];
-    } else {
-        s.kind = KIND_PLAIN;
-        s.p0 = (const void*)sg[0], s.p1 = (const void*)sg[1];
-        s.x[0] = sg[2];
-        s.x[1] = s.x[2] = s.x[3] = s.x[4] = s.x[5] = 0;
-        s.slot = (int)sg[3];
-        s.mag = MODE != MODE_PLAIN ? sg[4] : 0;
-        s.ws = MODE != MODE_PLAIN ? sg[5] : 0;
-    }
+    for (int i = 0; i < 6; ++i) s.x[i] = sg[6 + i];
     return s;
 }
 
@@ -306,9 +294,10 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge16_kernel(const long l
     float bcoef = 1.f;                                          // (DoRA) 1 + sum_j (g_j[n] - 1), what the base is scaled by
     bool merged = false, staged = false;
     for (int j = 0; j < tg.nseg; ++j) {
-        const Segment sg = load_segment<MODE, FORMS>(segments, tg.seg0 + j);
+        const Segment sg = load_segment(segments, tg.seg0 + j);
         const float s = scales[sg.slot];
         if (s == 0.f) continue;                                 // (uniform) an adapter at scale 0 contributes nothing, whatever it holds
+        if (!FORMS && sg.kind != KIND_PLAIN) continue;          // (uniform) a wrong `forms` flag drops a segment; its tables are never read as factors
         if (MODE == MODE_NORM && sg.mag == 0) continue;         // (uniform) a plain segment has no norm
         // (uniform; a table that breaks the max_rank contract: no image overrun)
         if (sg.kind != KIND_KRON && ((sg.rp() + 8) * 2 > lds_row || (sg.rp2() + 8) * 2 > lds_row)) continue;
@@ -452,9 +441,10 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long l
     }
     bool merged = false;
     for (int j = 0; j < tg.nseg; ++j) {
-        const Segment sg = load_segment<MODE, FORMS>(segments, tg.seg0 + j);
+        const Segment sg = load_segment(segments, tg.seg0 + j);
         const float s = scales[sg.slot];
         if (s == 0.f) continue;
+        if (!FORMS && sg.kind != KIND_PLAIN) continue;          // (uniform; see the 16-bit kernel)
         if (MODE == MODE_NORM && sg.mag == 0) continue;
         merged = true;
         float acc[8][4];
@@ -519,7 +509,7 @@ __global__ __launch_bounds__(LORA_THREADS) void lora_merge32_kernel(const long l
         finish_row<float, MODE == MODE_DORA>(tg, n0 + i, k0, sum[i], merged, vec, MODE == MODE_DORA ? bcoef[i] : 1.f);
 }
 
-template <int MODE, bool FORMS = false>
+template <int MODE, bool FORMS>
 static int lora_launch(const char* what, const long long* targets, const long long* segments, int max_rank, const int* tiles, long n_tiles,
                        const float* scales, float* workspace, int dtype, hipStream_t st) {
     const dim3 grid((unsigned)n_tiles), block(LORA_THREADS);
@@ -529,74 +519,46 @@ static int lora_launch(const char* what, const long long* targets, const long lo
         hipLaunchKernelGGL((lora_merge16_kernel<bf16, MODE, FORMS>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
     else if (dtype == ST_F16)
         hipLaunchKernelGGL((lora_merge16_kernel<f16, MODE, FORMS>), grid, block, lds, st, targets, segments, tiles, scales, lds_row, workspace);
-    else if (dtype == ST_F32)
+    else                                                          // ST_F32: the entry point has checked the dtype
         hipLaunchKernelGGL((lora_merge32_kernel<MODE, FORMS>), grid, block, 0, st, targets, segments, tiles, scales, workspace);
-    else
-        return st_fail("%s: unsupported dtype %d", what, dtype);
     return st_check_launch(what);
+}
+
+// the norm pass (when any segment has a magnitude), then the merge, in the FORMS instantiations or the lean ones
+template <bool FORMS>
+static int lora_passes(const long long* targets, const long long* segments, int max_rank, const int* tiles, long n_tiles, const int* norm_tiles,
+                       long n_norm_tiles, const float* scales, float* workspace, int dtype, hipStream_t st) {
+    if (!FORMS && n_norm_tiles == 0)
+        return lora_launch<MODE_PLAIN, false>("lora_merge", targets, segments, max_rank, tiles, n_tiles, scales, nullptr, dtype, st);
+    if (n_norm_tiles > 0) {
+        const int rc = lora_launch<MODE_NORM, FORMS>("lora_merge (norm pass)", targets, segments, max_rank, norm_tiles, n_norm_tiles, scales,
+                                                     workspace, dtype, st);
+        if (rc) return rc;
+    }
+    return lora_launch<MODE_DORA, FORMS>("lora_merge", targets, segments, max_rank, tiles, n_tiles, scales, workspace, dtype, st);
 }
 
 }  // namespace
 
 extern "C" int st_lora_merge(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
-                             const int* tiles, long n_tiles, const float* scales, int n_scales, int dtype, void* stream) {
+                             const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
+                             float* workspace, size_t workspace_bytes, int dtype, int forms, void* stream) {
     ST_REQUIRE(targets && tiles && scales && (segments || n_segments == 0), "lora_merge: null pointer");
     ST_REQUIRE(n_targets > 0 && n_segments >= 0 && n_scales > 0, "lora_merge: bad sizes (targets %d, segments %d, scales %d)",
                n_targets, n_segments, n_scales);      // (a target without segments is restored to its base)
-    ST_REQUIRE(n_tiles > 0 && n_tiles <= 0x7fffffffL, "lora_merge: %ld tiles (a launch takes 1 .. 2^31 - 1)", n_tiles);
-    ST_REQUIRE((uintptr_t)targets % 8 == 0 && (uintptr_t)segments % 8 == 0 && (uintptr_t)tiles % 4 == 0 && (uintptr_t)scales % 4 == 0,
-               "lora_merge: misaligned table");
-    ST_REQUIRE(max_rank >= 0 && max_rank <= ST_LORA_MAX_RANK && (n_segments == 0 || max_rank > 0),
-               "lora_merge: max_rank %d (the largest padded rank of the segments, 1 .. %d)", max_rank, (int)ST_LORA_MAX_RANK);
-    return lora_launch<MODE_PLAIN>("lora_merge", targets, segments, max_rank, tiles, n_tiles, scales, nullptr, dtype, (hipStream_t)stream);
-}
-
-extern "C" int st_lora_merge_dora(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
-                                  const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
-                                  float* workspace, size_t workspace_bytes, int dtype, void* stream) {
-    ST_REQUIRE(targets && tiles && scales && segments, "lora_merge_dora: null pointer");
-    ST_REQUIRE(n_targets > 0 && n_segments > 0 && n_scales > 0, "lora_merge_dora: bad sizes (targets %d, segments %d, scales %d)",
-               n_targets, n_segments, n_scales);
     ST_REQUIRE(n_tiles > 0 && n_tiles <= 0x7fffffffL && n_norm_tiles >= 0 && n_norm_tiles <= n_tiles,
-               "lora_merge_dora: %ld tiles, %ld norm tiles (a launch takes 1 .. 2^31 - 1; the norm pass covers a subset of the targets)",
+               "lora_merge: %ld tiles, %ld norm tiles (a launch takes 1 .. 2^31 - 1; the norm pass covers a subset of the targets)",
                n_tiles, n_norm_tiles);
     ST_REQUIRE(n_norm_tiles == 0 || (norm_tiles && workspace && workspace_bytes >= 4),
-               "lora_merge_dora: the norm pass needs its tile list and a workspace");
+               "lora_merge: the norm pass needs its tile list and a workspace");
     ST_REQUIRE((uintptr_t)targets % 8 == 0 && (uintptr_t)segments % 8 == 0 && (uintptr_t)tiles % 4 == 0 && (uintptr_t)norm_tiles % 4 == 0 &&
-               (uintptr_t)scales % 4 == 0 && (uintptr_t)workspace % 4 == 0, "lora_merge_dora: misaligned table");
-    ST_REQUIRE(max_rank > 0 && max_rank <= ST_LORA_MAX_RANK,
-               "lora_merge_dora: max_rank %d (the largest padded rank of the segments, 1 .. %d)", max_rank, (int)ST_LORA_MAX_RANK);
-    ST_REQUIRE(dtype == ST_BF16 || dtype == ST_F16 || dtype == ST_F32, "lora_merge_dora: unsupported dtype %d", dtype);
+               (uintptr_t)scales % 4 == 0 && (uintptr_t)workspace % 4 == 0, "lora_merge: misaligned table");
+    // (0: no segment, or every segment is a Kronecker one - nothing is staged)
+    ST_REQUIRE(max_rank >= 0 && max_rank <= ST_LORA_MAX_RANK && (max_rank > 0 || n_segments == 0 || forms),
+               "lora_merge: max_rank %d (the largest padded rank of any factor pair, 1 .. %d; 0 when nothing is staged)", max_rank,
+               (int)ST_LORA_MAX_RANK);
+    ST_REQUIRE(dtype == ST_BF16 || dtype == ST_F16 || dtype == ST_F32, "lora_merge: unsupported dtype %d", dtype);
     hipStream_t st = (hipStream_t)stream;
-    if (n_norm_tiles > 0) {
-        const int rc = lora_launch<MODE_NORM>("lora_merge_dora (norm pass)", targets, segments, max_rank, norm_tiles, n_norm_tiles, scales,
-                                              workspace, dtype, st);
-        if (rc) return rc;
-    }
-    return lora_launch<MODE_DORA>("lora_merge_dora", targets, segments, max_rank, tiles, n_tiles, scales, workspace, dtype, st);
-}
-
-extern "C" int st_lora_merge_forms(const long long* targets, int n_targets, const long long* segments, int n_segments, int max_rank,
-                                   const int* tiles, long n_tiles, const int* norm_tiles, long n_norm_tiles, const float* scales, int n_scales,
-                                   float* workspace, size_t workspace_bytes, int dtype, void* stream) {
-    ST_REQUIRE(targets && tiles && scales && segments, "lora_merge_forms: null pointer");
-    ST_REQUIRE(n_targets > 0 && n_segments > 0 && n_scales > 0, "lora_merge_forms: bad sizes (targets %d, segments %d, scales %d)",
-               n_targets, n_segments, n_scales);
-    ST_REQUIRE(n_tiles > 0 && n_tiles <= 0x7fffffffL && n_norm_tiles >= 0 && n_norm_tiles <= n_tiles,
-               "lora_merge_forms: %ld tiles, %ld norm tiles (a launch takes 1 .. 2^31 - 1; the norm pass covers a subset of the targets)",
-               n_tiles, n_norm_tiles);
-    ST_REQUIRE(n_norm_tiles == 0 || (norm_tiles && workspace && workspace_bytes >= 4),
-               "lora_merge_forms: the norm pass needs its tile list and a workspace");
-    ST_REQUIRE((uintptr_t)targets % 8 == 0 && (uintptr_t)segments % 8 == 0 && (uintptr_t)tiles % 4 == 0 && (uintptr_t)norm_tiles % 4 == 0 &&
-               (uintptr_t)scales % 4 == 0 && (uintptr_t)workspace % 4 == 0, "lora_merge_forms: misaligned table");
-    ST_REQUIRE(max_rank >= 0 && max_rank <= ST_LORA_MAX_RANK,       // (0: every segment is a Kronecker one, nothing is staged)
-               "lora_merge_forms: max_rank %d (the largest padded rank of any factor pair, 0 .. %d)", max_rank, (int)ST_LORA_MAX_RANK);
-    ST_REQUIRE(dtype == ST_BF16 || dtype == ST_F16 || dtype == ST_F32, "lora_merge_forms: unsupported dtype %d", dtype);
-    hipStream_t st = (hipStream_t)stream;
-    if (n_norm_tiles > 0) {                                       // only when some segment has a magnitude
-        const int rc = lora_launch<MODE_NORM, true>("lora_merge_forms (norm pass)", targets, segments, max_rank, norm_tiles, n_norm_tiles,
-                                                    scales, workspace, dtype, st);
-        if (rc) return rc;
-    }
-    return lora_launch<MODE_DORA, true>("lora_merge_forms", targets, segments, max_rank, tiles, n_tiles, scales, workspace, dtype, st);
+    return forms ? lora_passes<true>(targets, segments, max_rank, tiles, n_tiles, norm_tiles, n_norm_tiles, scales, workspace, dtype, st)
+                 : lora_passes<false>(targets, segments, max_rank, tiles, n_tiles, norm_tiles, n_norm_tiles, scales, workspace, dtype, st);
 }

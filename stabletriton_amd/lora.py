@@ -399,11 +399,31 @@ def _padded_pair(up: torch.Tensor, down: torch.Tensor, like: torch.Tensor) -> Tu
     return up_p, down_t
 
 
-def build_factors(p: Placed, w: torch.Tensor, weight_shape, nhwc: bool) -> tuple:
+class Factor(NamedTuple):
+    """What the merge holds for one adapter on one weight (`build_factors`).  `kind` "plain": `tensors` (Up (N, rp), DownT (K, rp));
+    "hada" (LoHa): (Up1, DownT1, Up2, DownT2); "kron" (LoKr): the fp32 tables (W1, W2) with the weight's `taps` and `layout`
+    (`ops.lora_plan`).  Ranks are zero-padded; `magnitude` is the DoRA magnitude, (N,) fp32 on the weight's device, or None."""
+    kind: str
+    tensors: Tuple[torch.Tensor, ...]
+    taps: int = 1
+    layout: int = 0
+    magnitude: Optional[torch.Tensor] = None
+
+    def entry(self, slot: int) -> tuple:
+        """The factor tuple `ops.lora_plan` takes for this record in scale slot `slot`."""
+        mag = () if self.magnitude is None else (self.magnitude,)
+        if self.kind == "plain":
+            return (*self.tensors, slot, *mag)
+        if self.kind == "hada":
+            return ("hada", *self.tensors, slot, *mag)
+        return ("kron", *self.tensors, self.taps, self.layout, slot, *mag)
+
+
+def build_factors(p: Placed, w: torch.Tensor, weight_shape, nhwc: bool) -> Factor:
     """What the merge holds for one adapter on one weight, everything scale-independent done: `w` is the weight's (N, K) view,
-    `weight_shape` the parameter's own shape.  Returns (Up, DownT) for "lora" and "tucker", ("hada", Up1, DownT1, Up2, DownT2)
-    for "loha" and ("kron", W1, W2, taps, layout) for "lokr" (`ops.lora_plan` without the slot and the magnitude)."""
+    `weight_shape` the parameter's own shape.  "lora" and "tucker" give a "plain" Factor, "loha" a "hada" and "lokr" a "kron" one."""
     f32 = lambda t: t.detach().to(device=w.device, dtype=torch.float32)         # noqa: E731
+    mag = None if p.magnitude is None else f32(p.magnitude).reshape(-1).contiguous()
     conv = len(weight_shape) == 4
     taps = weight_shape[2] * weight_shape[3] if conv else 1
     if p.form in ("lora", "tucker"):
@@ -415,7 +435,7 @@ def build_factors(p: Placed, w: torch.Tensor, weight_shape, nhwc: bool) -> tuple
         elif conv:                                                           # the down factor in the K order of the weight's memory
             down = down[:, :, None, None] if down.dim() == 2 else down
             down = (down.permute(0, 2, 3, 1) if nhwc else down).reshape(r, -1)
-        return _padded_pair(up * (p.alpha / r), down, w)
+        return Factor("plain", _padded_pair(up * (p.alpha / r), down, w), magnitude=mag)
     parts = {k: f32(v) for k, v in p.parts.items()}
     if p.form == "loha":
         sigma = 1.0 if p.alpha is None else p.alpha / parts["hada_w1_b"].shape[0]
@@ -424,7 +444,7 @@ def build_factors(p: Placed, w: torch.Tensor, weight_shape, nhwc: bool) -> tuple
             wa, wb, t = parts[f"hada_w{m}_a"], parts[f"hada_w{m}_b"], parts.get(f"hada_t{m}")
             up, down = (wa.t(), contract_core(t, wb, nhwc)) if t is not None else (wa, _k_order(wb, weight_shape, nhwc))
             pairs += _padded_pair(up * sigma if m == "1" else up, down, w)
-        return ("hada", *pairs)
+        return Factor("hada", tuple(pairs), magnitude=mag)
     # LoKr
     rank = None
     if "lokr_w1" in parts:
@@ -443,21 +463,24 @@ def build_factors(p: Placed, w: torch.Tensor, weight_shape, nhwc: bool) -> tuple
     sigma = 1.0 if p.alpha is None or rank is None else p.alpha / rank
     layout = 1 if conv and nhwc else 0
     w2 = (w2.permute(0, 2, 3, 1) if layout else w2).reshape(c, -1)
-    return ("kron", (w1 * sigma).contiguous(), w2.contiguous(), taps, layout)
+    return Factor("kron", ((w1 * sigma).contiguous(), w2.contiguous()), taps, layout, mag)
 
 
-def factor_delta(f: tuple) -> torch.Tensor:
-    """The fp32 delta (N, K) of one factor tuple as the kernel forms it (torch, any device): a product, the elementwise product
-    of two products, or a Kronecker product in the column order of the tuple's layout."""
-    if f[0] == "hada":
-        return (f[1].float() @ f[2].float().t()) * (f[3].float() @ f[4].float().t())
-    if f[0] == "kron":
-        w1, w2, taps, layout = f[1:5]
-        if not layout:
+def factor_delta(f: Factor) -> torch.Tensor:
+    """The fp32 delta (N, K) of one factor as the kernel forms it (torch, any device): a product, the elementwise product
+    of two products, or a Kronecker product in the column order of the factor's layout."""
+    if f.kind == "kron":
+        w1, w2 = f.tensors
+        if not f.layout:
             return torch.kron(w1, w2)                                        # [i c + p, j (d taps) + col]
-        (a, b), c, d = w1.shape, w2.shape[0], w2.shape[1] // taps
-        return torch.einsum("ij,ptq->iptjq", w1, w2.reshape(c, taps, d)).reshape(a * c, taps * b * d)
-    return f[0].float() @ f[1].float().t()
+        (a, b), c, d = w1.shape, w2.shape[0], w2.shape[1] // f.taps
+        return torch.einsum("ij,ptq->iptjq", w1, w2.reshape(c, f.taps, d)).reshape(a * c, f.taps * b * d)
+    up, down_t = f.tensors[:2]
+    delta = up.float() @ down_t.float().t()
+    if f.kind == "hada":
+        up2, down2_t = f.tensors[2:]
+        delta = delta * (up2.float() @ down2_t.float().t())
+    return delta
 
 
 def target_linears(module: nn.Module) -> "OrderedDict[str, nn.Linear]":
@@ -493,9 +516,7 @@ def weight_rows(w: torch.Tensor) -> Tuple[torch.Tensor, bool]:
 class _Adapter:
     def __init__(self, slot: int, scale: float):
         self.slot, self.scale = slot, scale
-        # module -> (Up (N, rp), DownT (K, rp)[, magnitude (N,) fp32]), zero-padded ranks; ("hada", Up1, DownT1, Up2, DownT2[, magnitude])
-        # for LoHa; ("kron", W1, W2, taps, layout[, magnitude]) for LoKr (`build_factors`)
-        self.factors: Dict[str, tuple] = {}
+        self.factors: Dict[str, Factor] = {}      # module -> what `build_factors` made of the adapter's tensors for it
 
 
 class LoraSet:
@@ -576,8 +597,6 @@ class LoraSet:
             for mod, p in placed.items():
                 w, nhwc = weight_rows(targets[mod].weight.detach())
                 ad.factors[mod] = build_factors(p, w, tuple(targets[mod].weight.shape), nhwc)
-                if p.magnitude is not None:
-                    ad.factors[mod] += (p.magnitude.detach().to(device=w.device, dtype=torch.float32).reshape(-1).contiguous(),)
                 if mod not in self._base:
                     self._base[mod] = w.clone(memory_format=torch.contiguous_format)
         self._adapters[name] = ad
@@ -639,16 +658,11 @@ class LoraSet:
         return eff
 
     def _entries(self):
-        """Per snapshotted module: (parameter, its (N, K) view, base, [(Up, DownT, slot[, magnitude]), ...]) in load order (the
-        kernel's summation order); LoHa and LoKr tuples as `ops.lora_plan` takes them, the slot after their five leading items."""
+        """Per snapshotted module: (parameter, its (N, K) view, base, [(Factor, slot), ...]) in load order (the kernel's
+        summation order)."""
         out = []
         for mod, base in self._base.items():
-            facs = []
-            for a in self._adapters.values():
-                if mod in a.factors:
-                    f = a.factors[mod]
-                    lead = 5 if isinstance(f[0], str) else 2
-                    facs.append((*f[:lead], a.slot, *f[lead:]))
+            facs = [(a.factors[mod], a.slot) for a in self._adapters.values() if mod in a.factors]
             param = self.targets[mod].weight
             out.append((param, weight_rows(param.detach())[0], base, facs))
         return out
@@ -667,7 +681,7 @@ class LoraSet:
                 if self._scales is None:
                     self._scales = torch.zeros(MAX_ADAPTERS, dtype=torch.float32, device=w0.device)
                 if self._plan is None:
-                    self._plan = ops.lora_plan([(w, b, f) for _, w, b, f in entries])
+                    self._plan = ops.lora_plan([(w, b, [f.entry(slot) for f, slot in facs]) for _, w, b, facs in entries])
                 self._scales.copy_(torch.tensor(eff, dtype=torch.float32))
                 ops.lora_merge(self._plan, self._scales)
             else:
@@ -681,13 +695,8 @@ class LoraSet:
 
 def _merge_torch(w: torch.Tensor, base: torch.Tensor, facs, eff) -> None:
     """The kernel's formula in torch (CPU): fp32 products and sums, one rounding to the storage dtype, base bits when every
-    scale is zero.  `w` is the weight's (N, K) view; a factor tuple is (Up, DownT, slot[, magnitude]), ("hada", Up1, DownT1, Up2,
-    DownT2, slot[, magnitude]) or ("kron", W1, W2, taps, layout, slot[, magnitude]); `factor_delta` forms each one's delta."""
-    live = []
-    for f in facs:
-        at = 5 if isinstance(f[0], str) else 2                      # where the slot sits
-        if eff[f[at]] != 0.0:
-            live.append((f, eff[f[at]], f[at + 1] if len(f) > at + 1 else None))
+    scale is zero.  `w` is the weight's (N, K) view, `facs` its [(Factor, slot), ...]; `factor_delta` forms each one's delta."""
+    live = [(f, eff[slot], f.magnitude) for f, slot in facs if eff[slot] != 0.0]
     if not live:
         w.detach().copy_(base)
         return

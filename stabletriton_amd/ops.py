@@ -1466,19 +1466,18 @@ def lora_rank_multiple(dtype: torch.dtype) -> int:
 
 
 class LoraPlan:
-    """Descriptor table, segment table and flat tile list of one set of targets, on the device.  Built once per load / unload;
-    a scale change reuses it.  Holds every tensor the tables point at.  `dora`: some segment carries a magnitude; the plan then
-    has 6-word segment rows, the tile list of the norm pass and its workspace (st_lora_merge_dora).  `forms`: some segment is a
-    LoHa or LoKr one; the plan then has the wide rows of st_lora_merge_forms (and a norm pass only with `dora`)."""
+    """Descriptor table, segment table (LORA_FORM_WORDS int64 per row, None without a segment) and flat tile list of one set of
+    targets, on the device.  Built once per load / unload; a scale change reuses it.  Holds every tensor the tables point at.
+    `dora`: some segment carries a magnitude; the plan then has the tile list of the norm pass and its workspace.  `forms`: some
+    segment is a LoHa or LoKr one (or the caller asked for it): the merge runs the kernels that can form every kind."""
 
     def __init__(self, targets, segments, tiles, n_targets, n_segments, n_tiles, n_slots, max_rank, dtype, keep,
-                 norm_tiles=None, workspace=None, forms=False):
+                 norm_tiles=None, workspace=None, dora=False, forms=False):
         self.targets, self.segments, self.tiles = targets, segments, tiles
         self.n_targets, self.n_segments, self.n_tiles, self.n_slots, self.max_rank = n_targets, n_segments, n_tiles, n_slots, max_rank
         self.dtype, self.keep = dtype, keep
         self.norm_tiles, self.workspace = norm_tiles, workspace
-        self.dora = workspace is not None
-        self.forms = forms
+        self.dora, self.forms = dora, forms
 
 
 def _lora_tiles(counts, which) -> torch.Tensor:
@@ -1517,15 +1516,15 @@ def lora_plan(entries, forms: bool = False) -> LoraPlan:
                                                                          layout 0: K runs (channel, tap) and w2's columns (q, tap)
     Factor pairs are contiguous in the weight's dtype with rp a multiple of lora_rank_multiple(dtype) (zero padding);
     magnitude: None, or the DoRA magnitude of the segment, N fp32 values on the device (any shape).  A target with no factors
-    is restored to its base by the launch.  Plans without a "hada" / "kron" tuple keep the tables and entry points they had;
-    `forms=True` gives such a plan the wide rows too (the same bits through st_lora_merge_forms: what the tests compare)."""
+    is restored to its base by the launch.  A plan without a "hada" / "kron" tuple runs the lean kernels; `forms=True` sends
+    it through the ones that can form every kind (the same bits: what the tests compare)."""
     if not entries:
         raise BackendError("lora_plan: no targets")
     w0 = entries[0][0]
     dtype, device = w0.dtype, w0.device
     _C.dtype_code(dtype)
     mult = lora_rank_multiple(dtype)
-    trows, srows, wide, counts, keep, slots = [], [], [], [], [], 0
+    trows, srows, counts, keep, slots = [], [], [], [], 0
     ws_floats, norm_targets, forms, max_rank = 0, [], bool(forms), 0
     for w, base, factors in entries:
         _C.require_device(w, base)
@@ -1575,66 +1574,47 @@ def lora_plan(entries, forms: bool = False) -> LoraPlan:
             slot = int(slot)
             if any(r > LORA_MAX_RANK for r in ranks) or slot < 0:
                 raise BackendError(f"lora_plan: padded rank {max(ranks, default=0)} (at most {LORA_MAX_RANK}) / scale slot {slot}")
-            row = [body[0], body[1], body[2], slot, 0, 0]
+            mag_ptr = ws_at = 0
             if mag is not None:
                 _C.require_device(mag)
                 if mag.dtype != torch.float32 or mag.numel() != n or not mag.is_contiguous() or mag.device != device:
                     raise BackendError(f"lora_plan: the magnitude of a {(n, k)} weight must be {n} contiguous fp32 values on {device}; "
                                        f"got {tuple(mag.shape)} {mag.dtype}")
-                row[4:] = [mag.data_ptr(), ws_floats]
+                mag_ptr, ws_at = mag.data_ptr(), ws_floats
                 ws_floats += n * tiles_k
                 if not norm_targets or norm_targets[-1] != len(trows) - 1:
                     norm_targets.append(len(trows) - 1)
                 keep.append(mag)
-            srows.append(row)
-            wide.append([code, slot, row[4], row[5], *body])
+            srows.append([code, slot, mag_ptr, ws_at, *body])
             max_rank = max([max_rank, *ranks])
             slots = max(slots, slot + 1)
             keep += held
         counts.append(-(-n // _C.LORA_TILE_N) * tiles_k)
         keep += [w, base]
     tiles = _lora_tiles(counts, list(range(len(counts))))
-    args = (len(trows), len(srows), tiles.shape[0], slots, max_rank, dtype, keep)
-    targets = torch.tensor(trows, dtype=torch.int64).to(device)
-    dora = dict(norm_tiles=_lora_tiles(counts, norm_targets).to(device),
-                workspace=torch.empty(ws_floats, dtype=torch.float32, device=device)) if norm_targets else {}
-    if forms and srows:            # a LoHa or LoKr segment: the wide rows of st_lora_merge_forms
-        segments = torch.tensor(wide, dtype=torch.int64).reshape(-1, LORA_FORM_WORDS).to(device)
-        return LoraPlan(targets, segments, tiles.to(device), *args, forms=True, **dora)
-    if not norm_targets:           # no DoRA segment: the 4-word rows of st_lora_merge
-        segments = torch.tensor([r[:4] for r in srows], dtype=torch.int64).reshape(-1, 4).to(device) if srows else None
-        return LoraPlan(targets, segments, tiles.to(device), *args)
-    segments = torch.tensor(srows, dtype=torch.int64).reshape(-1, 6).to(device)
-    return LoraPlan(targets, segments, tiles.to(device), *args, **dora)
+    dora = bool(norm_targets)
+    return LoraPlan(torch.tensor(trows, dtype=torch.int64).to(device),
+                    torch.tensor(srows, dtype=torch.int64).reshape(-1, LORA_FORM_WORDS).to(device) if srows else None,
+                    tiles.to(device), len(trows), len(srows), tiles.shape[0], slots, max_rank, dtype, keep,
+                    norm_tiles=_lora_tiles(counts, norm_targets).to(device) if dora else None,
+                    workspace=torch.empty(ws_floats, dtype=torch.float32, device=device) if dora else None,
+                    dora=dora, forms=forms and bool(srows))
 
 
 def lora_merge(plan: LoraPlan, scales: torch.Tensor) -> None:
     """Rebuild every target of `plan` from its base: W = round(base + sum_j scales[slot_j] * up_j @ down_j), one launch; with
     DoRA segments in the plan W = round(base + sum_j (g_j V_j - base)), V_j = base + scales[slot_j] * up_j @ down_j and
-    g_j[n] = magnitude_j[n] / ||V_j[n]|| (1 for a plain segment), two launches (row norms, then the merge).  A plan with LoHa
-    or LoKr segments forms their deltas as `lora_plan` states them and is otherwise the same (st_lora_merge_forms).
+    g_j[n] = magnitude_j[n] / ||V_j[n]|| (1 for a plain segment), two launches (row norms, then the merge).  LoHa and LoKr
+    segments form their deltas as `lora_plan` states them and are otherwise the same.
     Writes through raw pointers: the caller bumps the version counters of the rewritten parameters."""
     _C.require_device(scales)
     if scales.dtype != torch.float32 or not scales.is_contiguous() or scales.numel() < max(plan.n_slots, 1) or scales.device != plan.targets.device:
         raise BackendError(f"lora_merge: scales must be a contiguous fp32 device table of at least {max(plan.n_slots, 1)} slots")
-    if plan.forms:
-        norm = plan.norm_tiles
-        _C.check(_C.load().st_lora_merge_forms(plan.targets.data_ptr(), plan.n_targets, plan.segments.data_ptr(), plan.n_segments, plan.max_rank,
-                                               plan.tiles.data_ptr(), plan.n_tiles, _ptr(norm), 0 if norm is None else norm.shape[0],
-                                               scales.data_ptr(), scales.numel(), _ptr(plan.workspace),
-                                               0 if plan.workspace is None else plan.workspace.numel() * 4,
-                                               _C.dtype_code(plan.dtype), _C.stream_ptr()), "lora_merge")
-        return
-    if plan.dora:
-        _C.check(_C.load().st_lora_merge_dora(plan.targets.data_ptr(), plan.n_targets, plan.segments.data_ptr(), plan.n_segments, plan.max_rank,
-                                              plan.tiles.data_ptr(), plan.n_tiles, plan.norm_tiles.data_ptr(), plan.norm_tiles.shape[0],
-                                              scales.data_ptr(), scales.numel(), plan.workspace.data_ptr(), plan.workspace.numel() * 4,
-                                              _C.dtype_code(plan.dtype), _C.stream_ptr()), "lora_merge")
-        return
+    norm, ws = plan.norm_tiles, plan.workspace
     _C.check(_C.load().st_lora_merge(plan.targets.data_ptr(), plan.n_targets, _ptr(plan.segments), plan.n_segments, plan.max_rank,
-                                     plan.tiles.data_ptr(),
-                                     plan.n_tiles, scales.data_ptr(), scales.numel(), _C.dtype_code(plan.dtype), _C.stream_ptr()),
-             "lora_merge")
+                                     plan.tiles.data_ptr(), plan.n_tiles, _ptr(norm), 0 if norm is None else norm.shape[0],
+                                     scales.data_ptr(), scales.numel(), _ptr(ws), 0 if ws is None else ws.numel() * 4,
+                                     _C.dtype_code(plan.dtype), int(plan.forms), _C.stream_ptr()), "lora_merge")
 
 
 # ----------------------------------------------------------------------------- FreeU

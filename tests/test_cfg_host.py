@@ -21,7 +21,7 @@ def _cfg(lib, **kw):
 
 
 def test_cfg_step_entry_point_validates_on_host(lib):
-    assert lib.st_abi_version() == _C.ABI_VERSION == 17
+    assert lib.st_abi_version() == _C.ABI_VERSION == 18
     for name in ("latent", "eps", "next_in", "dsigma", "in_scale", "guidance", "step"):
         assert _cfg(lib, **{name: None}) != 0 and b"null" in lib.st_last_error(), name
     assert _cfg(lib, per_sample=1020) != 0 and b"multiple of 8" in lib.st_last_error()

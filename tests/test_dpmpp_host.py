@@ -124,7 +124,7 @@ def _dpm(lib, **kw):
 
 
 def test_dpmpp_step_entry_point_validates_on_host(lib):
-    assert lib.st_abi_version() == _C.ABI_VERSION == 17
+    assert lib.st_abi_version() == _C.ABI_VERSION == 18
     assert "st_dpmpp2m_step" in _C.SIGNATURES
     for name in ("latent", "eps", "next_in", "history", "coef", "in_scale", "step", "start"):
         assert _dpm(lib, **{name: None}) != 0 and b"null" in lib.st_last_error(), name

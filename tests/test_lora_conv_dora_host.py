@@ -267,19 +267,21 @@ def test_conv_targets_are_opt_in_and_dora_on_linears_applies_by_default():
 
 # ------------------------------------------------------------------------------------------------ the library
 def test_library_exports_the_dora_merge(lib):
-    assert lib.st_abi_version() == 17 == _C.ABI_VERSION
-    assert hasattr(lib, "st_lora_merge_dora") and "st_lora_merge_dora" in _C.SIGNATURES
+    """The DoRA merge is st_lora_merge with a norm pass: its own entry point is gone."""
+    assert lib.st_abi_version() == 18 == _C.ABI_VERSION
+    assert hasattr(lib, "st_lora_merge") and "st_lora_merge" in _C.SIGNATURES
+    assert not hasattr(lib, "st_lora_merge_dora") and "st_lora_merge_dora" not in _C.SIGNATURES
     header = open(os.path.join(ROOT, "include", "stabletriton_amd.h")).read()
-    assert re.search(r"\bint st_lora_merge_dora\(", header)
+    assert re.search(r"\bint st_lora_merge\(", header) and not re.search(r"\bint st_lora_merge_dora\(", header)
     out = subprocess.run(["nm", "-D", "--defined-only", lib_path()], capture_output=True, text=True).stdout
-    assert re.search(r" T st_lora_merge_dora\b", out) and re.search(r" T st_lora_merge\b", out)
+    assert re.search(r" T st_lora_merge\b", out) and not re.search(r" T st_lora_merge_dora\b", out)
     # argument validation happens on the host, before any launch
     bf = _C.ST_BF16
-    assert lib.st_lora_merge_dora(None, 1, None, 1, 32, None, 1, None, 0, None, 8, None, 0, bf, None) != 0 and b"null" in lib.st_last_error()
-    assert lib.st_lora_merge_dora(8, 1, 8, 1, 32, 8, 1, 8, 2, 8, 8, 8, 64, bf, None) != 0 and b"norm tiles" in lib.st_last_error()
-    assert lib.st_lora_merge_dora(8, 1, 8, 1, 32, 8, 1, 8, 1, 8, 8, None, 0, bf, None) != 0 and b"workspace" in lib.st_last_error()
-    assert lib.st_lora_merge_dora(8, 1, 8, 1, 256, 8, 1, 8, 1, 8, 8, 8, 64, bf, None) != 0 and b"max_rank" in lib.st_last_error()
-    assert lib.st_lora_merge_dora(8, 1, 8, 1, 32, 8, 1, 8, 1, 8, 8, 8, 64, 7, None) != 0 and b"dtype" in lib.st_last_error()
+    assert lib.st_lora_merge(None, 1, None, 1, 32, None, 1, None, 0, None, 8, None, 0, bf, 0, None) != 0 and b"null" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 1, 8, 2, 8, 8, 8, 64, bf, 0, None) != 0 and b"norm tiles" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 1, 8, 1, 8, 8, None, 0, bf, 0, None) != 0 and b"workspace" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 256, 8, 1, 8, 1, 8, 8, 8, 64, bf, 0, None) != 0 and b"max_rank" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 1, 8, 1, 8, 8, 8, 64, 7, 0, None) != 0 and b"dtype" in lib.st_last_error()
 
 
 def test_zero_row_takes_gain_zero():

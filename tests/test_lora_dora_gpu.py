@@ -1,4 +1,4 @@
-"""The DoRA form of the grouped merge (st_lora_merge_dora through ops.lora_plan / ops.lora_merge) against float64:
+"""The DoRA form of the grouped merge (st_lora_merge with a norm pass, through ops.lora_plan / ops.lora_merge) against float64:
 
     V_j = B + s_j Up_j Down_j,   g_j[n] = m_j[n] / ||V_j[n]||  (1 for a plain segment),   W64 = B + sum_j (g_j V_j - B).
 
@@ -134,7 +134,7 @@ def test_dora_merge_vs_float64(gpu, dtype):
     for c in _cases_of(dtype, gpu):
         what = f"{dtype} {c.shape}"
         plan = ops.lora_plan([c.entry()])
-        assert plan.dora
+        assert plan.dora and plan.segments.shape[1] == ops.LORA_FORM_WORDS
         c.w.fill_(-3.0)
         ops.lora_merge(plan, table)
         torch.cuda.synchronize()
@@ -208,6 +208,7 @@ def test_plan_without_a_magnitude_is_the_plain_merge(gpu, dtype):
         c.w.fill_(9.0)
     plan = ops.lora_plan([(w, b, [(u, d, s, None) for u, d, s in f]) for w, b, f in entries])
     assert not plan.dora and not parent_form.dora and plan.segments.shape == parent_form.segments.shape
+    assert plan.segments.shape[1] == ops.LORA_FORM_WORDS
     ops.lora_merge(plan, table)
     for c, g in zip(cases, want):
         assert _same_bits(c.w, g), f"{dtype} {c.shape}"

@@ -1,4 +1,4 @@
-"""The LoHa and LoKr segment kinds of the grouped merge (st_lora_merge_forms through ops.lora_plan / ops.lora_merge) against
+"""The LoHa and LoKr segment kinds of the grouped merge (st_lora_merge with `forms` set, through ops.lora_plan / ops.lora_merge) against
 float64 restatements written here.  Per segment, from the tables the kernel reads (factor pairs rounded to the dtype, LoKr's
 two fp32 tables):
 
@@ -19,13 +19,14 @@ With DoRA magnitudes the bound is test_lora_dora_gpu.py's, c_j standing where it
 
 No element is left out.  Three adapters on one weight: plain rank 16, LoHa ranks 8 and 24, LoKr with w2 = a rank-8 product,
 at scales 0.75 / -1.5 / 0.3 in slots 5 / 0 / 2.  Shapes are the smallest that take each path (SHAPES).  Also the bit
-identities that tie the new entry point to the two existing ones, guard margins, and refused tables.
+identities that tie the kernels that form every kind to the lean ones, the lean kernels' skip of a row they cannot form, guard
+margins, and refused tables.
 
 Worst |W - W64| / bound measured on an MI355X: see DESIGN.md section 4 (the adapter forms)."""
 import pytest
 import torch
 
-from stabletriton_amd import ops
+from stabletriton_amd import _C, ops
 
 pytestmark = pytest.mark.gpu
 
@@ -201,7 +202,7 @@ def test_forms_merge_vs_float64(gpu, dtype, dora):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_plain_tables_through_the_new_entry_point_keep_their_bits(gpu, dtype):
-    """Plain segments in the wide rows give st_lora_merge's bits, and st_lora_merge_dora's with magnitudes."""
+    """Plain segments through the kernels that form every kind (`forms`) give the lean kernels' bits, with and without magnitudes."""
     table = _table(gpu)
     for c in _cases_of(dtype, gpu):
         for dora in (False, True):
@@ -215,6 +216,36 @@ def test_plain_tables_through_the_new_entry_point_keep_their_bits(gpu, dtype):
             assert new.forms and new.dora == dora
             ops.lora_merge(new, table)
             assert _same_bits(c.w, want), f"{c.what} dora={dora}"
+            assert _margins_intact(c.buf, 7.0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_lean_kernels_skip_a_row_that_is_not_plain(gpu, dtype):
+    """st_lora_merge with forms = 0 over a table that holds a HADA row: the lean kernels drop the row and give the bits of the plan
+    that holds the plain segment alone, without and with a magnitude on it.  HADA only: the row's first pair is a valid plain
+    factor pair, so a missing guard shows as wrong bits (the product of that pair is added), never as a read out of bounds."""
+    table = _table(gpu)
+    lib = _C.load()
+    for c in _cases_of(dtype, gpu):
+        if c.shape not in ((50, 77), (72, 328)):
+            continue
+        for dora in (False, True):
+            ops.lora_merge(ops.lora_plan([c.entry(dora, only=[0])]), table)
+            want = c.w.clone()
+            plan = ops.lora_plan([(c.w, c.base, [c.entry(dora, only=[0])[2][0], c.entry(only=[1])[2][0]])])
+            assert plan.forms and plan.dora == dora and plan.n_segments == 2
+            ops.lora_merge(plan, table)
+            assert not _same_bits(c.w, want), f"{c.what} dora={dora}: the HADA row is live when the table's flag is right"
+            c.w.fill_(9.0)
+            norm, ws = plan.norm_tiles, plan.workspace
+            rc = lib.st_lora_merge(plan.targets.data_ptr(), plan.n_targets, plan.segments.data_ptr(), plan.n_segments, plan.max_rank,
+                                   plan.tiles.data_ptr(), plan.n_tiles, None if norm is None else norm.data_ptr(),
+                                   0 if norm is None else norm.shape[0], table.data_ptr(), table.numel(),
+                                   None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel() * 4,
+                                   _C.dtype_code(dtype), 0, _C.stream_ptr())
+            assert rc == 0, lib.st_last_error()
+            torch.cuda.synchronize()
+            assert _same_bits(c.w, want), f"{c.what} dora={dora}: forms = 0 must drop the HADA row and nothing else"
             assert _margins_intact(c.buf, 7.0)
 
 

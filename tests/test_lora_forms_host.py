@@ -7,12 +7,17 @@ elementwise product, the scale's fma and the final sums - under 80 fp32 rounding
 A = |B| + sum_j |s_j| |D_j| up to the cancellation inside a dot product, for which a factor 4 is allowed over the weight's
 largest A: |W - W64| <= 320 u max(A) (2e-5 max(A)), times the largest DoRA gain, plus the gain's own relative error
 (K / 2 + 80) u |W64| with magnitudes."""
+import os
+import re
+import subprocess
+
 import pytest
 import torch
 from torch import nn
 
 import lora_forms_util as lf
 from stabletriton_amd import _C, lora
+from stabletriton_amd.build import lib_path
 
 U = 2.0 ** -24
 # the (N, K) views of test_lora_forms_gpu.py as modules: name -> (module, LoKr (a, b))
@@ -221,6 +226,12 @@ def test_mixed_kinds_stack_in_load_order():
 
 
 def test_library_exports_the_forms_entry_point():
+    """LoHa and LoKr segments go through st_lora_merge with `forms` set: their own entry point is gone."""
     lib = _C.load()
-    assert hasattr(lib, "st_lora_merge_forms") and "st_lora_merge_forms" in _C.SIGNATURES
-    assert lib.st_abi_version() == 17 == _C.ABI_VERSION
+    assert hasattr(lib, "st_lora_merge") and "st_lora_merge" in _C.SIGNATURES
+    assert not hasattr(lib, "st_lora_merge_forms") and "st_lora_merge_forms" not in _C.SIGNATURES
+    assert lib.st_abi_version() == 18 == _C.ABI_VERSION
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "stabletriton_amd.h")).read()
+    assert re.search(r"\bint st_lora_merge\(", header) and not re.search(r"\bint st_lora_merge_forms\(", header)
+    out = subprocess.run(["nm", "-D", "--defined-only", lib_path()], capture_output=True, text=True).stdout
+    assert re.search(r" T st_lora_merge\b", out) and not re.search(r" T st_lora_merge_forms\b", out)

@@ -292,7 +292,7 @@ def test_global_scale_multiplies_every_adapter():
 
 # ------------------------------------------------------------------------------------------------ the library
 def test_library_exports_lora_merge(lib):
-    assert lib.st_abi_version() == 17 == _C.ABI_VERSION
+    assert lib.st_abi_version() == 18 == _C.ABI_VERSION
     assert hasattr(lib, "st_lora_merge") and "st_lora_merge" in _C.SIGNATURES
     header = open(os.path.join(ROOT, "include", "stabletriton_amd.h")).read()
     assert re.search(r"\bint st_lora_merge\(", header)
@@ -300,7 +300,8 @@ def test_library_exports_lora_merge(lib):
     out = subprocess.run(["nm", "-D", "--defined-only", lib_path()], capture_output=True, text=True).stdout
     assert re.search(r" T st_lora_merge\b", out)
     # argument validation happens on the host, before any launch
-    assert lib.st_lora_merge(None, 1, None, 0, 0, None, 1, None, 8, _C.ST_BF16, None) != 0 and b"null" in lib.st_last_error()
-    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 0, 8, 8, _C.ST_BF16, None) != 0 and b"tiles" in lib.st_last_error()
-    assert lib.st_lora_merge(8, 1, 8, 1, 256, 8, 1, 8, 8, _C.ST_BF16, None) != 0 and b"max_rank" in lib.st_last_error()
-    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 1, 8, 8, 7, None) != 0 and b"dtype" in lib.st_last_error()
+    # (targets, n, segments, n, max_rank, tiles, n, norm tiles, n, scales, n, workspace, bytes, dtype, forms, stream)
+    assert lib.st_lora_merge(None, 1, None, 0, 0, None, 1, None, 0, None, 8, None, 0, _C.ST_BF16, 0, None) != 0 and b"null" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 0, None, 0, 8, 8, None, 0, _C.ST_BF16, 0, None) != 0 and b"tiles" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 256, 8, 1, None, 0, 8, 8, None, 0, _C.ST_BF16, 0, None) != 0 and b"max_rank" in lib.st_last_error()
+    assert lib.st_lora_merge(8, 1, 8, 1, 32, 8, 1, None, 0, 8, 8, None, 0, 7, 0, None) != 0 and b"dtype" in lib.st_last_error()

@@ -232,7 +232,7 @@ P = 1 << 20            # fake, aligned, never dereferenced device addresses: val
 
 def test_entry_points_validate_on_the_host(lib):
     from stabletriton_amd import _C
-    assert lib.st_abi_version() == _C.ABI_VERSION == 17, "new entry points, no bump"
+    assert lib.st_abi_version() == _C.ABI_VERSION == 18
 
     def euler(**kw):
         a = dict(latent=P, eps=P, next_in=P, dsigma=P, in_scale=P, guidance=P, rescale=None, pag=P, step=P, batch=1, per_sample=1024,

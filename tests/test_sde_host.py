@@ -176,7 +176,7 @@ def _sde(lib, **kw):
 
 
 def test_sde_step_entry_point_validates_on_host(lib):
-    assert lib.st_abi_version() == _C.ABI_VERSION == 17
+    assert lib.st_abi_version() == _C.ABI_VERSION == 18
     assert "st_sde_step" in _C.SIGNATURES and "st_philox_normal" in _C.SIGNATURES
     for name in ("latent", "eps", "next_in", "history", "coef", "in_scale", "step", "start", "seeds"):
         assert _sde(lib, **{name: None}) != 0 and b"null" in lib.st_last_error(), name

@@ -117,8 +117,8 @@ def main():
             traffic = 2 * weight_bytes + norm_read
             ad = ls._adapters["probe"]
             no_torch = args.dora or args.form != "lora"           # (no do-it-yourself route to compare with: both figures are null)
-            old_way = [] if no_torch else [(lora.weight_rows(ls.targets[n].weight)[0], ls._base[n], ad.factors[n][0],
-                                            ad.factors[n][1].t().contiguous()) for n in mods]
+            old_way = [] if no_torch else [(lora.weight_rows(ls.targets[n].weight)[0], ls._base[n], ad.factors[n].tensors[0],
+                                            ad.factors[n].tensors[1].t().contiguous()) for n in mods]
 
             def torch_merge(s):
                 for w, base, up, down in old_way:
