@@ -58,7 +58,7 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
                                               st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
                                               st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then a DoRA and a LoHa / LoKr entry point beside
-                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed;
+                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed (st_attention_regions, after 18, likewise);
                                               18: st_lora_merge takes one ST_LORA_FORM_WORDS segment row, the norm pass's tables and `forms`, and is
                                               the only LoRA entry point again: the two beside it are removed) */
 const char* st_last_error(void);           /* host string, thread-local     */
@@ -438,6 +438,24 @@ int st_freeu(const void* h, const void* skip, void* h_out, void* skip_out, int N
  * writes the rows of its sub-batch, the copy the rows of the tail, bit-equal to st_split_f32 of the copied values. */
 int st_attention_pag(const void* q, const void* k, const void* v, void* out, int B, int T, int S, int H, int D,
                      long ldq, long ldk, long ldv, long ldo, float scale, int dtype, int ident_count, void* stream);
+
+/* ---- regional prompts (no reference counterpart: ComfyUI's conditioning masks / "attention couple", the diffusers community
+ * regional-prompting pipeline): cross-attention over R key/value segments, each with its own softmax, combined per query row.
+ *
+ * st_attention_regions: q (B, T, H*D); k, v (B, R*seg_len, H*D), segment r = keys [r*seg_len, (r+1)*seg_len); weights (B, R, T)
+ * fp32, dense;
+ *   out[b,t,h,:] = sum_r weights[b,r,t] * softmax_s(scale * q[b,t,h] . k[b, r*seg_len+s, h]) v[b, r*seg_len+s, h]   (s in segment r).
+ * Every segment has its own running maximum and row sum; the weighted sum is formed in fp32 from the un-rounded normalised segment
+ * results and rounded to the storage type once.  The weights are not normalised here: any finite values are legal, and a segment
+ * whose weight is 0 for a row contributes exactly 0 (its k / v must be finite).  With weights 1 on one segment and 0 on the others
+ * the result is bit-identical to st_attention on that segment's slice of k and v.
+ * dtype ST_BF16 or ST_F16, D = 64, 1 <= R <= 8, 1 <= seg_len < 256 (the range in which st_attention takes its text-context kernel);
+ * ld* are token strides in elements, batch strides T*ldq, R*seg_len*ldk, R*seg_len*ldv, T*ldo; alignment as st_attention (q, k, v,
+ * out 16-byte aligned; ldq, ldk, ldv multiples of 8, ldo of 4).  One launch, the text-context launch's grid; no atomics, nothing
+ * written outside out; never emits a split image (csrc/attention_regions.hip). */
+int st_attention_regions(const void* q, const void* k, const void* v, const float* weights, void* out,
+                         int B, int T, int R, int seg_len, int H, int D,
+                         long ldq, long ldk, long ldv, long ldo, float scale, int dtype, void* stream);
 
 /* The three updates with a third noise prediction: st_cfg_euler_step, st_dpmpp2m_step and st_sde_step with one more device table
  * `pag` of n_steps floats (never NULL) and one more row block of eps / next_in, the prediction under perturbed self-attention.

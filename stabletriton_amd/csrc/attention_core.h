@@ -117,11 +117,14 @@ __device__ __forceinline__ float att_max3(float a, float b, float c) { return fm
 // attention can run it as its epilogue on the Q tile it has just left in LDS (gemm.hip, st_ln_linear_xattn).
 //   Qb / Ob: row 0 of this block's NW*16 queries / outputs of ONE head (global or LDS for Qb); rows >= q_rows are clamped,
 //   rows >= o_rows not stored; Kb / Vb: key 0 of that head; lds: 3 * 16 KiB ring, 16-byte aligned.
-template <typename E, int NW>
-__device__ __forceinline__ void attn16_core(const E* Qb, long ldq, int q_rows, const E* Kb, const E* Vb, long ldk, long ldv,
-                                            int S, E* Ob, long ldo, int o_rows, float scale_log2e, char* lds, int wave, int lane) {
+// attn16_core_run is that body with the output left to the caller: `emit(o, inv, row, g)` receives the lane's un-normalised
+// O^T registers (d = 16 db + 4 g + e of query `row` of the block), and inv = 1 / row sum; attn16_core, below it, stores
+// (E)(o * inv).  The regional kernel (attention_regions.hip) runs the body once per key segment and keeps the fp32 result.
+// The body ends on s_waitcnt vmcnt(0) WITHOUT a barrier: a caller that runs it again on the same ring puts one in between.
+template <typename E, int NW, typename EMIT>
+__device__ __forceinline__ void attn16_core_run(const E* Qb, long ldq, int q_rows, const E* Kb, const E* Vb, long ldk, long ldv,
+                                                int S, float scale_log2e, char* lds, int wave, int lane, EMIT&& emit) {
     typedef typename V16<E>::x8 E8;
-    typedef typename V16<E>::x4 E4;
     constexpr int TILE_B = ATT_KV * 128;
     constexpr int BUF_B = 2 * TILE_B;
     constexpr int PIECES = 16 / NW;
@@ -281,15 +284,25 @@ __device__ __forceinline__ void attn16_core(const E* Qb, long ldq, int q_rows, c
     // row sum: row 0 of the extra block lives in register 0 of the lanes with g == 0
     const float l = __shfl(o[4][0], c16, 64);
     const float inv = 1.0f / l;
-    if (q0 + c16 < o_rows) {
-        E* orow = Ob + (size_t)(q0 + c16) * ldo;
+    emit(o, inv, q0 + c16, g);
+}
+
+template <typename E, int NW>
+__device__ __forceinline__ void attn16_core(const E* Qb, long ldq, int q_rows, const E* Kb, const E* Vb, long ldk, long ldv,
+                                            int S, E* Ob, long ldo, int o_rows, float scale_log2e, char* lds, int wave, int lane) {
+    typedef typename V16<E>::x4 E4;
+    attn16_core_run<E, NW>(Qb, ldq, q_rows, Kb, Vb, ldk, ldv, S, scale_log2e, lds, wave, lane,
+                           [&](const f32x4 (&o)[5], float inv, int row, int g) {
+        if (row < o_rows) {
+            E* orow = Ob + (size_t)row * ldo;
 #pragma unroll
-        for (int db = 0; db < 4; ++db) {
-            E4 a_;
+            for (int db = 0; db < 4; ++db) {
+                E4 a_;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) a_[e] = (E)(o[db][e] * inv);
-            *reinterpret_cast<E4*>(orow + 16 * db + 4 * g) = a_;
+                for (int e = 0; e < 4; ++e) a_[e] = (E)(o[db][e] * inv);
+                *reinterpret_cast<E4*>(orow + 16 * db + 4 * g) = a_;
+            }
         }
-    }
+    });
 }
 

@@ -53,6 +53,8 @@ class _HoistedUNet(nn.Module):
         self._new_prompt = False                  # set when a context was (re)projected: the fp8 plan measures its scales again
         self._last_t = None                       # fp8 plan only: the last call's (largest) timestep, to tell where a trajectory starts
         self._pag_chunks = 0                      # enable_pag: the last B // chunks rows of a call are perturbed (0: none)
+        self._regions = None                      # set_regions: (masks, chunks), applied to the buffers of a call's (rows, latent size)
+        self._regions_applied = {}                # ... rows -> the latent size the buffers of that row count were last written for
 
     def refresh_weights(self) -> int:
         """Re-derive fused / folded weight buffers after an in-place weight update (also done at every new prompt).
@@ -115,6 +117,49 @@ class _HoistedUNet(nn.Module):
         import contextlib
         state = getattr(self.compiled, "pag", None)
         return state.using(chunks) if state is not None else contextlib.nullcontext()
+
+    # ---- regional prompts (regions.py): weight buffers the cross-attention sites read by address; the captured graphs stay ----
+    def set_regions(self, masks: torch.Tensor, chunks: int = 2) -> None:
+        """Region masks, (R, lh, lw) or (batch, R, lh, lw) at latent resolution, for every following call whose
+        `encoder_hidden_states` is the R prompts concatenated along the token axis.  `chunks` says how a call's batch divides,
+        as in `enable_pag`: 2 = [uncond | cond], 3 = [uncond | cond | cond (perturbed)] - the first block is the negative one and
+        keeps segment 0, the others take the masks; 1 = every row takes them (a call without a negative block).  The buffers of a
+        batch size and latent size are allocated at the first call that has them, and written in place; a call whose latent is
+        not the masks' size raises.  Raises on a wrapper compiled without `regions=R`."""
+        from . import regions
+        st = regions.state_of(self.compiled, "set_regions")
+        regions.positive_rows(chunks, chunks)                    # (validates chunks)
+        masks = torch.as_tensor(masks)
+        regions._as_batched(masks, st.R, "set_regions")          # (validates the masks now, not at the next call)
+        self._regions = (masks, chunks)
+        self._regions_applied = {}
+
+    def clear_regions(self) -> None:
+        """Back to "off": every row takes segment 0 alone, the bits of a wrapper compiled without `regions` on the first prompt."""
+        from . import regions
+        regions.state_of(self.compiled, "clear_regions").clear()
+        self._regions = None
+        self._regions_applied = {}
+
+    def _apply_regions(self, sample: torch.Tensor) -> None:
+        """Bind the buffers of this call's batch and latent size and, when masks are set, write them for this geometry.  Buffers
+        are found by (rows, queries), so two latent shapes with the same row count can share one (128 x 64 and 64 x 128): the
+        weights are written again whenever the geometry of a row count changes, and masks of another size than the call's
+        latent raise.  Without masks nothing is written: new buffers are "off", and another owner's setting is left alone."""
+        from . import regions
+        state = getattr(self.compiled, "regions", None)
+        if not isinstance(state, regions.Regions) or torch.cuda.is_current_stream_capturing():
+            return
+        rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
+        state.bind(rows, hw, sample.device)
+        if self._regions is None or self._regions_applied.get(rows) == hw:
+            return
+        masks, chunks = self._regions
+        if tuple(masks.shape[-2:]) != hw:
+            raise ValueError(f"set_regions: the masks are {tuple(masks.shape[-2:])}, this call's latent is {hw}: masks are given at "
+                             "latent resolution")
+        state.set(masks, regions.positive_rows(rows, chunks), rows)
+        self._regions_applied[rows] = hw
 
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
@@ -185,6 +230,7 @@ class _HoistedUNet(nn.Module):
         # (.to() is the identity when the caller already computes in this dtype: an fp16 pipeline over an fp16 module)
         io_dtype = sample.dtype
         dev = sample.device
+        self._apply_regions(sample)
         self._context_for(ehs)
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor(float(timesteps), dtype=torch.float32)
@@ -248,27 +294,32 @@ class DiffusersUNet(_HoistedUNet):
 
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
-                                 cuda_graph: bool = True, freeu: bool = False, pag_layers=None) -> DiffusersUNet:
+                                 cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
+                                 region_tokens: int = 77) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
     `pag_layers=("mid",)` compiles the perturbed-attention sites in (diffusers' `pag_applied_layers`): `enable_pag(chunks)` /
-    `disable_pag()` then say which rows of a call are the perturbed ones."""
+    `disable_pag()` then say which rows of a call are the perturbed ones.
+    `regions=R` compiles regional cross-attention in (regions.py): the pipeline passes R prompts of `region_tokens` tokens
+    concatenated along the token axis as `encoder_hidden_states`; `set_regions(masks, chunks)` / `clear_regions()` drive it."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
         model = UNet2DConditionModel(spec)
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
-    compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers)
+    compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
-def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None):
+def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
+                        regions=None, region_tokens: int = 77):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
-    pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers)
+    pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
+                                             regions=regions, region_tokens=region_tokens)
     return pipe
 
 
@@ -288,17 +339,22 @@ class ComfyUNet(_HoistedUNet):
         return self._run(x, timesteps, context, y.to(self.compute_dtype))
 
 
-def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None) -> ComfyUNet:
+def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
+                       region_tokens: int = 77) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
-    perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`."""
+    perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
+    with regional cross-attention (conditioning masks / "attention couple"): `context` is the R conditionings concatenated along
+    the token axis, `set_regions(masks, chunks)` / `clear_regions()` drive it."""
     dtype = next(unet.parameters()).dtype
-    compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers)
+    compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
+                              region_tokens=region_tokens)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
-def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None) -> ComfyUNet:
+def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
+                      regions=None, region_tokens: int = 77) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens)
     model_patcher.model.diffusion_model = adapter
     return adapter

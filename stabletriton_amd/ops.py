@@ -1032,6 +1032,60 @@ def attention_pag(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: 
     return out
 
 
+REGIONS_MAX = 8               # st_attention_regions: segments per launch
+
+
+def attention_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights: torch.Tensor, num_heads: int, scale: float,
+                      seg_len: int) -> torch.Tensor:
+    """Cross-attention over R key/value segments of `seg_len` keys (k, v: (B, R*seg_len, H*D)), each with its own softmax, combined
+    per query row with the fp32 `weights` (B, R, T) - regional prompts (regions.py, csrc/attention_regions.hip):
+        out[b,t,h] = sum_r weights[b,r,t] * softmax(scale * q[b,t,h] k[b, segment r, h]^T) v[b, segment r, h]
+    in fp32 from the un-rounded segment results, rounded once.  bf16 / fp16 at head size 64 is ONE launch; fp32 (strict mode) and
+    head sizes 16 / 32 / 128 take the slow path: R `attention` launches on the segment slices and a torch fp32 weighted sum of
+    their (rounded) results - elementwise torch ops, legal inside a capture; that result carries no split image, the consuming
+    projection splits it itself.  One-hot weights give the bits of `attention` on that segment on both paths."""
+    _C.require_device(q, k, v, weights)
+    lib = _C.load()
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise BackendError("attention_regions expects (B, T, H*D) tensors")
+    B, T, Cc = q.shape
+    seg_len = int(seg_len)
+    if weights.dim() != 3 or weights.shape[0] != B or weights.shape[2] != T or weights.dtype != torch.float32:
+        raise BackendError(f"attention_regions: weights must be float32 (B, R, T) = ({B}, R, {T}) for q {tuple(q.shape)}, got "
+                           f"{tuple(weights.shape)} {weights.dtype}")
+    R = weights.shape[1]
+    if seg_len < 1 or R < 1 or k.shape[1] != R * seg_len or k.shape != v.shape or k.shape[0] != B or k.shape[2] != Cc:
+        raise BackendError(f"attention_regions: k / v must be (B, R*seg_len, H*D) = ({B}, {R}*{seg_len}, {Cc}), got k {tuple(k.shape)}, "
+                           f"v {tuple(v.shape)} with weights {tuple(weights.shape)}")
+    if k.dtype != q.dtype or v.dtype != q.dtype:
+        raise BackendError(f"attention_regions: q, k and v must share a dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+    D = Cc // num_heads
+    if q.dtype == torch.float32 or D != 64:
+        # the documented slow path: every segment through the ordinary attention launch, then the weighted sum in fp32
+        acc = None
+        for r in range(R):
+            a = attention(q, k[:, r * seg_len:(r + 1) * seg_len], v[:, r * seg_len:(r + 1) * seg_len], num_heads, scale)
+            term = a.float() * weights[:, r].unsqueeze(-1)
+            acc = term if acc is None else acc + term
+        return acc.to(q.dtype)
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    q_, ldq = tok(q)
+    k_, ldk = tok(k)
+    v_, ldv = tok(v)
+    w_ = weights.contiguous()
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    _C.check(lib.st_attention_regions(q_.data_ptr(), k_.data_ptr(), v_.data_ptr(), w_.data_ptr(), out.data_ptr(), B, T, R, seg_len,
+                                      num_heads, D, ldq, ldk, ldv, Cc, float(scale), _C.dtype_code(q.dtype), _C.stream_ptr()),
+             "attention_regions")
+    return out
+
+
 # ----------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int, *,
            upsample2x: bool = False, rowbias: Optional[torch.Tensor] = None,

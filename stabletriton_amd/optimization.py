@@ -18,13 +18,13 @@ from torch import fx, nn
 from . import _C, ops
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_pag, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_pag, insert_regions, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
-                    gn_stats: bool = True, freeu: bool = False, pag_layers=None) -> fx.GraphModule:
+                    gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77) -> fx.GraphModule:
     """Pass pipeline.  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
@@ -32,7 +32,11 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     the graph is then exactly the one without it) puts a FreeU site in front of the decoder concatenations of the first two
     stages and installs the neutral parameter state as `gm.freeu` (freeu.py).  `pag_layers` (addition, off by default, likewise):
     regular expressions selecting the self-attention sites that take perturbed batch entries (optimizers/insert_pag.py); the state,
-    `gm.pag`, starts with chunks 0 = ordinary attention."""
+    `gm.pag`, starts with chunks 0 = ordinary attention.  `regions=R` (addition, off by default, likewise): every cross-attention
+    site runs R key/value segments of `region_tokens` keys with their own softmax, combined by the weights of `gm.regions`
+    (optimizers/insert_regions.py, regions.py); those sites keep their query projection as a launch of its own."""
+    if regions is not None and fp8:
+        raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
     stats: Dict[str, int] = {}
     if freeu:      # first: the readers of a concatenation still carry their module paths
         stats["freeu_sites"] = insert_freeu(gm)
@@ -42,6 +46,8 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     stats["attention"] = fuse_attention(gm)
     if pag_layers is not None:      # directly after: the query projections still carry their module paths
         stats["pag_sites"] = insert_pag(gm, pag_layers)
+    if regions is not None:         # likewise
+        stats["region_sites"] = insert_regions(gm, regions, region_tokens)
     stats["geglu"] = fuse_geglu(gm)
     stats["linear_silu"] = replace_linear_activ(gm, nn.SiLU())
     stats["group_norm_silu"] = replace_group_norm_activation(gm, nn.SiLU())
@@ -75,8 +81,12 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
-                   pag_layers=None) -> fx.GraphModule:
-    """`pag_layers=("mid",)` (addition): the selected self-attention sites can treat the last B // chunks batch entries of a call as
+                   pag_layers=None, regions=None, region_tokens: int = 77) -> fx.GraphModule:
+    """`regions=R` (addition): regional prompts (regions.py).  The text context is R prompts of `region_tokens` tokens concatenated
+    along the token axis; every cross-attention gives each its own softmax and combines them per latent cell with the weights of
+    `gm.regions` - `bind(rows, latent_hw, device)` once, then `set(masks, positive_rows)` / `clear()` in place, no new capture;
+    after `bind` the state is "off": the bits of the module compiled without it on the first prompt.  Not with `fp8=True`.
+    `pag_layers=("mid",)` (addition): the selected self-attention sites can treat the last B // chunks batch entries of a call as
     perturbed (perturbed-attention guidance, pag.py): `gm.pag.using(chunks)` around the caller's own calls; chunks 0, the initial
     state, is ordinary attention.
     `freeu=True` (addition): the compiled module carries FreeU sites and `gm.freeu`, their parameter state, neutral until
@@ -99,7 +109,10 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     model = model.eval().to(memory_format=torch.channels_last)      # conv weights -> (Cout,R,S,Cin) strides
     if fp8 and p0.dtype != torch.bfloat16:
         raise RuntimeError("fp8 projections need a bfloat16 model")
-    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers)
+    if regions is not None and fp8:
+        raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
+    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
+                         region_tokens=region_tokens)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

@@ -42,6 +42,12 @@ Perturbed-attention guidance (`pag_scale`, `set_pag`; pag.py) adds one more bloc
 latent, and the self-attention sites of a UNet compiled with `pag_layers` return v for them (one copy launch per site instead of
 the attention).  The update is the `st_pag_*` form of the loop's sampler, which adds pag[i] (e_pos - e_pert) before the rescale; the
 scale is one more device table of n_steps floats, so `set_pag` needs no new capture.
+
+Regional prompts (`set_regions`; regions.py) on a UNet compiled with `regions=R`: the loop is built with `tokens = R * region_tokens`,
+the positive text state is the R prompts concatenated along the token axis, and every cross-attention combines the R per-prompt
+results per latent cell with weights derived from `set_regions(masks)`.  The weights are device buffers the sites read by address:
+setting or clearing them is an in-place write, before or after `capture()`.  Until `set_regions` the loop computes what a UNet
+compiled without `regions` computes on the first prompt.
 """
 from __future__ import annotations
 
@@ -72,6 +78,13 @@ class DenoiseLoop:
             from . import pag
             self._pag_state = pag.state_of(unet, "DenoiseLoop(pag_scale=...)")
         self._pag_chunks = 0 if pag_scale is None else (3 if guidance_scale is not None else 2)
+        # regional prompts: the sites are part of the compiled UNet, the text context carries its R prompts side by side
+        from . import regions as _regions
+        self._regions_state = getattr(unet, "regions", None) if isinstance(getattr(unet, "regions", None), _regions.Regions) else None
+        if self._regions_state is not None and tokens != self._regions_state.R * self._regions_state.seg_len:
+            st = self._regions_state
+            raise ValueError(f"DenoiseLoop: this UNet was compiled with regions={st.R}, region_tokens={st.seg_len}: build the loop with "
+                             f"tokens={st.R * st.seg_len} ({st.R} prompts concatenated), got tokens={tokens}")
         self.unet, self.mode, self.dtype = unet, mode, dtype
         self.device = torch.device(device)
         self.tables = tables or euler_discrete_tables(50)
@@ -84,6 +97,8 @@ class DenoiseLoop:
         self.batch = batch
         # guidance: the UNet sees [negative | positive]; with pag_scale one more block, [.. | perturbed]
         rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
+        if self._regions_state is not None:                # the weight buffers of this row count: allocated once, "off"
+            self._regions_state.bind(rows, (lh, lw), dev)
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
         self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
         self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
@@ -169,6 +184,11 @@ class DenoiseLoop:
         """Prompt conditioning, B rows each.  With guidance the negative prompt's rows go first; a missing negative text
         state or pooled embedding is zeros (SDXL's force_zeros_for_empty_prompt), missing negative time ids copy the
         positive ones."""
+        st = self._regions_state
+        if (st is not None and negative_encoder_hidden_states is not None and st.R > 1
+                and negative_encoder_hidden_states.shape[1] == st.seg_len):
+            # one negative prompt for the whole picture: the same text in every segment
+            negative_encoder_hidden_states = negative_encoder_hidden_states.repeat(1, st.R, 1)
         negatives = (negative_encoder_hidden_states, negative_text_embeds, negative_time_ids)
         b = self.batch
         if self.guidance is None:
@@ -277,6 +297,26 @@ class DenoiseLoop:
             state.disable()
         else:
             state.set(s1, s2, b1, b2, version)
+
+    def set_regions(self, masks: Optional[torch.Tensor]) -> None:
+        """Region masks (regions.py): (R, lh, lw) for every sample or (B, R, lh, lw), non-negative, at latent resolution; segment r
+        of the text context conditions the cells where mask r has weight (normalised over r per cell; a cell no mask covers takes
+        segment 0).  The negative block under guidance keeps segment 0, PAG's perturbed block takes the positive weights.
+        `set_regions(None)` is "off".  An in-place write of the buffers the UNet's cross-attention sites read: no new capture, legal
+        before or after `capture()`.  The UNet must have been compiled with `regions=R`.  A loop that shares its UNet and its row
+        count with another owner shares the weights."""
+        from . import regions
+        state = regions.state_of(self.unet, "set_regions")
+        rows = self.x_in.shape[0]
+        if masks is None:
+            state.clear(rows)
+            return
+        if torch.is_tensor(masks) and masks.dim() == 4 and masks.shape[0] != self.batch:
+            raise ValueError(f"set_regions: per-sample masks need B = {self.batch} entries, got {tuple(masks.shape)}")
+        if torch.is_tensor(masks) and tuple(masks.shape[-2:]) != tuple(self.latent.shape[-2:]):
+            raise ValueError(f"set_regions: masks are given at latent resolution {tuple(self.latent.shape[-2:])}, got {tuple(masks.shape)}")
+        first = self.batch if self.guidance is not None else 0
+        state.set(masks, range(first, rows), rows)
 
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,

@@ -1,5 +1,5 @@
 """Micro-benchmark of the HIP operators at the SDXL-base shapes (developer tool).
-Usage: python tools/op_bench.py [linear|conv|attn|norm|all]"""
+Usage: python tools/op_bench.py [linear|lnlinear|conv|attn|norm|regions|all]"""
 import os
 import sys
 
@@ -129,8 +129,31 @@ def norm():
         print(f"layer_norm M={M} C={C}: {us:7.1f} us {2.0 * x.numel() * 2 / us / 1e3:7.1f} GB/s x{cnt} = {us * cnt / 1e3:6.2f} ms")
 
 
+def regions():
+    """The cross-attention site of a transformer block at the two SDXL shapes: the fused query projection + attention launch
+    (st_ln_linear_xattn), its two-launch form, and the regional form (query projection + st_attention_regions) at R = 2, 4."""
+    for T, C, H in [(4096, 640, 10), (1024, 1280, 20)]:
+        x, w, b, g, be = rnd(1, T, C), rnd(C, C) * C ** -0.5, rnd(C), rnd(C), rnd(C)
+        wf, c, d = ops.fold_layer_norm(g, be, w, b)
+        wp, res = rnd(C, C) * C ** -0.5, rnd(1, T, C)
+        _, st = ops.linear(x, wp, None, residual=res, emit_stats=True)
+        k1, v1 = rnd(1, 77, C), rnd(1, 77, C)
+        t_fused = timeit(lambda: ops.ln_linear_xattn(x, st, wf, c, d, 1e-5, k1, v1, H, 0.125))
+        t_q = timeit(lambda: ops.ln_linear(x, st, wf, c, d, 1e-5))
+        q = ops.ln_linear(x, st, wf, c, d, 1e-5)
+        t_a = timeit(lambda: ops.attention(q, k1, v1, H, 0.125))
+        line = f"xattn T={T} C={C} H={H}: fused {t_fused:6.1f} us | ln_linear {t_q:6.1f} + attention(77) {t_a:6.1f} = {t_q + t_a:6.1f} us"
+        for R in (2, 4):
+            kr, vr = rnd(1, R * 77, C), rnd(1, R * 77, C)
+            wt = torch.rand(1, R, T, device=dev)
+            wt = wt / wt.sum(dim=1, keepdim=True)
+            t_r = timeit(lambda: ops.attention_regions(q, kr, vr, wt, H, 0.125, 77))
+            line += f" | regions R={R} {t_r:6.1f} (+ ln_linear = {t_q + t_r:6.1f}) us"
+        print(line)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
-    for name, fn in (("linear", linear), ("lnlinear", lnlinear), ("conv", conv), ("attn", attn), ("norm", norm)):
+    for name, fn in (("linear", linear), ("lnlinear", lnlinear), ("conv", conv), ("attn", attn), ("norm", norm), ("regions", regions)):
         if what in (name, "all"):
             fn()
