@@ -58,7 +58,7 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
                                               st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
                                               st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then a DoRA and a LoHa / LoKr entry point beside
-                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed (st_attention_regions, after 18, likewise);
+                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed (st_attention_regions and st_attention_segments, after 18, likewise);
                                               18: st_lora_merge takes one ST_LORA_FORM_WORDS segment row, the norm pass's tables and `forms`, and is
                                               the only LoRA entry point again: the two beside it are removed) */
 const char* st_last_error(void);           /* host string, thread-local     */
@@ -456,6 +456,28 @@ int st_attention_pag(const void* q, const void* k, const void* v, void* out, int
 int st_attention_regions(const void* q, const void* k, const void* v, const float* weights, void* out,
                          int B, int T, int R, int seg_len, int H, int D,
                          long ldq, long ldk, long ldv, long ldo, float scale, int dtype, void* stream);
+
+/* ---- ragged segmented cross-attention (no reference counterpart: IP-Adapter's decoupled cross-attention, Ye et al. 2023;
+ * diffusers' IPAdapterAttnProcessor2_0): S key/value segments of different lengths in different buffers, each with its own softmax,
+ * combined per query row under a live per-segment scale.
+ *
+ * st_attention_segments: q (B, T, H*D); segment r: k, v of `len` keys, token strides ldk / ldv and batch strides bsk / bsv in
+ * elements (bs* = 0: one K / V for every batch entry); weights (B, S, T) fp32, dense; seg_scale (S) fp32 or NULL = all 1;
+ *   w_eff[b,r,t] = fl32(seg_scale[r] * weights[b,r,t])
+ *   out[b,t,h,:] = sum_r w_eff[b,r,t] * softmax_s(scale * q[b,t,h] . k_r[b,s,h]) v_r[b,s,h]                 (s over the len_r keys).
+ * Segments run in index order; the weighted sum is formed in fp32 from the un-rounded normalised segment results and rounded to
+ * the storage type once, so weights 1 under a one-hot seg_scale give the bits of st_attention on that segment, and equal lengths
+ * in one buffer with seg_scale NULL give the bits of st_attention_regions.
+ * `segs` is a HOST array of S descriptors, read at the call and passed to the kernel by value (a captured launch keeps them);
+ * `weights` and `seg_scale` are DEVICE memory read at every launch.  A segment whose seg_scale is exactly 0 is skipped by the whole
+ * grid: its k / v are never read (they need not be finite) and it contributes nothing; with every segment skipped out = 0.  A
+ * segment that runs with weight 0 on a row contributes exactly 0 there (its k / v must be finite).
+ * dtype ST_BF16 or ST_F16, D = 64, 1 <= S <= 8, 1 <= len < 256; q batch stride T*ldq, out T*ldo; q, out and every k, v 16-byte
+ * aligned; ldq, ldk, ldv, bsk, bsv multiples of 8, ldk, ldv >= H*D, ldo a multiple of 4.  One launch, the grid of
+ * st_attention_regions; no atomics, nothing written outside out; never emits a split image (csrc/attention_segments.hip). */
+typedef struct { const void* k; const void* v; long ldk, ldv; long bsk, bsv; int len; } st_kv_segment;
+int st_attention_segments(const void* q, const st_kv_segment* segs, int S, const float* weights, const float* seg_scale,
+                          void* out, int B, int T, int H, int D, long ldq, long ldo, float scale, int dtype, void* stream);
 
 /* The three updates with a third noise prediction: st_cfg_euler_step, st_dpmpp2m_step and st_sde_step with one more device table
  * `pag` of n_steps floats (never NULL) and one more row block of eps / next_in, the prediction under perturbed self-attention.

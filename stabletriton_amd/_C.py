@@ -61,10 +61,18 @@ SIGNATURES = {
     "st_freeu": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _p, _p, _i, _p, _z, _p]),
     "st_attention_pag": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _p]),
     "st_attention_regions": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _p]),
+    "st_attention_segments": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _l, _l, _f, _i, _p]),
     "st_pag_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
 }
+
+
+
+class KVSegment(C.Structure):
+    """st_kv_segment: one key/value segment of st_attention_segments (strides in elements; bs*: between batch entries)."""
+    _fields_ = [("k", _p), ("v", _p), ("ldk", _l), ("ldv", _l), ("bsk", _l), ("bsv", _l), ("len", _i)]
+
 
 _lib = None
 

@@ -19,7 +19,7 @@
 // two differ where the fp32 product lands on a binary16 midpoint, about 3 values in 10^5.  The fp32 value o * inv alone cannot
 // give the first kind back, so for those elements the kernel also carries the product's fp32 residual fma(o, inv, -(o * inv))
 // (exact), weighted like the value itself, and the final conversion is one rounding of value + residual (RegionsOut,
-// fma_mix_f16 below).  tests/test_regions_gpu.py pins the correspondence bit for bit; bf16 converts every element alike.
+// fma_mix_f16 in attention_sum.h).  tests/test_regions_gpu.py pins the correspondence bit for bit; bf16 converts every element alike.
 //
 // Between two segments there is a block-wide barrier: the body ends on s_waitcnt vmcnt(0) with no barrier, and its prologue
 // requests tiles 0 and 1 into ring slots 0 and 1 at once - without the barrier a fast wave's next-segment DMA could land in the
@@ -27,24 +27,7 @@
 // so every wave of a block takes part in every cooperative tile load.
 // No atomics; the only stores are the T * H * 64 values of `out`.  16-bit element types only (fp32 and the other head sizes go
 // R times through st_attention: ops.attention_regions).
-#include "attention_core.h"
-
-constexpr int REGIONS_MAX = 8;
-
-// elements (of every four consecutive head-dim values a lane stores) that st_attention's fp16 epilogue rounds once from the exact
-// product o * inv (see the file comment)
-template <typename E> struct RegionsOut { static constexpr bool fused(int) { return false; } };
-template <> struct RegionsOut<f16> { static constexpr bool fused(int e) { return e == 0 || e == 3; } };
-
-// binary16(a + c) with ONE rounding: v_fma_mixlo_f16 on fp32 sources
-__device__ __forceinline__ f16 fma_mix_f16(float a, float c) {
-    unsigned r = 0;
-    asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "+v"(r) : "v"(a), "v"(1.0f), "v"(c));
-    return __builtin_bit_cast(f16, (unsigned short)r);
-}
-template <typename E> __device__ __forceinline__ E regions_round(float a, float c);
-template <> __device__ __forceinline__ bf16 regions_round<bf16>(float a, float) { return (bf16)a; }
-template <> __device__ __forceinline__ f16 regions_round<f16>(float a, float c) { return fma_mix_f16(a, c); }
+#include "attention_sum.h"      // RegionsOut, fma_mix_f16, regions_round, REGIONS_MAX: shared with attention_segments.hip
 
 template <typename E>
 __global__ __launch_bounds__(256) void attn_regions_kernel(const E* __restrict__ Q, const E* __restrict__ K, const E* __restrict__ V,

@@ -55,6 +55,9 @@ class _HoistedUNet(nn.Module):
         self._pag_chunks = 0                      # enable_pag: the last B // chunks rows of a call are perturbed (0: none)
         self._regions = None                      # set_regions: (masks, chunks), applied to the buffers of a call's (rows, latent size)
         self._regions_applied = {}                # ... rows -> the latent size the buffers of that row count were last written for
+        self._ip_images = {}                      # set_ip_adapter_image: slot -> (tokens, negative_tokens, chunks)
+        self._ip_masks = {}                       # set_ip_adapter_masks: slot -> masks
+        self._ip_applied = {}                     # ... rows -> the latent size the buffers of that row count were last written for
 
     def refresh_weights(self) -> int:
         """Re-derive fused / folded weight buffers after an in-place weight update (also done at every new prompt).
@@ -161,6 +164,82 @@ class _HoistedUNet(nn.Module):
         state.set(masks, regions.positive_rows(rows, chunks), rows)
         self._regions_applied[rows] = hw
 
+    # ---- IP-Adapter image prompts (ip_adapter.py): buffers the cross-attention sites read by address; the captured graphs stay ----
+    def _ip(self, what: str):
+        from . import ip_adapter
+        return ip_adapter.state_of(self.compiled, what)
+
+    def load_ip_adapter(self, state_dict, slot: int = 0):
+        """Copy an IP-Adapter checkpoint's to_k_ip / to_v_ip weights into adapter slot `slot` (ip_adapter.IPAdapter.load); returns
+        its image_proj sub-dict.  An image set earlier is projected again with the new weights at the next call.
+        `added_cond_kwargs["image_embeds"]` is NOT read by the wrappers: project the embeddings once
+        (ip_adapter.project_image_embeds, or a Resampler of the caller's) and pass the tokens to `set_ip_adapter_image`.  Raises on a
+        wrapper compiled without `ip_adapter=N`."""
+        proj = self._ip("load_ip_adapter").load(state_dict, slot)
+        self._ip_applied = {}
+        return proj
+
+    def set_ip_adapter_image(self, tokens: torch.Tensor, negative_tokens: Optional[torch.Tensor] = None, slot: int = 0,
+                             chunks: int = 2) -> None:
+        """Image tokens (batch or 1, N, cross_dim) of slot `slot` for every following call.  `chunks` says how a call's batch
+        divides, as in `set_regions`: 2 = [uncond | cond], 3 = [uncond | cond | cond (perturbed)] - the first block is the negative
+        one and takes `negative_tokens` (default: zero tokens = no contribution), the others take `tokens`; 1 = every row takes
+        `tokens`.  The K/V buffers of a batch size are allocated at the first call that has it and written in place."""
+        from . import regions
+        st = self._ip("set_ip_adapter_image")
+        slot = st._slot(slot, "set_ip_adapter_image")
+        regions.positive_rows(chunks, chunks)                    # (validates chunks)
+        for t, what in ((tokens, "tokens"), (negative_tokens, "negative_tokens")):
+            if t is not None and (torch.as_tensor(t).dim() != 3 or torch.as_tensor(t).shape[1] != st.tokens[slot]):
+                raise ValueError(f"set_ip_adapter_image: {what} must be (batch or 1, N, cross_dim) with N = {st.tokens[slot]} tokens for slot "
+                                 f"{slot} (compiled with ip_adapter={st.tokens}), got {tuple(torch.as_tensor(t).shape)}")
+        if chunks == 1 and negative_tokens is not None:
+            raise ValueError("set_ip_adapter_image: negative_tokens need a negative row block (chunks 2 or 3)")
+        self._ip_images[slot] = (tokens, negative_tokens, chunks)
+        self._ip_applied = {}
+
+    def set_ip_adapter_scale(self, scale, slot: int = 0) -> None:
+        """A float for every site, or a mapping {regular expression on the site paths: float} (first match wins, "mid" selects the
+        middle block, unmatched sites get 0); 0 switches a site's image attention off at no cost.  Written at once, in place."""
+        self._ip("set_ip_adapter_scale").set_scale(scale, slot)
+
+    def set_ip_adapter_masks(self, masks: Optional[torch.Tensor], slot: int = 0) -> None:
+        """Where slot `slot`'s image prompt applies: (lh, lw) or (batch, lh, lw) at latent resolution, written to every row of the
+        following calls; None = everywhere.  A call whose latent is not the masks' size raises."""
+        from . import ip_adapter
+        st = self._ip("set_ip_adapter_masks")
+        slot = st._slot(slot, "set_ip_adapter_masks")
+        if masks is not None:
+            ip_adapter.mask_level_weights(masks, 0)               # (validates the masks now, not at the next call)
+        self._ip_masks[slot] = masks
+        self._ip_applied = {}
+
+    def unload_ip_adapter(self, slot: int = 0) -> None:
+        """Slot `slot` back to "off": scale 0, weights and image K/V zero, masks 1 - the bits of the wrapper before the adapter."""
+        st = self._ip("unload_ip_adapter")
+        st.unload(slot)
+        self._ip_images.pop(slot, None)
+        self._ip_masks.pop(slot, None)
+
+    def _apply_ip_adapter(self, sample: torch.Tensor) -> None:
+        """Bind the buffers of this call's batch and latent size and write what was set for this geometry (as _apply_regions)."""
+        from . import ip_adapter
+        state = getattr(self.compiled, "ip_adapter", None)
+        if not isinstance(state, ip_adapter.IPAdapter) or torch.cuda.is_current_stream_capturing():
+            return
+        rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
+        state.bind(rows, hw, sample.device)
+        if self._ip_applied.get(rows) == hw:
+            return
+        for slot, (tokens, negative, chunks) in self._ip_images.items():
+            state.set_image(tokens, negative, slot, rows, chunks)
+        for slot, masks in self._ip_masks.items():
+            if masks is not None and tuple(torch.as_tensor(masks).shape[-2:]) != hw:
+                raise ValueError(f"set_ip_adapter_masks: the masks are {tuple(torch.as_tensor(masks).shape[-2:])}, this call's latent is {hw}: "
+                                 "masks are given at latent resolution")
+            state.set_masks(masks, slot, rows)
+        self._ip_applied[rows] = hw
+
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
         version it had then.  A different object of the same shape (ComfyUI re-concatenates cond | uncond on every call) is
@@ -231,6 +310,7 @@ class _HoistedUNet(nn.Module):
         io_dtype = sample.dtype
         dev = sample.device
         self._apply_regions(sample)
+        self._apply_ip_adapter(sample)
         self._context_for(ehs)
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor(float(timesteps), dtype=torch.float32)
@@ -295,31 +375,35 @@ class DiffusersUNet(_HoistedUNet):
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                                 region_tokens: int = 77) -> DiffusersUNet:
+                                 region_tokens: int = 77, ip_adapter=None) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
     `pag_layers=("mid",)` compiles the perturbed-attention sites in (diffusers' `pag_applied_layers`): `enable_pag(chunks)` /
     `disable_pag()` then say which rows of a call are the perturbed ones.
     `regions=R` compiles regional cross-attention in (regions.py): the pipeline passes R prompts of `region_tokens` tokens
-    concatenated along the token axis as `encoder_hidden_states`; `set_regions(masks, chunks)` / `clear_regions()` drive it."""
+    concatenated along the token axis as `encoder_hidden_states`; `set_regions(masks, chunks)` / `clear_regions()` drive it.
+    `ip_adapter=N` (or a tuple of token counts, one per adapter) compiles IP-Adapter image attention in (ip_adapter.py):
+    `load_ip_adapter`, `set_ip_adapter_image`, `set_ip_adapter_scale`, `set_ip_adapter_masks`, `unload_ip_adapter` drive it;
+    `added_cond_kwargs["image_embeds"]` is not read."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
         model = UNet2DConditionModel(spec)
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
-    compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens)
+    compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
+                              ip_adapter=ip_adapter)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                        regions=None, region_tokens: int = 77):
+                        regions=None, region_tokens: int = 77, ip_adapter=None):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
-                                             regions=regions, region_tokens=region_tokens)
+                                             regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter)
     return pipe
 
 
@@ -340,21 +424,23 @@ class ComfyUNet(_HoistedUNet):
 
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                       region_tokens: int = 77) -> ComfyUNet:
+                       region_tokens: int = 77, ip_adapter=None) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
     with regional cross-attention (conditioning masks / "attention couple"): `context` is the R conditionings concatenated along
-    the token axis, `set_regions(masks, chunks)` / `clear_regions()` drive it."""
+    the token axis, `set_regions(masks, chunks)` / `clear_regions()` drive it.  `ip_adapter=N`: with IP-Adapter image attention
+    (the IPAdapter nodes), driven by `load_ip_adapter` / `set_ip_adapter_image` / `set_ip_adapter_scale` / `set_ip_adapter_masks` /
+    `unload_ip_adapter`."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                              region_tokens=region_tokens)
+                              region_tokens=region_tokens, ip_adapter=ip_adapter)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                      regions=None, region_tokens: int = 77) -> ComfyUNet:
+                      regions=None, region_tokens: int = 77, ip_adapter=None) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens, ip_adapter)
     model_patcher.model.diffusion_model = adapter
     return adapter

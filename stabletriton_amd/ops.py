@@ -1086,6 +1086,94 @@ def attention_regions(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, weights
     return out
 
 
+def attention_segments(q: torch.Tensor, segments, weights: torch.Tensor, seg_scale, num_heads: int, scale: float) -> torch.Tensor:
+    """Cross-attention over S key/value segments of different lengths in different buffers, each with its own softmax, combined
+    per query row under a per-segment scale - IP-Adapter's decoupled cross-attention (ip_adapter.py, csrc/attention_segments.hip):
+        out[b,t,h] = sum_r fl32(seg_scale[r] * weights[b,r,t]) * softmax(scale * q[b,t,h] k_r[b,:,h]^T) v_r[b,:,h]
+    `segments`: a list of (k, v) pairs, each (B, len_r, H*D) with unit stride along the last axis - column slices of a wider buffer
+    (the k | v halves of the hoisted context cache) are taken as they are, anything else is made contiguous.  `weights` (B, S, T)
+    fp32.  `seg_scale`: None (all 1), a float32 DEVICE tensor (S,) - read at every launch, so a captured launch follows in-place
+    writes, and a segment whose entry is 0 is skipped by the whole grid (its k / v are never read and need not be finite) - or a
+    sequence of S host floats, folded into the weights here (segments at 0 are dropped before the launch).
+    bf16 / fp16 at head size 64 is ONE launch; fp32 (strict mode) and head sizes 16 / 32 / 128 take the slow path: one `attention`
+    launch per segment and a torch fp32 weighted sum of their (rounded) results, rounded once - elementwise torch ops, legal inside
+    a capture, no split image.  The slow path skips a scale-0 segment only when `seg_scale` is host floats; with a device table
+    it multiplies, and finite k / v are the caller's duty.  One-hot scales with weights 1 give the bits of `attention` on that
+    segment on both paths; every segment at 0 gives zeros."""
+    _C.require_device(q, weights)
+    lib = _C.load()
+    if q.dim() != 3:
+        raise BackendError("attention_segments expects q (B, T, H*D)")
+    B, T, Cc = q.shape
+    pairs = [tuple(p) if isinstance(p, (tuple, list)) else () for p in segments]
+    if not all(len(p) == 2 and torch.is_tensor(p[0]) and torch.is_tensor(p[1]) for p in pairs):
+        raise BackendError("attention_segments: segments must be a list of (k, v) tensor pairs")
+    S = len(pairs)
+    if not 1 <= S <= REGIONS_MAX:
+        raise BackendError(f"attention_segments: S {S} outside [1, {REGIONS_MAX}] segments")
+    if weights.dim() != 3 or tuple(weights.shape) != (B, S, T) or weights.dtype != torch.float32:
+        raise BackendError(f"attention_segments: weights must be float32 (B, S, T) = ({B}, {S}, {T}) for q {tuple(q.shape)} and {S} segments, "
+                           f"got {tuple(weights.shape)} {weights.dtype}")
+    for r, (k, v) in enumerate(pairs):
+        _C.require_device(k, v)
+        if k.dim() != 3 or k.shape != v.shape or k.shape[0] != B or k.shape[2] != Cc or k.shape[1] < 1:
+            raise BackendError(f"attention_segments: segment {r}: k / v must be (B, len, H*D) = ({B}, len, {Cc}), got k {tuple(k.shape)}, "
+                               f"v {tuple(v.shape)}")
+        if k.dtype != q.dtype or v.dtype != q.dtype:
+            raise BackendError(f"attention_segments: segment {r}: q, k and v must share a dtype, got {q.dtype}, {k.dtype}, {v.dtype}")
+    host_scale = None
+    if seg_scale is not None and not torch.is_tensor(seg_scale):
+        host_scale = [float(s) for s in seg_scale]
+        if len(host_scale) != S:
+            raise BackendError(f"attention_segments: seg_scale must have S = {S} entries, got {len(host_scale)}")
+    elif seg_scale is not None:
+        _C.require_device(seg_scale)
+        if tuple(seg_scale.shape) != (S,) or seg_scale.dtype != torch.float32 or not seg_scale.is_contiguous():
+            raise BackendError(f"attention_segments: seg_scale must be a contiguous float32 device tensor (S,) = ({S},) or host floats, got "
+                               f"{tuple(seg_scale.shape)} {seg_scale.dtype}")
+    D = Cc // num_heads
+    if q.dtype == torch.float32 or D != 64:
+        # the documented slow path: every segment through the ordinary attention launch, then the weighted sum in fp32
+        acc = None
+        for r, (k, v) in enumerate(pairs):
+            if host_scale is not None and host_scale[r] == 0.0:
+                continue
+            w = weights[:, r] if seg_scale is None else weights[:, r] * (host_scale[r] if host_scale is not None else seg_scale[r])
+            term = attention(q, k, v, num_heads, scale).float() * w.unsqueeze(-1)
+            acc = term if acc is None else acc + term
+        return torch.zeros_like(q) if acc is None else acc.to(q.dtype)
+
+    if host_scale is not None:      # folded into the weights (the kernel's own fl32(scale * weight)); segments at 0 never reach the launch
+        keep = [r for r in range(S) if host_scale[r] != 0.0]
+        if not keep:
+            return torch.zeros_like(q)
+        weights = torch.stack([weights[:, r] * host_scale[r] for r in keep], dim=1)
+        pairs, seg_scale, S = [pairs[r] for r in keep], None, len(keep)
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    def seg(t):      # unit stride along the channels; token and batch strides as they are
+        return t if t.stride(2) == 1 and t.stride(1) >= Cc and t.stride(0) >= 0 else t.contiguous()
+
+    q_, ldq = tok(q)
+    table = (_C.KVSegment * S)()
+    held = []
+    for r, (k, v) in enumerate(pairs):
+        k_, v_ = seg(k), seg(v)
+        held.append((k_, v_))
+        table[r] = _C.KVSegment(k_.data_ptr(), v_.data_ptr(), k_.stride(1), v_.stride(1), k_.stride(0), v_.stride(0), k_.shape[1])
+    w_ = weights.contiguous()
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    _C.check(lib.st_attention_segments(q_.data_ptr(), table, S, w_.data_ptr(), None if seg_scale is None else seg_scale.data_ptr(),
+                                       out.data_ptr(), B, T, num_heads, D, ldq, Cc, float(scale), _C.dtype_code(q.dtype), _C.stream_ptr()),
+             "attention_segments")
+    return out
+
+
 # ----------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int, *,
            upsample2x: bool = False, rowbias: Optional[torch.Tensor] = None,

@@ -16,15 +16,17 @@ import torch
 from torch import fx, nn
 
 from . import _C, ops
+from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_pag, insert_regions, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_ip_adapter, insert_pag, insert_regions, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
-                    gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77) -> fx.GraphModule:
+                    gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
+                    ip_adapter=None) -> fx.GraphModule:
     """Pass pipeline.  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
@@ -34,9 +36,13 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     regular expressions selecting the self-attention sites that take perturbed batch entries (optimizers/insert_pag.py); the state,
     `gm.pag`, starts with chunks 0 = ordinary attention.  `regions=R` (addition, off by default, likewise): every cross-attention
     site runs R key/value segments of `region_tokens` keys with their own softmax, combined by the weights of `gm.regions`
-    (optimizers/insert_regions.py, regions.py); those sites keep their query projection as a launch of its own."""
+    (optimizers/insert_regions.py, regions.py); those sites keep their query projection as a launch of its own.  `ip_adapter=N` or a
+    tuple of up to 4 image token counts (addition, off by default, likewise): every cross-attention site adds a decoupled attention
+    over the image tokens of each adapter slot under the live scales of `gm.ip_adapter` (optimizers/insert_ip_adapter.py,
+    ip_adapter.py); the same cost per site as regions; not with `regions` or `fp8`."""
     if regions is not None and fp8:
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
+    check_combination(ip_adapter, regions, fp8)
     stats: Dict[str, int] = {}
     if freeu:      # first: the readers of a concatenation still carry their module paths
         stats["freeu_sites"] = insert_freeu(gm)
@@ -48,6 +54,8 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
         stats["pag_sites"] = insert_pag(gm, pag_layers)
     if regions is not None:         # likewise
         stats["region_sites"] = insert_regions(gm, regions, region_tokens)
+    if ip_adapter is not None:      # likewise
+        stats["ip_adapter_sites"] = insert_ip_adapter(gm, ip_adapter)
     stats["geglu"] = fuse_geglu(gm)
     stats["linear_silu"] = replace_linear_activ(gm, nn.SiLU())
     stats["group_norm_silu"] = replace_group_norm_activation(gm, nn.SiLU())
@@ -81,8 +89,13 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
-                   pag_layers=None, regions=None, region_tokens: int = 77) -> fx.GraphModule:
-    """`regions=R` (addition): regional prompts (regions.py).  The text context is R prompts of `region_tokens` tokens concatenated
+                   pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None) -> fx.GraphModule:
+    """`ip_adapter=N` (addition; 4: base adapters, 16: plus; a tuple of up to 4 counts for several adapters): IP-Adapter image prompts
+    (ip_adapter.py).  Every cross-attention adds s * Attn(q, K_img, V_img) per adapter slot, in the same launch.  `gm.ip_adapter` -
+    `bind(rows, latent_hw, device)` once, then `load(state_dict, slot)`, `set_image(tokens, ...)`, `set_scale(scale, slot)`,
+    `set_masks(masks, slot)`, `unload(slot)`, all in place, no new capture; a slot at scale 0 (the state after `bind`) is skipped:
+    the bits of the module compiled without it.  Not with `regions` or `fp8=True`.
+    `regions=R` (addition): regional prompts (regions.py).  The text context is R prompts of `region_tokens` tokens concatenated
     along the token axis; every cross-attention gives each its own softmax and combines them per latent cell with the weights of
     `gm.regions` - `bind(rows, latent_hw, device)` once, then `set(masks, positive_rows)` / `clear()` in place, no new capture;
     after `bind` the state is "off": the bits of the module compiled without it on the first prompt.  Not with `fp8=True`.
@@ -111,8 +124,9 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
         raise RuntimeError("fp8 projections need a bfloat16 model")
     if regions is not None and fp8:
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
+    check_combination(ip_adapter, regions, fp8)
     gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                         region_tokens=region_tokens)
+                         region_tokens=region_tokens, ip_adapter=ip_adapter)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

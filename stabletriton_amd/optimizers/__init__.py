@@ -15,6 +15,7 @@ from .fuse_skip_cat import fuse_skip_cat
 from .insert_freeu import insert_freeu
 from .insert_pag import insert_pag
 from .insert_regions import insert_regions
+from .insert_ip_adapter import insert_ip_adapter
 from .cleanup import dedupe_pure_calls, fuse_token_residual
 from .layout import keep_channels_last
 from .graphs import make_dynamic_graphed_callable

@@ -48,6 +48,13 @@ the positive text state is the R prompts concatenated along the token axis, and 
 results per latent cell with weights derived from `set_regions(masks)`.  The weights are device buffers the sites read by address:
 setting or clearing them is an in-place write, before or after `capture()`.  Until `set_regions` the loop computes what a UNet
 compiled without `regions` computes on the first prompt.
+
+IP-Adapter image prompts (`load_ip_adapter`, `set_ip_adapter_image`, `set_ip_adapter_scale`, `set_ip_adapter_masks`,
+`unload_ip_adapter`; ip_adapter.py) on a UNet compiled with `ip_adapter=N`: every cross-attention adds a decoupled attention over the
+image tokens of each adapter slot, in the same launch, under per-site scales in a device table.  Adapter weights, image K/V, scales
+and masks are device buffers the sites read by address: every one of the five calls is an in-place write, before or after
+`capture()`.  A slot at scale 0 - the state until `set_ip_adapter_scale` - is skipped by the kernel: the bits of a UNet compiled
+without `ip_adapter`.
 """
 from __future__ import annotations
 
@@ -99,6 +106,10 @@ class DenoiseLoop:
         rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
         if self._regions_state is not None:                # the weight buffers of this row count: allocated once, "off"
             self._regions_state.bind(rows, (lh, lw), dev)
+        from . import ip_adapter as _ip
+        self._ip_state = getattr(unet, "ip_adapter", None) if isinstance(getattr(unet, "ip_adapter", None), _ip.IPAdapter) else None
+        if self._ip_state is not None:                     # scale table, mask weights, image K/V of this row count: allocated once, "off"
+            self._ip_state.bind(rows, (lh, lw), dev)
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
         self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
         self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
@@ -317,6 +328,43 @@ class DenoiseLoop:
             raise ValueError(f"set_regions: masks are given at latent resolution {tuple(self.latent.shape[-2:])}, got {tuple(masks.shape)}")
         first = self.batch if self.guidance is not None else 0
         state.set(masks, range(first, rows), rows)
+
+    # ---- IP-Adapter image prompts (ip_adapter.py): in-place writes of buffers the sites read by address, no new capture -----
+    def _ip(self, what: str):
+        from . import ip_adapter
+        return ip_adapter.state_of(self.unet, what)
+
+    def load_ip_adapter(self, state_dict, slot: int = 0):
+        """Copy an IP-Adapter checkpoint's to_k_ip / to_v_ip weights into adapter slot `slot` (ip_adapter.IPAdapter.load: the
+        published {"image_proj", "ip_adapter"} layout, the same flattened, or path-spelled keys; validated before anything is
+        written).  Returns the checkpoint's image_proj sub-dict (ip_adapter.project_image_embeds turns CLIP image embeddings into
+        tokens with it).  The UNet must have been compiled with `ip_adapter=N`.  Call `set_ip_adapter_image` afterwards."""
+        return self._ip("load_ip_adapter").load(state_dict, slot)
+
+    def set_ip_adapter_image(self, tokens: torch.Tensor, negative_tokens: Optional[torch.Tensor] = None, slot: int = 0) -> None:
+        """Image tokens (B or 1, N, cross_dim) of slot `slot`, projected once into every site's K/V buffers.  Under guidance the
+        negative block takes `negative_tokens` (default: zero tokens = no contribution), PAG's perturbed block the positive ones."""
+        rows = self.x_in.shape[0]
+        self._ip("set_ip_adapter_image").set_image(tokens, negative_tokens, slot, rows, rows // self.batch, self.guidance is not None)
+
+    def set_ip_adapter_scale(self, scale, slot: int = 0) -> None:
+        """A float for every site, or a mapping {regular expression on the site paths: float} (first match wins, "mid" selects the
+        middle block, unmatched sites get 0).  Scale 0 switches a site's image attention off at no cost."""
+        self._ip("set_ip_adapter_scale").set_scale(scale, slot)
+
+    def set_ip_adapter_masks(self, masks: Optional[torch.Tensor], slot: int = 0) -> None:
+        """Where slot `slot`'s image prompt applies: (lh, lw) or (B, lh, lw) at latent resolution, non-negative; None = everywhere."""
+        if masks is not None:
+            m = torch.as_tensor(masks)
+            if m.dim() == 3 and m.shape[0] != self.batch:
+                raise ValueError(f"set_ip_adapter_masks: per-sample masks need B = {self.batch} entries, got {tuple(m.shape)}")
+            if tuple(m.shape[-2:]) != tuple(self.latent.shape[-2:]):
+                raise ValueError(f"set_ip_adapter_masks: masks are given at latent resolution {tuple(self.latent.shape[-2:])}, got {tuple(m.shape)}")
+        self._ip("set_ip_adapter_masks").set_masks(masks, slot, self.x_in.shape[0])
+
+    def unload_ip_adapter(self, slot: int = 0) -> None:
+        """Slot `slot` back to "off": scale 0, weights and image K/V zero, masks 1 - the bits of the loop before the adapter."""
+        self._ip("unload_ip_adapter").unload(slot)
 
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
