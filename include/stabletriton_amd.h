@@ -439,6 +439,36 @@ int st_freeu(const void* h, const void* skip, void* h_out, void* skip_out, int N
 int st_attention_pag(const void* q, const void* k, const void* v, void* out, int B, int T, int S, int H, int D,
                      long ldq, long ldk, long ldv, long ldo, float scale, int dtype, int ident_count, void* stream);
 
+/* ---- smoothed energy guidance (SEG; Hong 2024; no reference counterpart: the published SEG pipeline for SDXL, ComfyUI's SEG node):
+ * the perturbed batch entries of a self-attention run with their projected queries Gaussian-blurred over the token grid
+ * (csrc/seg.hip).  Added after ABI 18 without a bump: new entry points, no existing signature or contract changed.
+ *
+ * st_seg_blur: q holds n * h * w rows of C values at row stride ldq (3 * H * D behind the fused q|k|v projection), token
+ * t = y * w + x of every batch entry; out the same rows at row stride ldo.  Every one of the C planes of h x w becomes the separable
+ * convolution g (x) g of its reflect-padded self (pad k / 2, the edge sample not repeated), fp32 accumulation, the intermediate
+ * between the two passes fp32, one rounding on output.  params is a DEVICE row of ST_SEG_PARAM_WORDS floats, read when the kernels
+ * run: [mode, k, g_0 ... g_{k-1}], k odd with k / 2 < min(h, w) (the kernels clamp what they read to that range); mode != 0:
+ * every token of a plane becomes the plane's mean (rows summed in x order, then the row means in y order: fixed order, no
+ * atomics, bitwise repeatable).  h, w <= ST_SEG_MAX_SIDE, C and both strides multiples of 16 bytes of elements, q and out 16-byte
+ * aligned and not overlapping.  Grids whose fp32 plane pair fits the LDS take one launch and no workspace; the others two launches
+ * through `workspace`, st_seg_blur_workspace_bytes(...) bytes (0: none needed), 16-byte aligned, not shared between concurrent
+ * launches.  Nothing is written outside the n * h * w output rows.
+ *
+ * st_attention_seg: st_attention whose LAST tail_count batch entries (0 <= tail_count <= B) take blurred queries; tail_count > 0
+ * needs T == S == h * w.  st_attention, unmodified, on the leading B - tail_count entries (bit-identical to st_attention on that
+ * sub-batch; skipped when there are none), st_seg_blur of the tail's queries into `scratch` (tail_count * T dense rows of H * D
+ * elements, 16-byte aligned), st_attention on the tail with q = scratch and the tail's own k, v and out rows.  tail_count == 0 is
+ * st_attention (scratch, params and workspace may be NULL).  workspace as st_seg_blur's for (tail_count, h, w, H * D).  An image
+ * armed by st_arm_split_output for the whole (B * T, H * D) fp32 output is handed to the two attention launches for their rows. */
+#define ST_SEG_MAX_SIDE 128
+#define ST_SEG_PARAM_WORDS 132              /* 2 + the 129 taps of a 128 x 128 grid, rounded up to 16 bytes */
+size_t st_seg_blur_workspace_bytes(int n, int h, int w, int C, int dtype);
+int st_seg_blur(const void* q, void* out, const float* params, int n, int h, int w, int C, long ldq, long ldo, int dtype,
+                void* workspace, size_t workspace_bytes, void* stream);
+int st_attention_seg(const void* q, const void* k, const void* v, void* out, void* scratch, int B, int T, int S, int H, int D,
+                     long ldq, long ldk, long ldv, long ldo, float scale, int dtype, int tail_count, int h, int w,
+                     const float* params, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- regional prompts (no reference counterpart: ComfyUI's conditioning masks / "attention couple", the diffusers community
  * regional-prompting pipeline): cross-attention over R key/value segments, each with its own softmax, combined per query row.
  *

@@ -16,6 +16,7 @@ from .build import lib_path
 ST_F32, ST_BF16, ST_F16, ST_F32S = 0, 1, 2, 3
 ST_NCHW, ST_NHWC = 0, 1
 LORA_TILE_N, LORA_TILE_K = 64, 128      # st_lora_merge's tile (ST_LORA_TILE_N / _K)
+SEG_MAX_SIDE, SEG_PARAM_WORDS = 128, 132      # st_seg_blur's largest token grid side and its parameter row (ST_SEG_MAX_SIDE / _PARAM_WORDS)
 EPI_BIAS, EPI_SILU, EPI_GEGLU, EPI_RESIDUAL, EPI_ROWBIAS = 1, 2, 4, 8, 16
 ABI_VERSION = 18
 
@@ -65,6 +66,9 @@ SIGNATURES = {
     "st_pag_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
+    "st_seg_blur_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "st_seg_blur": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _i, _p, _z, _p]),
+    "st_attention_seg": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _i, _i, _p, _p, _z, _p]),
 }
 
 

@@ -53,6 +53,7 @@ class _HoistedUNet(nn.Module):
         self._new_prompt = False                  # set when a context was (re)projected: the fp8 plan measures its scales again
         self._last_t = None                       # fp8 plan only: the last call's (largest) timestep, to tell where a trajectory starts
         self._pag_chunks = 0                      # enable_pag: the last B // chunks rows of a call are perturbed (0: none)
+        self._seg_chunks = 0                      # enable_seg: likewise, for the smoothed-energy sites (blurred queries)
         self._regions = None                      # set_regions: (masks, chunks), applied to the buffers of a call's (rows, latent size)
         self._regions_applied = {}                # ... rows -> the latent size the buffers of that row count were last written for
         self._ip_images = {}                      # set_ip_adapter_image: slot -> (tokens, negative_tokens, chunks)
@@ -120,6 +121,42 @@ class _HoistedUNet(nn.Module):
         import contextlib
         state = getattr(self.compiled, "pag", None)
         return state.using(chunks) if state is not None else contextlib.nullcontext()
+
+    # ---- smoothed energy guidance (seg.py): which rows of a call take blurred queries; sigma is a device row, written in place ----
+    def enable_seg(self, chunks: int, sigma: float = float("inf")) -> None:
+        """The last B // chunks batch rows of every following call take the smoothed-energy self-attention (queries Gaussian-blurred
+        over the latent grid at the sites compiled in with `seg_layers`; sigma = infinity: their spatial mean): 3 for a pipeline
+        with guidance ([uncond | cond | cond]), 2 without ([cond | cond]), 1 for a fully perturbed call (ComfyUI's SEG node makes
+        one).  Only the UNet is evaluated here: the guidance combine stays with the calling pipeline.  One captured graph per
+        `chunks`; sigma needs none (`set_seg_sigma`).  Raises on a wrapper compiled without `seg_layers`."""
+        from . import seg
+        state = seg.state_of(self.compiled, "enable_seg")
+        if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 1:
+            raise ValueError(f"enable_seg: chunks must be a positive integer (3, 2 or 1), got {chunks!r}")
+        state.set_sigma(sigma)
+        self._seg_chunks = chunks             # (the state's own `chunks` is set around this wrapper's calls only: _seg_scope)
+
+    def set_seg_sigma(self, sigma: float) -> None:
+        """The blur's sigma for the following calls: an in-place write of the parameter rows the captured graphs read by address."""
+        from . import seg
+        seg.state_of(self.compiled, "set_seg_sigma").set_sigma(sigma)
+
+    def disable_seg(self) -> None:
+        from . import seg
+        seg.state_of(self.compiled, "disable_seg")
+        self._seg_chunks = 0
+
+    def _seg_scope(self, chunks: int, latent_hw):
+        import contextlib
+        state = getattr(self.compiled, "seg", None)
+        return state.using(chunks, latent_hw) if state is not None else contextlib.nullcontext()
+
+    def _apply_seg(self, sample: torch.Tensor) -> None:
+        """Allocate the parameter rows of this call's latent size, outside any capture (the sites only look them up)."""
+        state = getattr(self.compiled, "seg", None)
+        if state is None or not self._seg_chunks or torch.cuda.is_current_stream_capturing():
+            return
+        state.bind((int(sample.shape[-2]), int(sample.shape[-1])), sample.device)
 
     # ---- regional prompts (regions.py): weight buffers the cross-attention sites read by address; the captured graphs stay ----
     def set_regions(self, masks: torch.Tensor, chunks: int = 2) -> None:
@@ -272,8 +309,8 @@ class _HoistedUNet(nn.Module):
         if fn is None:
             ctx = self._ctx[shape]                 # closed over: the graph reads these buffers in place
 
-            def step(sample, timesteps, cond, pag_chunks=0):      # (a plain integer: part of the graph cache's key)
-                with self._pag_scope(pag_chunks):
+            def step(sample, timesteps, cond, pag_chunks=0, seg_chunks=0):      # (plain integers: part of the graph cache's key)
+                with self._pag_scope(pag_chunks), self._seg_scope(seg_chunks, tuple(sample.shape[-2:])):
                     return self.compiled.forward_with_context(sample, timesteps, ctx, cond)[0]
 
             fn = make_dynamic_graphed_callable(step) if self.cuda_graph else step
@@ -296,7 +333,7 @@ class _HoistedUNet(nn.Module):
             from .optimization import recalibrate_fp8
             ctx = self._ctx[shape]
             def run_once():
-                with self._pag_scope(self._pag_chunks):
+                with self._pag_scope(self._pag_chunks), self._seg_scope(self._seg_chunks, tuple(x.shape[-2:])):
                     return self.compiled.forward_with_context(x, timesteps, ctx, cond)
 
             ectx = getattr(self.compiled, "exec_context", None)
@@ -311,6 +348,7 @@ class _HoistedUNet(nn.Module):
         dev = sample.device
         self._apply_regions(sample)
         self._apply_ip_adapter(sample)
+        self._apply_seg(sample)
         self._context_for(ehs)
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor(float(timesteps), dtype=torch.float32)
@@ -322,7 +360,9 @@ class _HoistedUNet(nn.Module):
             self._fp8_restart(x, timesteps, tuple(ehs.shape), cond)
         self._new_prompt = False
         with torch.no_grad():
-            if self._pag_chunks:
+            if self._seg_chunks:
+                out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond, self._pag_chunks, self._seg_chunks)
+            elif self._pag_chunks:
                 out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond, self._pag_chunks)
             else:
                 out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond)
@@ -375,12 +415,14 @@ class DiffusersUNet(_HoistedUNet):
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                                 region_tokens: int = 77, ip_adapter=None) -> DiffusersUNet:
+                                 region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
     `pag_layers=("mid",)` compiles the perturbed-attention sites in (diffusers' `pag_applied_layers`): `enable_pag(chunks)` /
     `disable_pag()` then say which rows of a call are the perturbed ones.
+    `seg_layers=("mid",)` compiles the smoothed-energy sites in (seg.py; not with `pag_layers`): `enable_seg(chunks, sigma)` /
+    `set_seg_sigma(sigma)` / `disable_seg()` drive them.
     `regions=R` compiles regional cross-attention in (regions.py): the pipeline passes R prompts of `region_tokens` tokens
     concatenated along the token axis as `encoder_hidden_states`; `set_regions(masks, chunks)` / `clear_regions()` drive it.
     `ip_adapter=N` (or a tuple of token counts, one per adapter) compiles IP-Adapter image attention in (ip_adapter.py):
@@ -393,17 +435,17 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
-                              ip_adapter=ip_adapter)
+                              ip_adapter=ip_adapter, seg_layers=seg_layers)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                        regions=None, region_tokens: int = 77, ip_adapter=None):
+                        regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
-                                             regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter)
+                                             regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers)
     return pipe
 
 
@@ -424,23 +466,24 @@ class ComfyUNet(_HoistedUNet):
 
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                       region_tokens: int = 77, ip_adapter=None) -> ComfyUNet:
+                       region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
     with regional cross-attention (conditioning masks / "attention couple"): `context` is the R conditionings concatenated along
     the token axis, `set_regions(masks, chunks)` / `clear_regions()` drive it.  `ip_adapter=N`: with IP-Adapter image attention
     (the IPAdapter nodes), driven by `load_ip_adapter` / `set_ip_adapter_image` / `set_ip_adapter_scale` / `set_ip_adapter_masks` /
-    `unload_ip_adapter`."""
+    `unload_ip_adapter`.  `seg_layers=("mid",)`: with smoothed-energy sites (the SEG node); its extra, fully perturbed call is
+    `enable_seg(1, sigma)`."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                              region_tokens=region_tokens, ip_adapter=ip_adapter)
+                              region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                      regions=None, region_tokens: int = 77, ip_adapter=None) -> ComfyUNet:
+                      regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens, ip_adapter)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens, ip_adapter, seg_layers)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -1032,6 +1032,119 @@ def attention_pag(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: 
     return out
 
 
+def _seg_arguments(what: str, q: torch.Tensor, grid_hw, params_row: torch.Tensor):
+    """The checks seg_blur and attention_seg share; returns (h, w)."""
+    try:
+        h, w = (int(s) for s in grid_hw)
+    except (TypeError, ValueError):
+        raise BackendError(f"{what}: grid_hw must be (h, w), got {grid_hw!r}") from None
+    if h < 1 or w < 1 or h * w != q.shape[1]:
+        raise BackendError(f"{what}: the token grid {h} x {w} does not hold T = {q.shape[1]} tokens")
+    if h > _C.SEG_MAX_SIDE or w > _C.SEG_MAX_SIDE:
+        raise BackendError(f"{what}: token grid {h} x {w} is larger than {_C.SEG_MAX_SIDE} x {_C.SEG_MAX_SIDE}")
+    if (not torch.is_tensor(params_row) or params_row.dtype != torch.float32 or params_row.dim() != 1 or not params_row.is_contiguous()
+            or params_row.numel() < _C.SEG_PARAM_WORDS):
+        raise BackendError(f"{what}: params_row must be a contiguous fp32 device row of {_C.SEG_PARAM_WORDS} values [mode, k, taps...] (seg.param_row)")
+    return h, w
+
+
+def _seg_workspace(lib, n: int, h: int, w: int, C: int, dtype: torch.dtype, device):
+    nbytes = lib.st_seg_blur_workspace_bytes(n, h, w, C, _C.dtype_code(dtype))
+    return (torch.empty(nbytes // 4, dtype=torch.float32, device=device) if nbytes else None), nbytes
+
+
+def seg_blur(q: torch.Tensor, grid_hw, params_row: torch.Tensor) -> torch.Tensor:
+    """The query blur of smoothed energy guidance (SEG, csrc/seg.hip): q (n, T = h * w, C), token t = y * w + x, read as C planes of
+    h x w; every plane becomes the separable Gaussian of its reflect-padded self, or its mean, as the DEVICE row `params_row`
+    ([mode, k, taps...]; seg.param_row) says when the kernels run.  q may be a column slice of the fused q|k|v projection (row stride
+    3 C); the result is dense.  fp32 accumulation, an fp32 intermediate between the two passes, one rounding on output."""
+    _C.require_device(q, params_row)
+    lib = _C.load()
+    if q.dim() != 3:
+        raise BackendError("seg_blur expects a (n, T, C) tensor")
+    n, T, Cc = q.shape
+    h, w = _seg_arguments("seg_blur", q, grid_hw, params_row)
+    if q.stride(2) == 1 and q.stride(0) == q.stride(1) * T:
+        q_, ldq = q, q.stride(1)
+    else:
+        q_, ldq = q.contiguous(), Cc
+    out = torch.empty((n, T, Cc), dtype=q.dtype, device=q.device)
+    ws, nbytes = _seg_workspace(lib, n, h, w, Cc, q.dtype, q.device)
+    _C.check(lib.st_seg_blur(q_.data_ptr(), out.data_ptr(), params_row.data_ptr(), n, h, w, Cc, ldq, Cc, _C.dtype_code(q.dtype), _ptr(ws), nbytes,
+                             _C.stream_ptr()), "seg_blur")
+    return out
+
+
+def attention_seg(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float, tail_count: int, grid_hw,
+                  params_row: torch.Tensor) -> torch.Tensor:
+    """`attention` whose last `tail_count` batch entries are perturbed the SEG way (csrc/seg.hip): their queries are blurred over
+    the `grid_hw` token grid (seg_blur) before the attention, with their own unblurred k and v.  The leading entries go through the
+    unmodified attention launch (the bits of `attention` on that sub-batch), the tail is the blur and one more attention launch
+    (the bits of `attention(seg_blur(q_tail), k_tail, v_tail)`); tail_count = 0 is `attention` itself.  Strict mode: both attention
+    launches write their rows of the output's split image."""
+    tail_count = int(tail_count)
+    if tail_count == 0:
+        return attention(q, k, v, num_heads, scale)
+    _C.require_device(q, k, v, params_row)
+    lib = _C.load()
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise BackendError("attention_seg expects (B, T, H*D) tensors")
+    B, T, Cc = q.shape
+    S = k.shape[1]
+    D = Cc // num_heads
+    if not 0 <= tail_count <= B:
+        raise BackendError(f"attention_seg: tail_count {tail_count} outside [0, B = {B}]")
+    if T != S or k.shape != q.shape or v.shape != q.shape:
+        raise BackendError(f"attention_seg: the blurred tail needs self-attention shapes (T == S); got q {tuple(q.shape)}, "
+                           f"k {tuple(k.shape)}, v {tuple(v.shape)}")
+    h, w = _seg_arguments("attention_seg", q, grid_hw, params_row)
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    q_, ldq = tok(q)
+    k_, ldk = tok(k)
+    v_, ldv = tok(v)
+    lead = B - tail_count
+    es = q.element_size()
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    scratch = torch.empty((tail_count, T, Cc), dtype=q.dtype, device=q.device)
+    ws, nbytes = _seg_workspace(lib, tail_count, h, w, Cc, q.dtype, q.device)
+    img = torch.empty((B * T, Cc), dtype=torch.float32, device=q.device) if (EMIT_SPLIT and split_usable(out.dtype, Cc)) else None
+    ki = _image_columns(k_, B * S, ldk) if q.dtype == torch.float32 else None      # strict mode: K / V columns of a producer's split image
+    vi = _image_columns(v_, B * S, ldv) if ki is not None else None
+    code, st = _C.dtype_code(q.dtype), _C.stream_ptr()
+
+    def arm(first_row: int, rows: int):
+        if img is not None:
+            _C.check(lib.st_arm_split_output(img.data_ptr() + 4 * first_row * Cc, rows, Cc), "arm_split_output")
+
+    with _Armed(img):
+        if ki is not None and vi is not None and D == 64:
+            # the split-image attention on both sub-batches (the images' leading rows, then the tail's with the blurred queries)
+            kc, vc = ki[0].shape[1], vi[0].shape[1]
+            kp, vp = ki[0].data_ptr() + 4 * ki[1], vi[0].data_ptr() + 4 * vi[1]
+            if lead > 0:
+                arm(0, lead * T)
+                _C.check(lib.st_attention_split(q_.data_ptr(), kp, vp, out.data_ptr(), lead, T, S, num_heads, D, ldq, kc, vc, Cc, float(scale), st),
+                         "attention_split")
+            _C.check(lib.st_seg_blur(q_.data_ptr() + es * lead * T * ldq, scratch.data_ptr(), params_row.data_ptr(), tail_count, h, w, Cc, ldq, Cc,
+                                     code, _ptr(ws), nbytes, st), "seg_blur")
+            arm(lead * T, tail_count * T)
+            _C.check(lib.st_attention_split(scratch.data_ptr(), kp + 4 * lead * S * kc, vp + 4 * lead * S * vc, out.data_ptr() + es * lead * T * Cc,
+                                            tail_count, T, S, num_heads, D, Cc, kc, vc, Cc, float(scale), st), "attention_split")
+        else:
+            arm(0, B * T)
+            _C.check(lib.st_attention_seg(q_.data_ptr(), k_.data_ptr(), v_.data_ptr(), out.data_ptr(), scratch.data_ptr(), B, T, S, num_heads, D,
+                                          ldq, ldk, ldv, Cc, float(scale), code, tail_count, h, w, params_row.data_ptr(), _ptr(ws), nbytes, st),
+                     "attention_seg")
+    _note_split(out, img, B * T, Cc)
+    return out
+
+
 REGIONS_MAX = 8               # st_attention_regions: segments per launch
 
 

@@ -19,14 +19,14 @@ from . import _C, ops
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_ip_adapter, insert_pag, insert_regions, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_ip_adapter, insert_pag, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
-                    ip_adapter=None) -> fx.GraphModule:
+                    ip_adapter=None, seg_layers=None) -> fx.GraphModule:
     """Pass pipeline.  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
@@ -39,7 +39,11 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     (optimizers/insert_regions.py, regions.py); those sites keep their query projection as a launch of its own.  `ip_adapter=N` or a
     tuple of up to 4 image token counts (addition, off by default, likewise): every cross-attention site adds a decoupled attention
     over the image tokens of each adapter slot under the live scales of `gm.ip_adapter` (optimizers/insert_ip_adapter.py,
-    ip_adapter.py); the same cost per site as regions; not with `regions` or `fp8`."""
+    ip_adapter.py); the same cost per site as regions; not with `regions` or `fp8`.  `seg_layers` (addition, off by default,
+    likewise): regular expressions selecting the self-attention sites whose perturbed batch entries take blurred queries (smoothed
+    energy guidance; optimizers/insert_seg.py, seg.py); the state, `gm.seg`, starts with chunks 0 = ordinary attention; not with
+    `pag_layers` (both claim the perturbed row block, and a site carries one leaf)."""
+    _check_seg_and_pag(seg_layers, pag_layers)
     if regions is not None and fp8:
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
     check_combination(ip_adapter, regions, fp8)
@@ -52,6 +56,8 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     stats["attention"] = fuse_attention(gm)
     if pag_layers is not None:      # directly after: the query projections still carry their module paths
         stats["pag_sites"] = insert_pag(gm, pag_layers)
+    if seg_layers is not None:      # likewise (never both: _check_seg_and_pag)
+        stats["seg_sites"] = insert_seg(gm, seg_layers)
     if regions is not None:         # likewise
         stats["region_sites"] = insert_regions(gm, regions, region_tokens)
     if ip_adapter is not None:      # likewise
@@ -84,13 +90,24 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     return gm
 
 
+def _check_seg_and_pag(seg_layers, pag_layers) -> None:
+    if seg_layers is not None and pag_layers is not None:
+        raise ValueError("seg_layers cannot be combined with pag_layers: smoothed energy guidance and perturbed-attention guidance both "
+                         "claim the perturbed row block of a call, and a self-attention site carries one leaf")
+
+
 def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
     return replace_backend(gm)
 
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
-                   pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None) -> fx.GraphModule:
-    """`ip_adapter=N` (addition; 4: base adapters, 16: plus; a tuple of up to 4 counts for several adapters): IP-Adapter image prompts
+                   pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> fx.GraphModule:
+    """`seg_layers=("mid",)` (addition): smoothed energy guidance (seg.py).  The selected self-attention sites can treat the last
+    B // chunks batch entries of a call as perturbed: their queries are Gaussian-blurred over the latent grid (sigma = infinity: the
+    spatial mean).  `gm.seg.bind(latent_hw, device)` once per latent size, `gm.seg.using(chunks, latent_hw)` around the caller's own
+    calls, `gm.seg.set_sigma(sigma)` in place, no new capture; chunks 0, the initial state, is ordinary attention.  Not with
+    `pag_layers`.
+    `ip_adapter=N` (addition; 4: base adapters, 16: plus; a tuple of up to 4 counts for several adapters): IP-Adapter image prompts
     (ip_adapter.py).  Every cross-attention adds s * Attn(q, K_img, V_img) per adapter slot, in the same launch.  `gm.ip_adapter` -
     `bind(rows, latent_hw, device)` once, then `load(state_dict, slot)`, `set_image(tokens, ...)`, `set_scale(scale, slot)`,
     `set_masks(masks, slot)`, `unload(slot)`, all in place, no new capture; a slot at scale 0 (the state after `bind`) is skipped:
@@ -125,8 +142,9 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     if regions is not None and fp8:
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
     check_combination(ip_adapter, regions, fp8)
+    _check_seg_and_pag(seg_layers, pag_layers)
     gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                         region_tokens=region_tokens, ip_adapter=ip_adapter)
+                         region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()
@@ -154,6 +172,23 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
 
         graphed = make_dynamic_graphed_callable(run_with_chunks, before_replay=gm.exec_context.refresh_derived)
         gm.forward = lambda *args, **kwargs: graphed(*args, _pag_chunks=state.chunks, **kwargs)
+    elif cuda_graph and seg_layers is not None:
+        # likewise: the perturbed range and the call's latent size (the sites' token grids) are host state of the captured launches
+        seg_state, seg_inner = gm.seg, gm.forward
+
+        def run_with_seg(*args, _seg_chunks: int = 0, _seg_latent=None, **kwargs):
+            with seg_state.using(_seg_chunks, _seg_latent):
+                return seg_inner(*args, **kwargs)
+
+        seg_graphed = make_dynamic_graphed_callable(run_with_seg, before_replay=gm.exec_context.refresh_derived)
+
+        def seg_forward(*args, **kwargs):
+            if seg_state.chunks and seg_state.latent_hw is not None:      # rows are allocated outside the capture the cache may start
+                sample = args[0] if args else kwargs["sample"]
+                seg_state.bind(seg_state.latent_hw, sample.device)
+            return seg_graphed(*args, _seg_chunks=seg_state.chunks, _seg_latent=seg_state.latent_hw if seg_state.chunks else None, **kwargs)
+
+        gm.forward = seg_forward
     elif cuda_graph:
         gm.forward = make_dynamic_graphed_callable(gm.forward, before_replay=gm.exec_context.refresh_derived)
     return gm

@@ -14,6 +14,7 @@ from .fuse_groupnorm_stats import fuse_groupnorm_stats
 from .fuse_skip_cat import fuse_skip_cat
 from .insert_freeu import insert_freeu
 from .insert_pag import insert_pag
+from .insert_seg import insert_seg
 from .insert_regions import insert_regions
 from .insert_ip_adapter import insert_ip_adapter
 from .cleanup import dedupe_pure_calls, fuse_token_residual

@@ -43,6 +43,12 @@ latent, and the self-attention sites of a UNet compiled with `pag_layers` return
 the attention).  The update is the `st_pag_*` form of the loop's sampler, which adds pag[i] (e_pos - e_pert) before the rescale; the
 scale is one more device table of n_steps floats, so `set_pag` needs no new capture.
 
+Smoothed energy guidance (`seg_scale`, `seg_sigma`, `set_seg`; seg.py) is the same row layout, scale table and `st_pag_*` update
+with another perturbation: the self-attention sites of a UNet compiled with `seg_layers` blur the perturbed rows' queries over the
+latent grid (two more launches per site than plain attention: the blur and the tail's own attention launch).  sigma lives in device
+parameter rows the blur reads by address, so `set_seg(scale, sigma)` needs no new capture, finite <-> infinity included.  Not
+together with `pag_scale`.
+
 Regional prompts (`set_regions`; regions.py) on a UNet compiled with `regions=R`: the loop is built with `tokens = R * region_tokens`,
 the positive text state is the R prompts concatenated along the token axis, and every cross-attention combines the R per-prompt
 results per latent cell with weights derived from `set_regions(masks)`.  The weights are device buffers the sites read by address:
@@ -74,8 +80,11 @@ class DenoiseLoop:
                  tokens: int = 77, mode: str = "loop", n_time_ids: int = 6,
                  guidance_scale: Optional[Union[float, Sequence[float]]] = None,
                  guidance_rescale: Optional[Union[float, Sequence[float]]] = None,
-                 pag_scale: Optional[Union[float, Sequence[float]]] = None):
+                 pag_scale: Optional[Union[float, Sequence[float]]] = None,
+                 seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf")):
         assert mode in ("loop", "step", "eager")
+        if seg_scale is not None and pag_scale is not None:
+            raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
         if guidance_rescale is not None and guidance_scale is None:
             raise ValueError("guidance_rescale needs guidance_scale")
         # perturbed-attention guidance: the UNet's sites must exist (compiled in), and the loop names the perturbed row block
@@ -85,6 +94,15 @@ class DenoiseLoop:
             from . import pag
             self._pag_state = pag.state_of(unet, "DenoiseLoop(pag_scale=...)")
         self._pag_chunks = 0 if pag_scale is None else (3 if guidance_scale is not None else 2)
+        # smoothed energy guidance: the same perturbed row block under another perturbation (blurred queries); everything below
+        # that speaks of `pag_scale` - rows, conditioning, the scale table, the update launches - serves both
+        self._seg_state, self._seg_chunks = None, 0
+        if seg_scale is not None:
+            from . import seg
+            self._seg_state = seg.state_of(unet, "DenoiseLoop(seg_scale=...)")
+            seg.check_sigma(seg_sigma)
+            self._seg_chunks = 3 if guidance_scale is not None else 2
+            pag_scale = seg_scale
         # regional prompts: the sites are part of the compiled UNet, the text context carries its R prompts side by side
         from . import regions as _regions
         self._regions_state = getattr(unet, "regions", None) if isinstance(getattr(unet, "regions", None), _regions.Regions) else None
@@ -110,6 +128,10 @@ class DenoiseLoop:
         self._ip_state = getattr(unet, "ip_adapter", None) if isinstance(getattr(unet, "ip_adapter", None), _ip.IPAdapter) else None
         if self._ip_state is not None:                     # scale table, mask weights, image K/V of this row count: allocated once, "off"
             self._ip_state.bind(rows, (lh, lw), dev)
+        self._latent_hw = (lh, lw)
+        if self._seg_state is not None:                    # the blur's parameter rows of this latent size: allocated once, outside capture
+            self._seg_state.bind((lh, lw), dev)
+            self._seg_state.set_sigma(seg_sigma)
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
         self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
         self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
@@ -145,7 +167,7 @@ class DenoiseLoop:
         self.pag = None
         if pag_scale is not None:
             self.pag = torch.zeros(n, dtype=torch.float32, device=dev)
-            self.set_pag(pag_scale)
+            self.pag.copy_(self._step_table(pag_scale, "scale", "set_seg" if self._seg_state is not None else "set_pag"))
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -186,9 +208,22 @@ class DenoiseLoop:
         """Perturbed-attention guidance scale per step: a float, or n_steps floats (pag.adaptive_scales gives diffusers' adaptive
         table).  Written into the device table in place: no new capture.  Scale 0 keeps the perturbed rows and gives the value
         the loop would compute without them."""
-        if self.pag is None:
+        if self.pag is None or self._seg_state is not None:
             raise ValueError("set_pag: this loop was built without pag_scale")
         self.pag.copy_(self._step_table(scale, "scale", "set_pag"))
+
+    def set_seg(self, scale: Optional[Union[float, Sequence[float]]] = None, sigma: Optional[float] = None) -> None:
+        """Smoothed energy guidance: the scale per step (a float, or n_steps floats) and / or the blur's sigma (float("inf"): the
+        spatial mean).  Both are in-place writes of device buffers the captured graph reads by address: no new capture.  Scale 0
+        keeps the perturbed rows and gives the value the loop would compute without them.  sigma belongs to the UNet's SEG state:
+        loops that share one compiled UNet share it."""
+        if self._seg_state is None:
+            raise ValueError("set_seg: this loop was built without seg_scale")
+        table = self._step_table(scale, "scale", "set_seg") if scale is not None else None
+        if sigma is not None:
+            self._seg_state.set_sigma(sigma)
+        if table is not None:
+            self.pag.copy_(table)
 
     def set_conditioning(self, encoder_hidden_states, text_embeds, time_ids, negative_encoder_hidden_states=None,
                          negative_text_embeds=None, negative_time_ids=None) -> None:
@@ -465,6 +500,9 @@ class DenoiseLoop:
     def _unet(self, t, time_row=None):
         if self._pag_state is not None:      # the last B rows are the perturbed block, for this loop's own calls only
             with self._pag_state.using(self._pag_chunks):
+                return self._unet_call(t, time_row)
+        if self._seg_state is not None:      # likewise, with the latent size the sites derive their token grids from
+            with self._seg_state.using(self._seg_chunks, self._latent_hw):
                 return self._unet_call(t, time_row)
         return self._unet_call(t, time_row)
 
