@@ -1,4 +1,5 @@
-"""Helpers of the edge tests (tests/test_edge_gate_host.py, tests/test_edges_gpu.py): a per-element float64 gate with a derived
+"""Helpers of the edge tests (tests/test_edge_gate_host.py, tests/test_edges_gpu.py, tests/test_dma_gate_host.py,
+tests/test_dma_edges_gpu.py): a per-element float64 gate with a derived
 budget, NaN-poisoned operands, guarded outputs, and C-ABI callers that write into an output the test owns."""
 import math
 
@@ -14,6 +15,9 @@ import torch.nn.functional as F
 #              adds inside an MFMA need not (they may truncate: twice the error per add), hence 2.
 #  EPI_OPS     the fp32 operations of the longest epilogue behind the sum (bias, row bias, residual, the two of a SiLU / the
 #              product of a GEGLU, dequantisation-free paths have fewer): each adds at most U_ACC * (magnitude so far).
+#              An in-launch K split (gemm_dma.h: splitk_combine) sums its sk fp32 slabs in slice order: sk - 1 more fp32 adds
+#              of partial sums of the same terms, at most 7 for sk <= 8 - inside these 8 (the split launches carry bias and
+#              residual only: two operations of their own; a slice's sum is shorter by what the other slices hold).
 #  ACT_SLOPE   SiLU and GELU have |f'| <= 1.13 (SiLU 1.0998 at x = 2.4, GELU 1.129 at x = 1.41): an error in the
 #              pre-activation grows by at most that.
 # Products of two bf16 / fp16 values are exact in fp32 (16 or 22 significand bits), so the sum is the only inexact step in
@@ -93,15 +97,8 @@ def silu64(x):
     return x / (1.0 + torch.exp(-x))
 
 
-def linear_ref64(x, w, bias, dtype, *, silu=False, geglu=False, residual=None):
-    """(ref64, mag64, extra64) of ops.linear's epilogue order: +bias, SiLU or GEGLU, +residual - float64 on the rounded operands."""
-    xd, wd = r64(x, dtype), r64(w, dtype)
-    K = xd.shape[-1]
-    pre = xd @ wd.T
-    mag = xd.abs() @ wd.abs().T
-    if bias is not None:
-        bd = r64(bias, dtype)
-        pre, mag = pre + bd, mag + bd.abs()
+def _epilogue64(pre, mag, K, dtype, *, silu=False, geglu=False, residual=None):
+    """SiLU or GEGLU, then +residual, on a pre-activation `pre` whose error is bounded by acc_bound(K, mag)."""
     extra = None
     if geglu:
         Fh = pre.shape[-1] // 2
@@ -123,6 +120,94 @@ def linear_ref64(x, w, bias, dtype, *, silu=False, geglu=False, residual=None):
         rd = r64(residual, dtype)
         ref, mag = ref + rd, mag + rd.abs()
     return ref, mag, extra
+
+
+def linear_ref64(x, w, bias, dtype, *, silu=False, geglu=False, residual=None, split_operands=False, products=None):
+    """(ref64, mag64, extra64) of ops.linear's epilogue order: +bias, SiLU or GEGLU, +residual - float64 on the rounded operands.
+    split_operands: the fp32 operands meet the matrix pipe as split images (as_magnitude(split_term(...)) joins mag64);
+    products: (x @ w.T, |x| @ |w|.T) in float64 where the caller keeps them (tests share them between epilogues)."""
+    K = x.shape[-1]
+    if products is None:
+        xd, wd = r64(x, dtype), r64(w, dtype)
+        products = (xd @ wd.T, xd.abs() @ wd.abs().T)
+    pre, mag = products
+    if split_operands:
+        mag = mag + as_magnitude(split_term(mag), K)
+    if bias is not None:
+        bd = r64(bias, dtype)
+        pre, mag = pre + bd, mag + bd.abs()
+    return _epilogue64(pre, mag, K, dtype, silu=silu, geglu=geglu, residual=residual)
+
+
+# ------------------------------------------------------------------------------------------------ the LDS-DMA GEMM's own terms
+# (tests/test_dma_gate_host.py measures every constant below on the fp32 emulation of the kernel's arithmetic; the GPU tests
+#  of tests/test_dma_edges_gpu.py use them as they stand)
+#
+# Split fp32 operands (csrc/split.h, Mma<fsp>): a value x meets the matrix pipe as hi + lo * 2^-11, hi = f16(x),
+# lo = f16((x - hi) * 2^11).  |x - hi| <= 2^-11 |x| is exact in fp32, and its half keeps 11 bits of it: the image is off by
+# at most 2^-22 |x| (normal halves); the kernel multiplies hi.hi + (hi.lo + lo.hi) * 2^-11 and drops lo.lo <= 2^-22 |x w|.
+# So a product is off by at most 3 * 2^-22 |x w|.  The suite states the image's accuracy as "22 significant bits", 2^-21 per
+# operand (tests/test_split_gpu.py, tests/test_ops_gpu.py::test_ln_linear): SPLIT_OPERAND_U, two operands a product,
+# 2 * 2^-21 = 4 * 2^-22 - which covers the dropped lo.lo as well.  The float64 reference multiplies the fp32 values themselves.
+SPLIT_OPERAND_U = 2.0 ** -21
+
+
+def split_term(mag_product64):
+    """Error of a sum of products of split fp32 operands that comes from the 22-bit images: 2 * 2^-21 * sum |x| |w|."""
+    return 2.0 * SPLIT_OPERAND_U * mag_product64
+
+
+def as_magnitude(err64, n_terms):
+    """An absolute error bound as the magnitude that gives it in acc_bound(n_terms, .): errors in front of an activation
+    travel through the epilogue with the accumulation error this way."""
+    return err64 / (ACC_FACTOR * (n_terms + EPI_OPS) * U_ACC)
+
+
+# LayerNorm folded into the GEMM (gemm_dma.h, gemm_args.h: ln_fold): y = fma(rstd, fma(-mean, c, acc), d) with
+#     a1 = sum of the producer's per-tile row sums, a2 = the same of the squares (fp32, fixed order: LnRowSum),
+#     mean = a1 / K,   rstd = rsqrtf(max(a2 / K - mean * mean, 0) + eps).
+# With S = sum_k x w' exact, mu / rho the exact mean / rstd of the row, m1 = sum |x| / K and q = sum x^2 / K:
+#  d_mean  a1 is a K-term fp32 sum in blocks (<= BN columns inside the producer's tile, then the tiles): its worst case is
+#          K U_ACC sum|x|, a bound no data of the tests comes near (rounding errors of both signs add like sqrt(K)).  The
+#          constants are therefore MEASURED on the emulation, in units of U_ACC * m1, and doubled at most (the device
+#          adds in another order): LN_MEAN_ULPS.  The division by K rounds once more: inside it.
+#  d_rstd  var = a2 / K - mean^2 cancels: both terms carry their absolute errors into a difference that is q / var times
+#          smaller.  d_var <= LN_VAR_ULPS * U_ACC * q + 2 |mu| d_mean (a2 / K measured like a1 / K, plus the two roundings of
+#          mean * mean and the subtraction), and rstd = (var + eps)^-1/2 moves by rho / 2 * d_var / (var + eps); rsqrtf itself
+#          is good to 2 ulp = 4 U_ACC on the device (1 ulp in the emulation).
+#  the two FMAs round once each: U_ACC (|S - mu c| rho + |y|), two of the EPI_OPS on the magnitude rho (mag_S + |mu c|) + |d|.
+# Per element the fold adds   rho |c| d_mean + d_rstd |S - mu c|   to the error of acc (rho * acc_bound(K, mag_S)).
+LN_MEAN_ULPS = 2.5        # measured 1.32 (tests/test_dma_gate_host.py::test_emulated_row_statistics prints it): x 2, rounded down
+LN_VAR_ULPS = 8.0         # measured 4.03
+RSQRT_ULPS = 4.0
+
+
+def ln_stat_bounds(x64, eps):
+    """(mu, rho, d_mean, d_rstd) per row of the float64 activations x64 (rows, K): exact statistics and the bounds above."""
+    mu, q, m1 = x64.mean(-1), (x64 * x64).mean(-1), x64.abs().mean(-1)
+    var = (q - mu * mu).clamp_min(0.0)
+    rho = (var + eps).rsqrt()
+    d_mean = LN_MEAN_ULPS * U_ACC * m1
+    d_var = LN_VAR_ULPS * U_ACC * q + 2.0 * mu.abs() * d_mean
+    d_rstd = rho * (0.5 * d_var / (var + eps) + RSQRT_ULPS * U_ACC)
+    return mu, rho, d_mean, d_rstd
+
+
+def ln_linear_ref64(x, wf, c, d, dtype, eps, *, geglu=False, split_operands=False):
+    """(ref64, mag64, extra64) of ops.ln_linear on the operands the kernel sees: x (rows, K) as stored by its producer, the
+    folded weight wf, the fp32 vectors c and d of ops.fold_layer_norm (split operands: c of the weight's image)."""
+    xd, wd = r64(x, dtype), r64(wf, dtype)
+    K = xd.shape[-1]
+    cd, dd = c.double(), d.double()
+    mu, rho, d_mean, d_rstd = (t[:, None] for t in ln_stat_bounds(xd, eps))
+    S, magS = xd @ wd.T, xd.abs() @ wd.abs().T
+    if split_operands:
+        magS = magS + as_magnitude(split_term(magS), K)
+    centred = S - mu * cd
+    pre = rho * centred + dd
+    mag = rho * (magS + mu.abs() * cd.abs()) + dd.abs()
+    mag = mag + as_magnitude(rho * cd.abs() * d_mean + d_rstd * centred.abs(), K)
+    return _epilogue64(pre, mag, K, dtype, geglu=geglu)
 
 
 def conv_ref64(x, w, bias, dtype, stride, pad, ups, rowbias=None, residual=None):
@@ -155,6 +240,74 @@ def linear_cases(dtype):
     return LINEAR_64x64 + (LINEAR_64x64_F32 if dtype == torch.float32 else []) + LINEAR_128x64 + LINEAR_128x128
 
 
+# ---- the LDS-DMA kernel (gemm_dma_kernel: K a whole number of 128-byte K tiles), tests/test_dma_edges_gpu.py ----------------
+# (tile gemm_dispatch takes in bf16 / fp16, (M, K, N)); every shape has a partial last M tile and a partial last N tile, N % 8 == 0.
+# 64 x 320 wins only where M <= 64 leaves every other tile more than one round of 256 blocks: N > 40960.
+DMA_PLAIN = [("64x64", (1, 64, 8)), ("64x64", (70, 64, 200)), ("128x64", (197, 64, 4128)), ("64x128", (259, 64, 4128)),
+             ("128x128", (400, 64, 5128)), ("128x80", (450, 64, 3368)), ("128x160", (771, 64, 4648)), ("256x128", (1027, 64, 4488)),
+             ("128x320", (1539, 64, 4648)), ("64x320", (33, 64, 40968))]
+DMA_GEGLU = [("64x64", (1, 64, 8)), ("64x64", (100, 64, 40)), ("128x64", (71, 64, 4168)), ("64x128", (134, 64, 3088)),
+             ("128x128", (197, 64, 4128)), ("128x160", (400, 64, 4128)), ("256x128", (400, 64, 5128)), ("128x320", (771, 64, 4128)),
+             ("64x320", (33, 64, 20488))]                       # (BN = 80 is not offered to GEGLU)
+# split fp32 operands: no BN = 320, no 256 x 128 - those shapes land on 128 x 128 (64 x 128 for the 64 x 320 one), which the
+# 128 x 128 shape has already: left out
+DMA_F32_TILES = ("64x64", "128x64", "64x128", "128x128", "128x80", "128x160")
+DMA_WIDE_TILES = ("128x160", "128x320", "256x128")
+# K tiles against ring stages (four; 256 x 128 three, 128 x 320 two): 2, 3, 4, 5 K tiles - and the single one of the lists above
+DMA_RING_K = {2: (128, 192, 256, 320), 4: (64, 96, 128, 160)}       # by element size: a K tile is 64 / 32 values
+# K split with slices of unequal length (nk % sk != 0): (sk, tile, shape) in bf16 / fp16 ...
+DMA_UNEVEN_SPLITS = [(2, "64x64", (1, 2752, 4488)), (3, "128x64", (71, 4160, 3448)), (3, "64x128", (71, 4160, 4168)),
+                     (3, "128x128", (197, 4160, 4248)), (4, "64x64", (1, 1088, 8)), (4, "128x80", (71, 4160, 3408)),
+                     (6, "64x64", (1, 2112, 928)), (6, "128x80", (71, 4160, 2248)), (8, "64x64", (1, 2112, 8))]
+# ... and what the same shapes take as split fp32 operands (K tiles of 32: nk = 86, 130, 34, 66 - every split uneven again)
+DMA_UNEVEN_SPLITS_F32 = [(6, "64x128", (1, 2752, 4488)), (8, "128x128", (71, 4160, 3448)), (4, "128x80", (71, 4160, 4168)),
+                         (3, "128x128", (197, 4160, 4248)), (8, "64x64", (1, 1088, 8)), (8, "128x128", (71, 4160, 3408)),
+                         (8, "64x64", (1, 2112, 928)), (6, "128x80", (71, 4160, 2248)), (8, "64x64", (1, 2112, 8))]
+DMA_LN_K = (128, 640)
+# row statistics: the buffer holds 64 N tiles (ops.STATS_MAX_CHUNKS), so the 128 x 64 shape above (65 tiles) and the 64 x 320
+# one (129) cannot emit them; 128 x 64 has a shape of its own, 64 x 320 is out of the buffer's reach at any N that selects it
+DMA_STATS = [(t, (257, 64, 3272) if t == "128x64" else s) for t, s in DMA_PLAIN if t != "64x320"]
+# eight-phase kernel (whole tiles only): the smallest M x N that gemm8p_applies accepts and the model prices under the small
+# tiles (which need more than 256 of their largest tiles before they lose), at two and at five K tiles
+GEMM8P = [("256x256", (768, 128, 11008)), ("256x256", (768, 320, 11008)), ("256x160", (5632, 128, 1440)), ("256x160", (5632, 320, 1440))]
+GEMM8P_F32 = [("256x160", (768, 64, 6880)), ("256x160", (768, 160, 6880))]
+
+
+def dma_plain(dtype):
+    return [(t, s) for t, s in DMA_PLAIN if dtype != torch.float32 or t in DMA_F32_TILES]
+
+
+def dma_geglu(dtype):
+    return [(t, s) for t, s in DMA_GEGLU if dtype != torch.float32 or t in DMA_F32_TILES]
+
+
+def dma_ring(dtype):
+    """The plain shape of every tile at 2, 3, 4 and 5 K tiles."""
+    return [(t, (M, k, N)) for t, (M, _, N) in dma_plain(dtype) if M > 1 for k in DMA_RING_K[4 if dtype == torch.float32 else 2]]
+
+
+def dma_wide(dtype):
+    return [(t, s) for t, s in dma_plain(dtype) if t in DMA_WIDE_TILES]
+
+
+def dma_splits(dtype):
+    return DMA_UNEVEN_SPLITS_F32 if dtype == torch.float32 else DMA_UNEVEN_SPLITS
+
+
+def dma_ln(dtype):
+    """(tile, shape, geglu): the plain and the GEGLU shape of every tile at K = 128 and 640."""
+    return [(t, (M, k, N), g) for g, lst in ((False, dma_plain(dtype)), (True, dma_geglu(dtype))) for t, (M, _, N) in lst
+            if M > 1 for k in DMA_LN_K]
+
+
+def dma_stats(dtype):
+    return [(t, s) for t, s in DMA_STATS if dtype != torch.float32 or t in DMA_F32_TILES]
+
+
+def gemm8p(dtype):
+    return GEMM8P_F32 if dtype == torch.float32 else GEMM8P
+
+
 # (N, Cin, H, W, Cout, k, stride, pad, upsample)
 THIN_CONVS = [(1, 8, 9, 7, 32, 1, 1, 0, False), (2, 32, 16, 16, 64, 1, 1, 0, False), (1, 48, 5, 5, 16, 1, 2, 0, False),
               (1, 3, 9, 7, 32, 3, 1, 1, False), (1, 7, 8, 8, 16, 3, 2, 1, False), (1, 6, 5, 7, 48, 3, 1, 1, True),
@@ -170,6 +323,17 @@ def normal(name: str, shape, scale: float = 1.0) -> torch.Tensor:
     """Seeded N(0, scale^2) values (CPU, fp32); the name picks the stream."""
     g = torch.Generator().manual_seed(int.from_bytes(name.encode(), "little") % (2 ** 63 - 1))
     return torch.randn(*shape, generator=g) * scale
+
+
+def dma_operands(M, K, rows):
+    """(x, w, bias) of an LDS-DMA case: pre-activations of about unit variance, so that |gate| stays under ACT_RANGE among millions."""
+    return normal(f"d.x{M}.{K}", (M, K)), normal(f"d.w{rows}.{K}", (rows, K), K ** -0.5), normal(f"d.b{rows}", (rows,), 0.5)
+
+
+def dma_ln_operands(M, K, rows):
+    """(x, gamma, beta, w, bias) of a LayerNorm-fold case: rows with a non-zero mean (0.4 against a deviation of 1.7)."""
+    return (normal(f"d.lx{M}.{K}", (M, K)) * 1.7 + 0.4, normal(f"d.g{K}", (K,), 0.2) + 1.0, normal(f"d.be{K}", (K,), 0.2),
+            normal(f"d.lw{rows}.{K}", (rows, K), K ** -0.5), normal(f"d.lb{rows}", (rows,), 0.5))
 
 
 # ------------------------------------------------------------------------------------------------ poisoned operands, guarded outputs
@@ -234,7 +398,9 @@ def linear_into(out, x, w, bias=None, *, silu=False, geglu=False, residual=None)
     K = x.shape[-1]
     N = w.shape[0] // 2 if geglu else w.shape[0]
     assert w.is_contiguous() and out.is_contiguous() and out.numel() == M * N and out.dtype == x.dtype == w.dtype
-    assert not ops.split_usable(x.dtype, K), "the split-operand path keeps its images in ops.linear"
+    code = _C.dtype_code(x.dtype)
+    if ops.split_usable(x.dtype, K):            # strict mode: split images of both operands, as ops.linear
+        x2, lda, w, code = ops._split_of(x2, M, K, lda), K, ops._split_weight(w)[0], _C.ST_F32S
     epi = (_C.EPI_BIAS if bias is not None else 0) | (_C.EPI_SILU if silu else 0) | (_C.EPI_GEGLU if geglu else 0)
     ldr = 0
     if residual is not None:
@@ -242,7 +408,7 @@ def linear_into(out, x, w, bias=None, *, silu=False, geglu=False, residual=None)
         epi |= _C.EPI_RESIDUAL
     gws = ops._gemm_workspace(x.device)
     _C.check(_C.load().st_linear(x2.data_ptr(), w.data_ptr(), ops._ptr(bias), ops._ptr(residual), None, out.data_ptr(), M, N, K,
-                                 lda, N, ldr, 0, epi, _C.dtype_code(x.dtype), gws.data_ptr(), gws.numel(), None, 0, None, None, 0, None,
+                                 lda, N, ldr, 0, epi, code, gws.data_ptr(), gws.numel(), None, 0, None, None, 0, None,
                                  None, 0, _C.stream_ptr()), "linear")
     return out
 
