@@ -482,3 +482,246 @@ def geglu_into(out, state, gate):
     _C.check(_C.load().st_geglu(state.data_ptr(), gate.data_ptr(), out.data_ptr(), rows, Fh, state.stride(0), gate.stride(0), Fh,
                                 _C.dtype_code(state.dtype), _C.stream_ptr()), "geglu")
     return out
+
+
+def attention_split_into(out, q, k_img, v_img, num_heads, scale):
+    """st_attention_split of fp32 (B, T, H*64) q and the split images of K and V ((B*S, H*64) float32-typed tensors of
+    ops.split_rows) into the dense `out`."""
+    _C, ops = _ops()
+    B, T, Cc = q.shape
+    S = k_img.shape[0] // B
+    assert q.dtype == torch.float32 and q.stride(2) == 1 and q.stride(0) == q.stride(1) * T
+    assert k_img.is_contiguous() and v_img.is_contiguous() and k_img.shape == v_img.shape == (B * S, Cc)
+    assert out.is_contiguous() and tuple(out.shape) == (B, T, Cc)
+    _C.check(_C.load().st_attention_split(q.data_ptr(), k_img.data_ptr(), v_img.data_ptr(), out.data_ptr(), B, T, S, num_heads,
+                                          Cc // num_heads, q.stride(1), Cc, Cc, Cc, float(scale), _C.stream_ptr()), "attention_split")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ attention: reference, budget, cases
+# (tests/test_attention_gate_host.py proves the gate on a CPU emulation of the kernels' arithmetic and measures the two
+#  constants that cannot be derived; tests/test_attention_edges_gpu.py applies it to every attention kernel)
+#
+# What the kernels are documented to compute (csrc/attention_core.h, attention.hip, attention_anyd.hip, attention_f32.hip):
+#     q' = round_E(fp32(q) * c),  c = fp32(scale) * fp32(log2 e) in fp32   (fp32 tensors: q' = the fp32 product, then split)
+#     s_k = q' . k_k (fp32 accumulation, started at -m_ref),   P_k = round_E(2^(s_k - m_ref)),   out = round(sum P_k v_k / sum P_k)
+# The reference is that in float64 WITH the documented rounding of q' (it is the design, not an error), a base-2 softmax p, and
+# ref = sum p_k v_k, mag = sum p_k |v_k|.  Every error of a P_k that is RELATIVE (P_k = p_k (1 + e_k), |e_k| <= e) enters the
+# numerator and - the row sum comes from the same P through the ones block - the denominator alike:
+#     out' - ref = sum e_k p_k (v_k - ref) / (1 + sum e_k p_k),     |out' - ref| <= e * sum p_k |v_k - ref|  (/ (1 - e)).
+# sum p_k |v_k - ref| is at most mag + |ref| (the plain first-order form) and, by Cauchy-Schwarz, at most the softmax-weighted
+# deviation sd = sqrt(sum p_k v_k^2 - ref^2), which one more product gives: W = min(mag + |ref|, sd) is the weight of every
+# relative term.  (The lazy maximum keeps P <= 2^ATT_LAG, a shift of the exponent: no relative bound changes.)  The terms:
+#  store       U_OUT |ref|                                       one rounding of fp32 -> E at the store
+#  P rounding  u_P W, u_P = U_OUT[E]; fp32 tensors: SPLIT_OPERAND_U (P is split in registers: a 22-bit image)
+#  scores      an fp32 sum of D exact products from -m_ref: acc_bound(D, smag) with smag = max_k sum_d |q'_d k_kd| + |m| + ATT_LAG
+#              (m: the row's true maximum; the reference maximum lags it by at most ATT_LAG; the subtraction of delta when
+#              it moves is one of the EPI_OPS).  An absolute error d of a base-2 exponent is a relative error ln 2 * d of P.
+#              fp32 tensors: plus the images of q' and K, ATT_SPLIT_MULT * split_term(max_k sum |q' k|), the same way.
+#  v_exp_f32   ATT_EXP2_ULPS * 2^-23 W                           (measured, below)
+#  O sum       numerator and denominator are fp32 sums of S products each, exact in fp32 for 16-bit operands:
+#              acc_bound(S, mag + |ref|) - the existing form 2 (n + 8) 2^-24 on the magnitude of both; its eight extra
+#              operations hold the rescales by alpha (each a rounding of O and of the row sum, and alpha's own exp2 error on
+#              everything summed so far), 1 / l and the product with it.
+#              fp32 tensors: plus the images of P and V in the products, ATT_SPLIT_MULT * split_term(mag + |ref|).
+#  subnormal P (fp16) a P under 2^-14 rounds with an ABSOLUTE error of 2^-25, not a relative one.  The row sum is at least 1 in
+#              the units of m_ref (the key that set m_ref has P = 1, and a key that moves it again has P = 1 afterwards), so
+#              every such key moves the output by at most 2^-25 (|v_k| + |ref|): 2^-25 (sum_k |v_k| + S |ref|).  The lo half
+#              of a split P under 2^-14 is off by 2^-36 in the same way (csrc/split.h); bf16 has fp32's exponent range.
+ATT_LAG = 6.0
+ATT_SUBNORMAL_P = {torch.bfloat16: 0.0, torch.float16: 2.0 ** -25, torch.float32: 2.0 ** -36}
+# The two constants measured on the CPU emulation against float64 (tests/test_attention_gate_host.py::test_measured_constants
+# prints them and holds them to "covers the measured value, at most twice it"), never against GPU output:
+#  ATT_EXP2_ULPS    error of the fp32 exp2 at the emulation's own arguments, in ulp (2^-23 relative): measured 0.58; x 2 = 1.16,
+#                   rounded down to the 1 ulp the instruction set documents for v_exp_f32
+#  ATT_SPLIT_MULT   what the split images of q', K, P and V move an fp32 output by, as a multiple of the worst-case terms
+#                   above (emulation with split operands against the same emulation on the fp32 values): measured 0.454 x 2, rounded down
+ATT_EXP2_ULPS = 1.0
+ATT_SPLIT_MULT = 0.9
+ATT_SPOT_GAINS = (0.35, 1.0, 2.0)
+ATT_SPOT_MIN_P = 0.05
+
+
+def attention_prescale(q, scale, dtype):
+    """q' = round_E(fp32(q) * c), c = fp32(scale) * fp32(log2 e) rounded to fp32 - the B operand of every score MFMA."""
+    c = torch.tensor(float(scale), dtype=torch.float32) * torch.tensor(1.4426950408889634, dtype=torch.float32)
+    return (q.to(dtype).float() * c).to(dtype)
+
+
+def att_heads(t, H):
+    """(B, N, H*D) -> (B, H, N, D)"""
+    B, N, C = t.shape
+    return t.reshape(B, N, H, C // H).transpose(1, 2)
+
+
+def att_tokens(t):
+    """(B, H, N, D) -> (B, N, H*D)"""
+    B, H, N, D = t.shape
+    return t.transpose(1, 2).reshape(B, N, H * D)
+
+
+class AttentionRef:
+    """The float64 reference of one attention problem in the (B, T, H*D) layout of the output, and what its budget needs."""
+
+    def __init__(self, q, k, v, H, scale, dtype):
+        qs = att_heads(attention_prescale(q, scale, dtype).double(), H)
+        kd, vd = att_heads(r64(k, dtype), H), att_heads(r64(v, dtype), H)
+        self.dtype, self.S, self.D = dtype, k.shape[1], q.shape[2] // H
+        s = qs @ kd.transpose(-1, -2)
+        m = s.max(-1, keepdim=True).values
+        p = torch.exp2(s - m)
+        p = p / p.sum(-1, keepdim=True)
+        ref, mag = p @ vd, p @ vd.abs()
+        sd = (p @ (vd * vd) - ref * ref).clamp_min(0.0).sqrt()
+        self.p = p                                                   # (B, H, T, S): the spotlight condition reads it
+        self.ref, self.mag = att_tokens(ref), att_tokens(mag)
+        self.weight = torch.minimum(self.mag + self.ref.abs(), att_tokens(sd))                  # W
+        qk = (qs.abs() @ kd.abs().transpose(-1, -2)).max(-1, keepdim=True).values           # (B, H, T, 1)
+        self.qk = att_tokens(qk.expand(-1, -1, -1, self.D))
+        self.smag = self.qk + att_tokens((m.abs() + ATT_LAG).expand(-1, -1, -1, self.D))
+        self.vsum = att_tokens(vd.abs().sum(-2, keepdim=True).expand(-1, -1, q.shape[1], -1))
+
+    def relative(self):
+        """e: the bound on the relative error of a P_k, per output element."""
+        f32 = self.dtype == torch.float32
+        e = (SPLIT_OPERAND_U if f32 else U_OUT[self.dtype]) + ATT_EXP2_ULPS * 2.0 ** -23 + math.log(2.0) * acc_bound(self.D, self.smag)
+        if f32:
+            e = e + math.log(2.0) * ATT_SPLIT_MULT * split_term(self.qk)
+        return e
+
+    def extra(self):
+        """Everything beyond U_OUT |ref| + acc_bound(S, mag + |ref|): the `extra64` of assert_elementwise."""
+        e = self.relative()
+        x = e / (1.0 - e) * self.weight + ATT_SUBNORMAL_P[self.dtype] * (self.vsum + self.S * self.ref.abs())
+        if self.dtype == torch.float32:
+            x = x + ATT_SPLIT_MULT * split_term(self.mag + self.ref.abs())
+        return x
+
+    def gate(self, out, what):
+        """assert_elementwise on every element; returns the worst ratio to the budget."""
+        return assert_elementwise(out, self.ref, self.mag + self.ref.abs(), self.S, self.dtype, what, self.extra())
+
+    def ratio(self, out):
+        return gate_ratio(out, self.ref, self.mag + self.ref.abs(), self.S, self.dtype, self.extra())[0]
+
+
+# ---- input families ------------------------------------------------------------------------------------------------------------
+def att_spot_keys(S):
+    """The keys the spotlight family must light: every key of the last two key tiles, the first and the last key of every tile."""
+    nkt = (S + 63) // 64
+    keys = set(range(max(0, (nkt - 2) * 64), S))
+    for t in range(nkt):
+        keys |= {t * 64, min(S, t * 64 + 64) - 1}
+    return sorted(keys)
+
+
+def att_spot_pairs(B, T, S, H):
+    """[(b, h, row, key, gain)]: the row's gain cycles through ATT_SPOT_GAINS.  The two upper gains give their key most of the
+    row whatever S is; 0.35 (four base-2 units: under the lag, the reference maximum stays) gives it 2^4 / (1.6 S + 2^4), under
+    ATT_SPOT_MIN_P from S = 200 on.  So every required key goes to a row of the upper gains - one row each while a head has
+    rows enough, else some rows carry two keys at the same gain and share the row - and the 0.35 rows take the keys that are
+    not required, or (short S, where every key is required and 0.35 suffices) required ones again in another head."""
+    need = att_spot_keys(S)
+    other = [c for c in range(S) if c not in set(need)]
+    strong = [r for r in range(T) if r % 3 != 0]
+    weak = [r for r in range(T) if r % 3 == 0]
+    if not strong:                                   # T = 1
+        strong, weak = weak, []
+    heads = B * H
+    per_head = min(len(need), max(len(strong), -(-len(need) // heads)))
+    pairs = []
+    for n in range(heads):
+        b, h = divmod(n, H)
+        mine = [need[(n * per_head + i) % len(need)] for i in range(per_head)]
+        pairs += [(b, h, strong[i % len(strong)], c, ATT_SPOT_GAINS[strong[i % len(strong)] % 3]) for i, c in enumerate(mine)]
+        pool = other if other else [c for c in need if c not in set(mine)]
+        pairs += [(b, h, r, pool[(n * len(weak) + i) % len(pool)], ATT_SPOT_GAINS[0]) for i, r in enumerate(weak[:len(pool)])]
+    return pairs
+
+
+def attention_inputs(family, B, T, S, H, D):
+    """(q, k, v) of a family, fp32 on the CPU, (B, T | S, H*D); and the spotlight pairs (None elsewhere)."""
+    C = H * D
+    q, k, v = normal(f"a.q{B}.{T}.{C}", (B, T, C)), normal(f"a.k{B}.{S}.{C}", (B, S, C)), normal(f"a.v{B}.{S}.{C}", (B, S, C))
+    amp = (64.0 / D) ** 0.5                           # the same score scale at every head size (scale = D^-0.5)
+    pairs = None
+    if family == "spotlight":
+        pairs = att_spot_pairs(B, T, S, H)
+        b, h, row, key = (torch.tensor([p[i] for p in pairs]) for i in range(4))
+        g = torch.tensor([p[4] for p in pairs], dtype=torch.float32)[:, None]
+        k4, q4 = k.view(B, S, H, D), q.view(B, T, H, D)            # (a key is lit once per head: no index repeats)
+        k4[b, key, h] = 0.3 * k4[b, key, h] + g * amp * q4[b, row, h]
+    elif family == "negative":
+        u = normal(f"a.u{C}", (C,)) * amp ** 0.5
+        q, k = u + 0.5 * q, -0.6 * u + 0.5 * k
+    else:
+        assert family == "normal"
+    return q, k, v, pairs
+
+
+def assert_spotlight_condition(ref: AttentionRef, pairs, S, H):
+    """From the reference: every required key holds at least ATT_SPOT_MIN_P of some row that lights it, in tile 0 and in the
+    last tile among them; returns the smallest of those probabilities."""
+    b, h, row, key = (torch.tensor([p[i] for p in pairs]) for i in range(4))
+    best = {}
+    for c, pr in zip(key.tolist(), ref.p[b, h, row, key].tolist()):
+        best[c] = max(best.get(c, 0.0), pr)
+    need = att_spot_keys(S)
+    low = {c: best.get(c, 0.0) for c in need if best.get(c, 0.0) < ATT_SPOT_MIN_P}
+    assert not low, f"spotlight keys under {ATT_SPOT_MIN_P} of every row that lights them: {low}"
+    assert 0 in best and S - 1 in best
+    return min(best[c] for c in need)
+
+
+# ---- which kernel a shape takes (attention.hip: attention16_launch, st_attention; attention_f32.hip; attention_anyd.hip) ----------
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def attention_kernel(dtype, B, T, S, H, D):
+    """(kernel, template arguments after the element type, grid) st_attention launches - the host's selection rule restated."""
+    if D != 64:
+        return "attn_anyd_kernel", (D, 4), (_cdiv(T, 64), H, B)
+    if dtype == torch.float32:
+        return "attn_split_kernel", (4, False), (_cdiv(T, 64) * H * B, 1, 1)
+    if S < 256:
+        return "attn16v2_kernel", (4, 1), (_cdiv(T, 64), H, B)
+    nw = 4 if _cdiv(T, 256) * H * B <= 128 else 7
+    if nw == 4 and _cdiv(T, 128) * H * B <= 176 and _cdiv(T, 96) * H * B <= 256:
+        nw = 3
+    if nw == 7:
+        r7, r8 = _cdiv(_cdiv(T, 224) * H * B, 256), _cdiv(_cdiv(T, 256) * H * B, 256)
+        if 6 * r8 < 5 * r7:
+            nw = 8
+    return "attn32i_kernel", (nw, nw != 8), (_cdiv(T, 32 * nw) * H * B, 1, 1)
+
+
+# ---- the cases: (kernel tag, (B, T, S, H, D), family) -------------------------------------------------------------------------------
+ATT_FAMILIES = ("normal", "spotlight", "negative")
+ATT_HALF = (torch.bfloat16, torch.float16)
+
+
+def _att_cases(tag, B, T, H, D, sizes, all_families):
+    return [(tag, (B, T, S, H, D), f) for S in sizes for f in ATT_FAMILIES if f == "normal" or S in all_families]
+
+
+# 16-row kernel: a second block with one live row; 1, 2, 3 and 4 key tiles against the ring of three, tails of 1, 13, 17 and 63
+ATT_16V2 = _att_cases("attn16v2", 1, 65, 2, 64, (1, 17, 64, 65, 77, 128, 129, 192, 255), (77, 255))
+# 32-row kernel: 4 to 13 key tiles (the six-slot ring wraps once from 385, twice at 769), tails on both sides of 32
+ATT_32I_3 = _att_cases("attn32i-3", 1, 97, 1, 64, (256, 257, 288, 289, 319, 320, 321, 384, 385, 449, 769), (257, 289, 449))
+ATT_32I_4 = _att_cases("attn32i-4", 1, 193, 90, 64, (257, 321, 449), (321,))            # cdiv(193, 128) * 90 = 180 > 176
+ATT_32I_7 = _att_cases("attn32i-7", 1, 257, 65, 64, (257, 321, 449), (449,))            # 130 blocks of 256 rows > 128; the second: 33 live rows
+ATT_32I_8 = _att_cases("attn32i-8", 1, 255, 130, 64, (256, 257, 289, 385, 769), (769,))    # r7 = 2, r8 = 1
+ATT_16BIT = ATT_16V2 + ATT_32I_3 + ATT_32I_4 + ATT_32I_7 + ATT_32I_8
+ATT_EXPECTED = {"attn16v2": ("attn16v2_kernel", (4, 1)), "attn32i-3": ("attn32i_kernel", (3, True)), "attn32i-4": ("attn32i_kernel", (4, True)),
+                "attn32i-7": ("attn32i_kernel", (7, True)), "attn32i-8": ("attn32i_kernel", (8, False)),
+                "anyd16": ("attn_anyd_kernel", (16, 4)), "anyd32": ("attn_anyd_kernel", (32, 4)), "anyd128": ("attn_anyd_kernel", (128, 4)),
+                "split": ("attn_split_kernel", (4, False))}
+# other head sizes (bf16, fp16, fp32): one LDS buffer, 1, 2 and 3 key tiles, tails of 1 and 63; every family at 65 and 129
+ATT_ANYD = [c for D in (16, 32, 128) for c in _att_cases(f"anyd{D}", 2, 33, 3, D, (1, 63, 64, 65, 129), (65, 129))]
+# fp32 at head size 64: two LDS buffers, 1 to 4 key tiles; st_attention and, on split images of K and V, st_attention_split
+ATT_F32 = _att_cases("split", 1, 65, 2, 64, (1, 63, 64, 65, 128, 129, 193), (65, 193))
+
+
+def attention_cases(dtype):
+    return ATT_ANYD + (ATT_F32 if dtype == torch.float32 else ATT_16BIT)
