@@ -1,5 +1,5 @@
 """Helpers of the edge tests (tests/test_edge_gate_host.py, tests/test_edges_gpu.py, tests/test_dma_gate_host.py,
-tests/test_dma_edges_gpu.py): a per-element float64 gate with a derived
+tests/test_dma_edges_gpu.py, tests/test_conv_gate_host.py, tests/test_conv_edges_gpu.py): a per-element float64 gate with a derived
 budget, NaN-poisoned operands, guarded outputs, and C-ABI callers that write into an output the test owns."""
 import math
 
@@ -725,3 +725,385 @@ ATT_F32 = _att_cases("split", 1, 65, 2, 64, (1, 63, 64, 65, 128, 129, 193), (65,
 
 def attention_cases(dtype):
     return ATT_ANYD + (ATT_F32 if dtype == torch.float32 else ATT_16BIT)
+
+
+# ------------------------------------------------------------------------------------------------ the conv family: dispatch restated, cases, operands
+# (tests/test_conv_gate_host.py proves the gate on a CPU emulation of both conv loops; tests/test_conv_edges_gpu.py applies it.)
+# The label of every case below - kernel, tile, K split - is COMPUTED by the restatements of the host's selection rules that
+# follow (csrc/conv_halo.h: conv_halo_applies, conv_halo_launch; csrc/dispatch.h: gemm_dispatch) and asserted against the
+# lists on the CPU; on the GPU, ColStats.rows (the tile's BM) is the piece of it a test can observe.
+CONV_WORKSPACE_BYTES = 192 << 20          # ops.GEMM_WORKSPACE_BYTES: what a K split may use (the GPU tests assert the two agree)
+
+
+def conv_geometry(cfg):
+    """(Ho, Wo, M, K) of a case (N, Cin, H, W, Cout, k, stride, pad, ups)."""
+    N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+    He, We = (2 * H, 2 * W) if ups else (H, W)
+    Ho, Wo = (He + 2 * pad - k) // stride + 1, (We + 2 * pad - k) // stride + 1
+    return Ho, Wo, N * Ho * Wo, k * k * Cin
+
+
+def conv_halo_applies(dtype, cfg):
+    """csrc/conv_halo.h: conv_halo_applies (kb: 64 channels a slice in 16 bit, 32 as split fp32)."""
+    N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+    Ho, Wo, M, _ = conv_geometry(cfg)
+    kb = 32 if dtype == torch.float32 else 64
+    if k != 3 or stride != 1 or pad != 1 or Cin % kb or Cout % 4 or Cout < 64:
+        return False
+    if ups:
+        return Wo in (64, 128) and Ho % (256 // Wo) == 0 and M % 256 == 0
+    if W not in (32, 64, 128) and not (W == 16 and kb == 64):
+        return False
+    bm = 128 if W == 128 else 256
+    return H % (bm // W) == 0 and M % bm == 0
+
+
+def conv_halo_plan(dtype, cfg, workspace_bytes=CONV_WORKSPACE_BYTES):
+    """conv_halo_launch restated: (label, BM, BN, sk, tiles).  The K split is the time model's choice:
+        rounds of 256 blocks x (tap trips per slice x trip_us + fixed_us) + per slice 1.2 us and its fp32 slab at ~4 TB/s,
+    a slice keeps at least two channel slices, at most 8 slices (16 where the launch has at most 16 tiles); a later candidate
+    must win by more than 0.5 us."""
+    N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+    Ho, Wo, M, _ = conv_geometry(cfg)
+    sp = dtype == torch.float32
+    sp128 = sp and Cout % 128 == 0 and Wo <= 64
+    bm = 128 if (not ups and W == 128) else 256
+    bn = (128 if sp128 else 64) if sp else (160 if (ups or W == 128) else 128)
+    if not sp and not ups and W == 128:
+        cost = lambda w: _cdiv((M // bm) * _cdiv(Cout, w), 256) * w
+        if cost(128) < cost(160):
+            bn = 128
+    tiles = (M // bm) * _cdiv(Cout, bn)
+    ncs = Cin // (32 if sp else 64)
+    sk = 1
+    if tiles <= 16384:
+        trip_us, fixed_us = (0.75 if sp else 0.77) * bn / 128.0, (10.0 if sp else 5.4)
+        slab_us = 2.0 * tiles * bm * bn * 4.0 / 4.0e6
+        trips, cap = ncs * 9, (16 if tiles <= 16 else 8)
+        max_sk = min(ncs // 2, cap)
+        best = 1e30
+        for s in range(1, max(max_sk, 1) + 1):
+            if s > 1 and s * tiles * bm * bn * 4 + 65536 > workspace_bytes:
+                break
+            rounds = (tiles * s + 255) // 256
+            t = rounds * (trips / float(s) * trip_us + fixed_us) + (s * (1.2 + slab_us) if s > 1 else 0.0)
+            if t < best - 0.5:
+                best, sk = t, s
+    wl2 = Wo.bit_length() - 1
+    label = f"halo<{wl2},{bm // Wo},{bn}{',ups' if ups else ''}>/sk{sk}"
+    return label, bm, bn, sk, tiles
+
+
+# gemm_dispatch's candidate list (tile, BM, BN, microseconds per K trip); a conv prices every trip at 1.6 x
+IGEMM_CANDS = [("128x128", 128, 128, 0.53), ("64x128", 64, 128, 0.34), ("128x64", 128, 64, 0.32), ("64x64", 64, 64, 0.19),
+               ("128x320", 128, 320, 1.9), ("64x320", 64, 320, 1.1), ("256x128", 256, 128, 0.72), ("128x80", 128, 80, 0.37),
+               ("128x160", 128, 160, 0.66)]
+IGEMM_SKS = (1, 2, 3, 4, 6, 8)
+
+
+def conv_igemm_plan(dtype, cfg, workspace_bytes=CONV_WORKSPACE_BYTES, plain_f32=False):
+    """gemm_dispatch<T, CONV = true> restated: (label, BM, BN, sk, tiles).  plain_f32: fp32 operands that are not split images
+    (one configuration: 64 x 64, no K split)."""
+    _, _, M, K = conv_geometry(cfg)
+    Nc = cfg[4]
+    if plain_f32:
+        return "igemm<64x64,f32>/sk1", 64, 64, 1, _cdiv(M, 64) * _cdiv(Nc, 64)
+    sp = dtype == torch.float32
+    nk = K // (32 if sp else 64)
+    best, pick = 1e30, None
+    for name, bm, bn, trip_us in IGEMM_CANDS:
+        if sp and (bn == 320 or name == "256x128"):
+            continue
+        nt = _cdiv(M, bm) * _cdiv(Nc, bn)
+        trip = (0.8 if (sp and name == "128x160") else trip_us) * 1.6
+        for s in IGEMM_SKS:
+            if s > 1 and (nk // s < 4 or nt > 16384):
+                break
+            slab_mb = float(s) * nt * bm * bn * 4.0 / 1e6
+            if s > 1 and slab_mb * 1e6 + 65536 > workspace_bytes:
+                break
+            rounds = float((nt * s + 255) // 256)
+            trip_bw = float(min(nt * s, 256)) * (bm + bn) * 128.0 / 14.0e6
+            cost = rounds * (_cdiv(nk, s) * max(trip, trip_bw) + 3.0) * (1.3 if rounds > 1.0 else 1.0) + \
+                (2.1 + 0.4 * slab_mb if s > 1 else 0.0)
+            if cost < best:
+                best, pick = cost, (name, bm, bn, s, nt)
+    name, bm, bn, s, nt = pick
+    return f"igemm<{name}>/sk{s}", bm, bn, s, nt
+
+
+def conv_plan(dtype, cfg, plain_f32=False):
+    """Where ops.conv2d sends a case: the thin kernel, the halo conv or the implicit GEMM - (label, BM, BN, sk, tiles)."""
+    N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+    if plain_f32:
+        assert dtype == torch.float32 and Cin % 32 == 0
+        return conv_igemm_plan(dtype, cfg, plain_f32=True)
+    if Cin % (32 if dtype == torch.float32 else 64):
+        return "thin", 0, 0, 1, 0
+    if conv_halo_applies(dtype, cfg):
+        return conv_halo_plan(dtype, cfg)
+    return conv_igemm_plan(dtype, cfg)
+
+
+# ---- the cases: (label in bf16 / fp16, label as split fp32 or None, (N, Cin, H, W, Cout, k, stride, pad, ups)) ------------------
+# Cin is the 16-bit one; the fp32 case has the same number of channel slices (a slice is 64 channels in 16 bit, 32 as split
+# fp32: half the Cin - conv_cases does that).  label = kernel<template arguments>/sk<K slices>:
+#   halo<WL2,TH,BN[,ups]>  conv_halo_kernel<T, WL2, TH, BN, 4, 2, UPS>: rows of 2^WL2 pixels, TH rows and BN channels a tile
+#   igemm<BMxBN>           gemm_dma_kernel<T, BM, BN, ..., CONV = true>
+# Smallest shapes that reach the path, about 2048 output pixels at most - two exceptions, both forced by the selection rule:
+# the 160-channel halo tile at W = 128 without upsampling is only taken where 128-channel tiles need a second round of 256
+# blocks and 160-channel tiles do not (43 rows x 644 channels: 258 against 215 tiles), and an implicit-GEMM tile other than
+# 64 x 64 wins only once the 64 x 64 tiles fill more than a round (a 1x1 conv with thousands of output channels: cheap).
+def _c3(n, cin, h, w, co, ups=False):
+    return (n, cin, h, w, co, 3, 1, 1, ups)
+
+
+def _c1(n, cin, h, w, co):
+    return (n, cin, h, w, co, 1, 1, 0, False)
+
+
+# halo conv, 16 bit, Cin = 128 (two slices: the patch double buffer and the weight ring's wrap), H > TH (a tile with an image
+# row above and below it), a ragged last channel tile; W = 64 also H = TH with two images; W = 128 also H = 3 and 2
+CONV_HALO_16 = [("halo<4,16,128>/sk1", None, _c3(2, 128, 32, 16, 136)), ("halo<5,8,128>/sk1", None, _c3(2, 128, 16, 32, 136)),
+                ("halo<6,4,128>/sk1", None, _c3(1, 128, 8, 64, 136)), ("halo<6,4,128>/sk1", None, _c3(2, 128, 4, 64, 72)),
+                ("halo<7,1,128>/sk1", None, _c3(1, 128, 3, 128, 136)), ("halo<7,1,128>/sk1", None, _c3(1, 128, 2, 128, 64)),
+                ("halo<7,1,160>/sk1", None, _c3(1, 128, 43, 128, 644)),
+                ("halo<6,4,160,ups>/sk1", None, _c3(1, 128, 4, 32, 168, True)), ("halo<7,2,160,ups>/sk1", None, _c3(1, 128, 2, 64, 168, True))]
+# halo conv, split fp32 (listed with the 16-bit Cin = 128: 64 channels, two slices): the 64-channel tile, the 128-channel one
+# (Cout % 128 == 0, Wout <= 64), the W = 128 form (always 64 channels), both upsampling forms
+CONV_HALO_32 = [(None, "halo<5,8,64>/sk1", _c3(1, 128, 16, 32, 72)), (None, "halo<5,8,128>/sk1", _c3(1, 128, 16, 32, 128)),
+                (None, "halo<6,4,64>/sk1", _c3(1, 128, 8, 64, 72)), (None, "halo<6,4,128>/sk1", _c3(2, 128, 4, 64, 128)),
+                (None, "halo<7,1,64>/sk1", _c3(1, 128, 3, 128, 72)), (None, "halo<7,1,64>/sk1", _c3(1, 128, 2, 128, 128)),
+                (None, "halo<6,4,64,ups>/sk1", _c3(1, 128, 4, 32, 72, True)), (None, "halo<6,4,128,ups>/sk1", _c3(1, 128, 4, 32, 128, True)),
+                (None, "halo<7,2,64,ups>/sk1", _c3(1, 128, 2, 64, 72, True))]
+# halo K split over channel slices: 4 slices in 2, 6 in 3, 5 in 2 and 7 in 3 (ncs % sk != 0: the first slices are longer), 20 in 9
+# (cap = 16 at no more than 16 tiles; 20 % 9 = 2).  The 16-pixel level exists in 16 bit only: split fp32 takes 8 x 32 there.
+CONV_HALO_SPLITS = [("halo<5,8,128>/sk2", "halo<5,8,128>/sk2", _c3(1, 256, 16, 32, 128)), ("halo<5,8,128>/sk3", "halo<5,8,128>/sk3", _c3(1, 384, 16, 32, 128)),
+                    ("halo<6,4,128>/sk2", "halo<6,4,64>/sk2", _c3(1, 320, 8, 64, 72)), ("halo<5,8,128>/sk3", "halo<5,8,128>/sk3", _c3(1, 448, 16, 32, 128)),
+                    ("halo<4,16,128>/sk9", None, _c3(1, 1280, 16, 16, 128)), (None, "halo<5,8,128>/sk9", _c3(1, 1280, 8, 32, 128))]
+# implicit GEMM, every tile of gemm_dispatch's candidate list by a 1x1 conv with ragged M and ragged N (one K tile).  Split fp32
+# is offered neither BN = 320 nor 256 x 128 (dispatch.h): those shapes land on the tiles named.  Every candidate is reachable.
+CONV_IGEMM_TILES = [("igemm<64x64>/sk1", "igemm<64x64>/sk1", _c1(1, 64, 1, 70, 200)), ("igemm<64x128>/sk1", "igemm<64x128>/sk1", _c1(1, 64, 1, 33, 16392)),
+                    ("igemm<128x64>/sk1", "igemm<128x64>/sk1", _c1(1, 64, 1, 70, 8200)), ("igemm<128x80>/sk1", "igemm<128x80>/sk1", _c1(1, 64, 1, 70, 16392)),
+                    ("igemm<128x128>/sk1", "igemm<128x128>/sk1", _c1(1, 64, 1, 70, 20488)), ("igemm<128x160>/sk1", "igemm<128x160>/sk1", _c1(1, 64, 1, 70, 32776)),
+                    ("igemm<256x128>/sk1", "igemm<64x128>/sk1", _c1(1, 64, 1, 134, 20488)), ("igemm<128x320>/sk1", "igemm<128x160>/sk1", _c1(1, 64, 1, 134, 32776)),
+                    ("igemm<64x320>/sk1", "igemm<64x128>/sk1", _c1(1, 64, 1, 33, 40968))]
+# implicit GEMM geometry: 3x3 at W = 12 and 24 (the UNet's levels at latent 96 x 64), stride 2 at an even and an odd size, 1x1
+# at stride 2, pad 0, upsampling at an odd size, two images of 63 pixels (one M tile holds both: the row bias and img = mm / hw)
+# - on 64 x 64 tiles (two K tiles a tap; the model splits K in four: 18 K tiles as 5 + 5 + 4 + 4, every boundary inside a tap)
+# and again, with one K tile a tap, on the 128- and 64-row tiles a wide Cout selects; two images of 195 pixels on 128 x 160
+# (the second M tile straddles them); 128 and 64 pixels an image (whole tiles: the launches that can emit column partials)
+CONV_IGEMM_GEOM = [("igemm<64x64>/sk4", "igemm<64x64>/sk4", _c3(1, 128, 12, 12, 72)), ("igemm<64x64>/sk4", "igemm<64x64>/sk4", _c3(1, 128, 24, 24, 72)),
+                   ("igemm<64x64>/sk4", "igemm<64x64>/sk4", (1, 128, 16, 12, 72, 3, 2, 1, False)), ("igemm<64x64>/sk4", "igemm<64x64>/sk4", (1, 128, 15, 13, 72, 3, 2, 1, False)),
+                   ("igemm<64x64>/sk1", "igemm<64x64>/sk1", (1, 128, 9, 7, 72, 1, 2, 0, False)), ("igemm<64x64>/sk4", "igemm<64x64>/sk4", (1, 128, 9, 7, 72, 3, 1, 0, False)),
+                   ("igemm<64x64>/sk4", "igemm<64x64>/sk4", _c3(1, 128, 5, 7, 72, True)), ("igemm<64x64>/sk4", "igemm<64x64>/sk4", _c3(2, 128, 9, 7, 72)),
+                   ("igemm<128x64>/sk1", "igemm<128x64>/sk1", _c3(2, 64, 9, 7, 8200)), ("igemm<128x160>/sk1", "igemm<128x160>/sk1", _c3(2, 64, 15, 13, 8200)),
+                   ("igemm<128x128>/sk1", "igemm<128x128>/sk1", _c3(2, 64, 9, 7, 20488)), ("igemm<64x64>/sk1", "igemm<64x64>/sk1", (1, 64, 16, 12, 8200, 3, 2, 1, False)),
+                   ("igemm<64x128>/sk1", "igemm<64x128>/sk1", (1, 64, 15, 13, 16392, 3, 2, 1, False)), ("igemm<64x128>/sk1", "igemm<64x128>/sk1", _c3(1, 64, 5, 7, 8200, True)),
+                   ("igemm<128x64>/sk1", "igemm<128x64>/sk1", _c3(1, 64, 16, 8, 8200)), ("igemm<64x64>/sk1", "igemm<64x64>/sk1", _c3(2, 64, 8, 8, 200))]
+# implicit GEMM K splits with nk % sk != 0: 2 (27 K tiles: 14 + 13, the boundary inside a tap), 3 (a 3x3 conv has nk % 9 == 0, so
+# thirds are whole taps: the uneven split in three is a 1x1 conv's, 13 K tiles as 5 + 4 + 4), 4, 6 and 8 on 64 x 64 tiles (18, 27,
+# 36 K tiles: boundaries inside taps); on the production tiles 128 x 80 in 8, 6 and 4 (45, 45, 54 K tiles) and 128 x 64 in 4
+# (63 K tiles: 16 + 16 + 16 + 15, two images of 575 pixels: the fifth M tile straddles them); stride 2 in four slices.
+# (The model splits 256 x 128 only from 2304 pixels x 1280 channels on, and 128 x 128 in 16 bit not below that either: left out.)
+CONV_IGEMM_SPLITS = [("igemm<64x64>/sk2", "igemm<64x64>/sk2", _c3(1, 192, 48, 48, 136)), ("igemm<64x64>/sk3", "igemm<64x64>/sk3", _c1(1, 832, 9, 7, 8)),
+                     ("igemm<64x64>/sk4", "igemm<64x64>/sk4", _c3(1, 128, 5, 7, 8)), ("igemm<64x64>/sk6", "igemm<64x64>/sk6", _c3(1, 192, 5, 7, 8)),
+                     ("igemm<64x64>/sk8", "igemm<64x64>/sk8", _c3(1, 256, 5, 7, 8)), ("igemm<128x80>/sk8", "igemm<128x80>/sk8", _c3(1, 320, 48, 48, 72)),
+                     ("igemm<128x80>/sk6", "igemm<128x80>/sk6", _c3(1, 320, 48, 48, 136)), ("igemm<128x80>/sk4", "igemm<128x80>/sk4", _c3(1, 384, 48, 48, 200)),
+                     ("igemm<128x64>/sk4", "igemm<128x64>/sk4", _c3(2, 448, 25, 23, 328)), ("igemm<64x64>/sk4", "igemm<64x64>/sk4", (1, 128, 48, 24, 320, 3, 2, 1, False))]
+# conv2d_cat (1x1 over [x0 | x1], never materialised): (label, label, cfg with Cin = C0 + C1, C0) - C0 != C1; Csplit inside the K
+# range of one launch, inside the second slice of a split in three (13 K tiles as 5 + 4 + 4, Csplit after 6) and of a split in
+# four (19 as 5 + 5 + 5 + 4, Csplit after 7); on a 128-row tile.  Bit-equal to conv2d(torch.cat(...)).
+CONV_CAT = [("igemm<64x64>/sk1", "igemm<64x64>/sk1", _c1(2, 192, 9, 7, 72), 64), ("igemm<64x64>/sk3", "igemm<64x64>/sk3", _c1(2, 832, 9, 7, 8), 384),
+            ("igemm<64x64>/sk4", "igemm<64x64>/sk4", _c1(2, 1216, 9, 7, 72), 448), ("igemm<128x64>/sk1", "igemm<128x64>/sk1", _c1(1, 192, 1, 70, 8200), 128)]
+# plain fp32 operands on the exact fp32 MFMA (gemm_dma_kernel<float, 64, 64, ..., CONV>, the 64 x 64 path): ops.conv2d takes it
+# for an fp32 weight that is NOT channels_last (its split image is not made).  A conv with Cin % 32 != 0 that is not thin
+# (k * k * Cin > 64) reaches no kernel: st_conv2d rejects it.  (cfg with the fp32 Cin itself.)
+CONV_PLAIN_F32 = [("igemm<64x64,f32>/sk1", _c3(2, 64, 9, 7, 72)), ("igemm<64x64,f32>/sk1", (1, 32, 15, 13, 72, 3, 2, 1, False)),
+                  ("igemm<64x64,f32>/sk1", _c3(1, 32, 5, 7, 72, True)), ("igemm<64x64,f32>/sk1", _c3(1, 64, 8, 32, 64))]
+CONV_GROUPS = {"halo": CONV_HALO_16 + CONV_HALO_32, "halo-k-split": CONV_HALO_SPLITS, "igemm-tiles": CONV_IGEMM_TILES,
+               "igemm-geometry": CONV_IGEMM_GEOM, "igemm-k-split": CONV_IGEMM_SPLITS}
+
+
+def conv_cfg_for(dtype, cfg):
+    """The listed (16-bit) case with the same number of channel slices in `dtype`."""
+    return cfg if dtype != torch.float32 else (cfg[0], cfg[1] // 2) + tuple(cfg[2:])
+
+
+def conv_cases(dtype, group):
+    """[(label, cfg)] of a group in `dtype`."""
+    i = 1 if dtype == torch.float32 else 0
+    return [(c[i], conv_cfg_for(dtype, c[2])) for c in CONV_GROUPS[group] if c[i] is not None]
+
+
+def conv_cat_cases(dtype):
+    """[(label, cfg, C0)]"""
+    i, div = (1, 2) if dtype == torch.float32 else (0, 1)
+    return [(c[i], conv_cfg_for(dtype, c[2]), c[3] // div) for c in CONV_CAT]
+
+
+def label_bm(label):
+    """Rows of a tile (ColStats.rows) from a label: halo<WL2,TH,..> is TH << WL2, igemm<BMxBN> is BM."""
+    args = label[label.index("<") + 1:label.index(">")].split(",")
+    return (int(args[1]) << int(args[0])) if label.startswith("halo") else int(args[0].split("x")[0])
+
+
+def label_sk(label):
+    return int(label.rsplit("/sk", 1)[1])
+
+
+# ---- two operand families -------------------------------------------------------------------------------------------------------------
+# "normal": seeded normal operands, gated with the constants above at n_terms = k * k * Cin + max(0, sk - 8) (EPI_OPS holds up to
+#     seven slab adds); split fp32 adds split_term.
+# "exact": activations from {-1, 0, 1}, weights / bias / row bias / residual multiples of 1/8 below 2.  Every product is a
+#     multiple of 1/8 and every partial sum - in any order, every K-split slab - is exact in fp32 while sum |terms| < 2^24 / 8
+#     (asserted on the reference); the split image of such a value has an empty low half.  The budget is the store rounding
+#     alone, U_OUT |ref| (fp32: equality), so ONE dropped or doubled term (at least 1/8) shows wherever U_OUT |ref| < 1/16 -
+#     asserted for 99 % of the elements.  bf16 needs |ref| < 16 there: weights have variance 1.25, so a sum of n terms (and bias,
+#     row bias, residual) deviates by 1.12 sqrt(n + 3); CONV_EXACT_TERMS[bf16] = 16 non-zero terms an output - a density of
+#     16 / K - puts 16 at 3.3 deviations (0.1 % of the elements beyond it, which leaves room for the neighbours of the spots
+#     below).  fp16 (|ref| < 128) and fp32 (no store rounding) take 400: 22 a deviation - and the column partials stay exact
+#     too (colstats_ratios: 256 squares of mean 1.25 * 403 sum to half of 2^18).
+CONV_EXACT_TERMS = {torch.bfloat16: 16, torch.float16: 400, torch.float32: 400}
+CONV_FAMILIES = ("normal", "exact")
+
+
+def _eighths(name, shape):
+    g = torch.Generator().manual_seed(int.from_bytes(name.encode(), "little") % (2 ** 63 - 1))
+    return torch.randint(-15, 16, shape, generator=g).float() / 8
+
+
+def conv_operands(cfg, family, dtype):
+    """(x, w, bias, rowbias, residual) of a case on the CPU in fp32 (the exact family's density depends on the type)."""
+    N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+    Ho, Wo, M, K = conv_geometry(cfg)
+    tag = "-".join(str(int(v)) for v in cfg)
+    if family == "normal":
+        return (normal(f"c.x{tag}", (N, Cin, H, W)), normal(f"c.w{tag}", (Cout, Cin, k, k), K ** -0.5), normal(f"c.b{tag}", (Cout,)),
+                normal(f"c.rb{tag}", (N, Cout)), normal(f"c.r{tag}", (N, Cout, Ho, Wo)))
+    assert family == "exact"
+    density = min(1.0, CONV_EXACT_TERMS[dtype] / K)
+    g = torch.Generator().manual_seed(int.from_bytes(f"c.e{tag}".encode(), "little") % (2 ** 63 - 1))
+    x = (torch.rand(N, Cin, H, W, generator=g) < density).float() * (torch.randint(0, 2, (N, Cin, H, W), generator=g).float() * 2 - 1)
+    w, b = _eighths(f"c.ew{tag}", (Cout, Cin, k, k)), _eighths(f"c.eb{tag}", (Cout,))
+    _exact_spots(x, w, b, cfg, dtype)
+    return x, w, b, _eighths(f"c.erb{tag}", (N, Cout)), _eighths(f"c.er{tag}", (N, Cout, Ho, Wo))
+
+
+# Below 32 (bf16) / 256 (fp16) every multiple of 1/8 is a value of the type, and up to twice that the others are ties: the exact
+# family alone never makes a store round, so a store that rounds WRONGLY (towards zero) would pass it.  Two "spots" per case
+# give it values that do round: the activations under one output element (n, co, oy, ox) are cleared and then set, one by one,
+# to the sign of the weight they meet, until conv + bias lands in [64, 96) / [512, 768) on a value 3/8 above a multiple of 1/2
+# in magnitude - there the type's spacing is 1/2, rounding to nearest errs by 1/8 and truncation by 3/8 > U_OUT |ref|.  Only
+# where the output has 256 pixels (512 with upsampling: a spot's neighbours - 9 or 16 pixels whose sums gain up to 680 terms -
+# stay inside the 1 % that may exceed 1/16 of store rounding; ConvCase asserts it) and the element has terms enough; fp32
+# has no store rounding.
+CONV_SPOT_RANGE = {torch.bfloat16: (64.0, 96.0), torch.float16: (512.0, 768.0)}
+
+
+def _exact_spots(x, w, b, cfg, dtype):
+    N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+    Ho, Wo, M, K = conv_geometry(cfg)
+    if dtype not in CONV_SPOT_RANGE or M < (512 if ups else 256):
+        return 0
+    lo, hi = CONV_SPOT_RANGE[dtype]
+    made = 0
+    for j in range(1 if (ups or M < 512) else 2):          # (few pixels, or upsampling's wider footprint: one spot's neighbours are enough)
+        n, oy, ox, co = (N - 1) * j, (Ho // 3 + 5 * j) % Ho, (Wo // 2 + 7 * j) % Wo, (3 + 11 * j) % Cout
+        weff = {}                                             # input pixel -> the weights it meets (upsampling: several taps share a pixel)
+        for r in range(k):
+            for s in range(k):
+                iy, ix = oy * stride - pad + r, ox * stride - pad + s
+                if not (0 <= iy < (2 * H if ups else H) and 0 <= ix < (2 * W if ups else W)):
+                    continue
+                key = (iy >> 1, ix >> 1) if ups else (iy, ix)
+                weff[key] = weff.get(key, 0) + w[co, :, r, s]
+        for (iy, ix) in weff:
+            x[n, :, iy, ix] = 0.0
+        v, done = float(b[co]), False
+        for (iy, ix), wv in weff.items():
+            for c in range(Cin):
+                if float(wv[c]) == 0.0:
+                    continue
+                x[n, c, iy, ix] = 1.0 if float(wv[c]) > 0 else -1.0
+                v += abs(float(wv[c]))
+                if lo <= v < hi and (v * 8) % 4 == 3:
+                    done = True
+                    break
+            if done:
+                break
+        if done:
+            made += 1
+        else:                                                 # not enough terms under this element: leave no half-made spot
+            for (iy, ix) in weff:
+                x[n, :, iy, ix] = 0.0
+    return made
+
+
+class ConvCase:
+    """Operands and float64 reference of one conv case, type and family: `expect(epi)` gives (ref64, mag64, n_terms) of the plain
+    (+bias) launch ("bias") and of the one with row bias and residual ("full"; conv2d_cat has no row bias: "res")."""
+
+    def __init__(self, cfg, dtype, family, sk=1, split_operands=None):
+        self.cfg, self.dtype, self.family, self.sk = cfg, dtype, family, sk
+        N, Cin, H, W, Cout, k, stride, pad, ups = cfg
+        self.x, self.w, self.b, self.rb, self.res = conv_operands(cfg, family, dtype)
+        self.K = k * k * Cin
+        self.split = (dtype == torch.float32) if split_operands is None else split_operands
+        self.prod, self.magprod = conv_ref64(self.x, self.w, None, dtype, stride, pad, ups)
+        if family == "exact":
+            full_mag = self.magprod + r64(self.b, dtype).abs()[None, :, None, None] + r64(self.rb, dtype).abs()[:, :, None, None] + r64(self.res, dtype).abs()
+            assert float(full_mag.max()) < 2.0 ** 24 / 8, f"conv {cfg} {dtype}: exact-sum operands are not exact (sum |terms| {float(full_mag.max())})"
+            for t in (self.x, self.w, self.b, self.rb, self.res):
+                assert torch.equal(t.to(dtype).float(), t) and torch.equal(t * 8, (t * 8).round())
+
+    def expect(self, epi):
+        d = self.dtype
+        ref, mag = self.prod + r64(self.b, d)[None, :, None, None], self.magprod + r64(self.b, d).abs()[None, :, None, None]
+        if epi == "full":
+            ref, mag = ref + r64(self.rb, d)[:, :, None, None], mag + r64(self.rb, d).abs()[:, :, None, None]
+        if epi in ("full", "res"):
+            ref, mag = ref + r64(self.res, d), mag + r64(self.res, d).abs()
+        n_terms = self.K + max(0, self.sk - 8)
+        if self.family == "exact":
+            blind = float((U_OUT[d] * ref.abs() >= 1.0 / 16).double().mean())
+            assert blind <= 0.01, f"conv {self.cfg} {d} {epi}: {blind:.3%} of the outputs could hide a one-term error (store rounding >= 1/16)"
+            return ref, torch.zeros_like(ref), n_terms
+        if self.split:
+            mag = mag + as_magnitude(split_term(self.magprod), n_terms)
+        return ref, mag, n_terms
+
+    def gate(self, out, epi, what):
+        ref, mag, n_terms = self.expect(epi)
+        return assert_elementwise(out, ref, mag, n_terms, self.dtype, what)
+
+
+def colstats_ratios(buf, rows, stored, bm, exact, what):
+    """Column partials (tiles, C, 2) of a launch against float64 sums of the STORED output over each tile's `rows` rows: the sums
+    inside 2 (BM + 8) 2^-24 sum |stored| (BM fp32 adds in two levels, each at most twice a rounding, the slot adds among the 8),
+    the squares the same on sum stored^2 (the fma rounds once per term); exact operands: equality (squares of multiples of 1/8 are multiples
+    of 1/64: their sums are exact in fp32 below 2^18, asserted; a 16-bit store keeps a multiple of 1/8 one).  Returns the two
+    worst ratios."""
+    assert rows == bm, f"{what}: column partials over {rows} rows a tile, the case is labelled {bm}"
+    o = stored.detach().double().cpu().permute(0, 2, 3, 1)
+    C = o.shape[-1]
+    o = o.reshape(-1, C)
+    M = o.shape[0]
+    assert M % rows == 0
+    o = o.view(M // rows, rows, C)
+    s = buf.detach().double().cpu()[:M // rows]
+    assert tuple(s.shape) == (M // rows, C, 2) and torch.isfinite(s).all(), f"{what}: a column partial is not finite"
+    s1, s2 = o.sum(1), (o * o).sum(1)
+    k = 2.0 * (rows + 8) * U_ACC
+    b1, b2 = k * o.abs().sum(1), k * s2
+    if exact:          # equality wherever the fp32 sums are exact: every column but the few that hold a spot, which keep the bound
+        small = (s2 < 2.0 ** 18) & (o.abs().sum(1) < 2.0 ** 21)
+        assert int((~small).sum()) <= 2, f"{what}: the partials of these operands are not exact in fp32"
+        bad = ((s[..., 0] != s1) | (s[..., 1] != s2)) & small
+        assert not bool(bad.any()), f"{what}: column partials of exact operands are not exact ({int(bad.sum())} of {bad.numel()})"
+        assert bool(((s[..., 0] - s1).abs() <= b1).all()) and bool(((s[..., 1] - s2).abs() <= b2).all()), f"{what}: column partials over their budget"
+        return 0.0, 0.0
+    r1 = float(((s[..., 0] - s1).abs() / b1.clamp_min(1e-300)).max())
+    r2 = float(((s[..., 1] - s2).abs() / b2.clamp_min(1e-300)).max())
+    assert r1 <= 1.0 and r2 <= 1.0, f"{what}: column partials {r1:.3g} (sums) / {r2:.3g} (squares) x their budget"
+    return r1, r2

@@ -102,7 +102,7 @@ def test_emulated_activation_epilogues_pass(dtype):
 def test_emulated_conv_passes_at_every_gpu_shape(dtype):
     halo = [(n, c, h, w, co, 3, 1, 1, False) for (n, c, h, w, co) in eu.HALO_CONVS] + \
            [(n, c, h, w, co, 3, 1, 1, True) for (n, c, h, w, co) in eu.HALO_CONVS_UPS]
-    for cfg in eu.THIN_CONVS + (halo + eu.IGEMM_CONVS if dtype == torch.float32 else []):      # (the GPU tests gate the Cin = 64 cases in fp32 only)
+    for cfg in eu.THIN_CONVS + halo + eu.IGEMM_CONVS:      # (Cin = 64: 576 terms, gated in every type)
         N, Cin, H, W, Cout, k, stride, pad, ups = cfg
         x, w, b = _conv_operands(cfg)
         ref, mag = eu.conv_ref64(x, w, b, dtype, stride, pad, ups)
@@ -142,7 +142,7 @@ def test_linear_rounding_mutations_fail_at_short_k(dtype, mutation, shape):
 
 
 _PAD_CASES = [(d, c) for d in eu.DTYPES for c in [(1, 3, 9, 7, 32, 3, 1, 1, False), (1, 7, 8, 8, 16, 3, 2, 1, False), (1, 4, 5, 7, 32, 3, 1, 1, True)]] + \
-             [(torch.float32, (1, 64, 3, 128, 160, 3, 1, 1, False))]      # (the Cin = 64 cases use the gate in fp32 only: n_terms = 576)
+             [(d, (1, 64, 3, 128, 160, 3, 1, 1, False)) for d in eu.DTYPES]      # (Cin = 64: n_terms = 576)
 
 
 @pytest.mark.parametrize("dtype,cfg", _PAD_CASES, ids=lambda v: _name(v) if isinstance(v, torch.dtype) else "-".join(str(int(e)) for e in v))
