@@ -1,5 +1,6 @@
 """Helpers of the edge tests (tests/test_edge_gate_host.py, tests/test_edges_gpu.py, tests/test_dma_gate_host.py,
-tests/test_dma_edges_gpu.py, tests/test_conv_gate_host.py, tests/test_conv_edges_gpu.py): a per-element float64 gate with a derived
+tests/test_dma_edges_gpu.py, tests/test_conv_gate_host.py, tests/test_conv_edges_gpu.py, tests/test_fp8_gate_host.py,
+tests/test_fp8_edges_gpu.py): a per-element float64 gate with a derived
 budget, NaN-poisoned operands, guarded outputs, and C-ABI callers that write into an output the test owns."""
 import math
 
@@ -122,11 +123,12 @@ def _epilogue64(pre, mag, K, dtype, *, silu=False, geglu=False, residual=None):
     return ref, mag, extra
 
 
-def linear_ref64(x, w, bias, dtype, *, silu=False, geglu=False, residual=None, split_operands=False, products=None):
+def linear_ref64(x, w, bias, dtype, *, silu=False, geglu=False, residual=None, split_operands=False, products=None, K=None):
     """(ref64, mag64, extra64) of ops.linear's epilogue order: +bias, SiLU or GEGLU, +residual - float64 on the rounded operands.
     split_operands: the fp32 operands meet the matrix pipe as split images (as_magnitude(split_term(...)) joins mag64);
-    products: (x @ w.T, |x| @ |w|.T) in float64 where the caller keeps them (tests share them between epilogues)."""
-    K = x.shape[-1]
+    products: (x @ w.T, |x| @ |w|.T) in float64 where the caller keeps them (tests share them between epilogues; with K given,
+    x and w are not needed at all: the fp8 gate's products are those of bytes and scales)."""
+    K = x.shape[-1] if K is None else K
     if products is None:
         xd, wd = r64(x, dtype), r64(w, dtype)
         products = (xd @ wd.T, xd.abs() @ wd.abs().T)
@@ -193,14 +195,19 @@ def ln_stat_bounds(x64, eps):
     return mu, rho, d_mean, d_rstd
 
 
-def ln_linear_ref64(x, wf, c, d, dtype, eps, *, geglu=False, split_operands=False):
+def ln_linear_ref64(x, wf, c, d, dtype, eps, *, geglu=False, split_operands=False, products=None):
     """(ref64, mag64, extra64) of ops.ln_linear on the operands the kernel sees: x (rows, K) as stored by its producer, the
-    folded weight wf, the fp32 vectors c and d of ops.fold_layer_norm (split operands: c of the weight's image)."""
-    xd, wd = r64(x, dtype), r64(wf, dtype)
+    folded weight wf, the fp32 vectors c and d of ops.fold_layer_norm (split operands: c of the weight's image).
+    products: (S, |S| term by term) in float64 where the product is not x @ wf.T - the fp8 GEMM takes the row statistics from
+    the 16-bit tensor x and multiplies its dequantised e4m3 copy (wf is then unused)."""
+    xd = r64(x, dtype)
     K = xd.shape[-1]
     cd, dd = c.double(), d.double()
     mu, rho, d_mean, d_rstd = (t[:, None] for t in ln_stat_bounds(xd, eps))
-    S, magS = xd @ wd.T, xd.abs() @ wd.abs().T
+    if products is None:
+        wd = r64(wf, dtype)
+        products = (xd @ wd.T, xd.abs() @ wd.abs().T)
+    S, magS = products
     if split_operands:
         magS = magS + as_magnitude(split_term(magS), K)
     centred = S - mu * cd
@@ -339,10 +346,16 @@ def dma_ln_operands(M, K, rows):
 # ------------------------------------------------------------------------------------------------ poisoned operands, guarded outputs
 PAD = 64          # elements on each side: a multiple of 8, so the view keeps the buffer's 16-byte alignment in every dtype
 ROW_GAP = 8       # NaN elements between the rows of a 2-D / 3-D activation (16 bytes in 16-bit types, 32 in fp32)
+E4M3_NAN = 0x7F   # the poison of uint8 tensors (e4m3 bytes): the NaN of OCP e4m3; a product with it is NaN
+ROW_GAP_U8 = 16   # between rows of e4m3 bytes (st_linear_fp8 wants row strides that are multiples of 16)
+
+
+def _poison(dtype):
+    return E4M3_NAN if dtype == torch.uint8 else math.nan
 
 
 def poisoned(t: torch.Tensor, pad: int = PAD, row_gap: int = 0) -> torch.Tensor:
-    """`t`'s values as a view inside a larger NaN-filled buffer: a read before the tensor, behind it or (row_gap > 0: rows of the
+    """`t`'s values as a view inside a larger NaN-filled buffer (uint8: filled with the e4m3 NaN byte): a read before the tensor, behind it or (row_gap > 0: rows of the
     last dimension at stride shape[-1] + row_gap) between its rows returns NaN, and a NaN that leaks into a result shows.
     Memory order is t's own (contiguous or channels_last); weights take row_gap = 0 and stay contiguous inside the buffer."""
     assert pad % 8 == 0 and row_gap % 8 == 0
@@ -350,23 +363,25 @@ def poisoned(t: torch.Tensor, pad: int = PAD, row_gap: int = 0) -> torch.Tensor:
         assert t.dim() in (2, 3) and t.is_contiguous()
         K = t.shape[-1]
         rows = t.numel() // K
-        buf = torch.full((2 * pad + rows * (K + row_gap),), math.nan, dtype=t.dtype, device=t.device)
+        buf = torch.full((2 * pad + rows * (K + row_gap),), _poison(t.dtype), dtype=t.dtype, device=t.device)
         v = buf[pad:pad + rows * (K + row_gap)].view(rows, K + row_gap)[:, :K]
         v.copy_(t.reshape(rows, K))
         if t.dim() == 3:
             v = v.as_strided(t.shape, (t.shape[1] * (K + row_gap), K + row_gap, 1), v.storage_offset())
         return v
-    buf = torch.full((2 * pad + t.numel(),), math.nan, dtype=t.dtype, device=t.device)
+    buf = torch.full((2 * pad + t.numel(),), _poison(t.dtype), dtype=t.dtype, device=t.device)
     v = buf[pad:pad + t.numel()].as_strided(t.shape, t.stride())
     assert t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)
     v.copy_(t)
     return v
 
 
-def guarded(shape, dtype, device, fill=math.nan, pad: int = PAD, channels_last: bool = False):
-    """(tensor, buffer): a dense tensor of `shape` whose memory sits inside a larger buffer; tensor and margins hold `fill`.  A
-    store out of bounds shows in the margins (assert_margins_intact), an element never stored keeps `fill`."""
+def guarded(shape, dtype, device, fill=None, pad: int = PAD, channels_last: bool = False):
+    """(tensor, buffer): a dense tensor of `shape` whose memory sits inside a larger buffer; tensor and margins hold `fill` (NaN;
+    uint8: the e4m3 NaN byte).  A store out of bounds shows in the margins (assert_margins_intact), an element never stored keeps
+    `fill`."""
     n = math.prod(shape)
+    fill = _poison(dtype) if fill is None else fill
     buf = torch.full((n + 2 * pad,), fill, dtype=dtype, device=device)
     t = buf[pad:pad + n]
     if channels_last:
@@ -411,6 +426,62 @@ def linear_into(out, x, w, bias=None, *, silu=False, geglu=False, residual=None)
                                  lda, N, ldr, 0, epi, code, gws.data_ptr(), gws.numel(), None, 0, None, None, 0, None,
                                  None, 0, _C.stream_ptr()), "linear")
     return out
+
+
+def _fp8_epilogue(_C, ops, bias, silu, geglu, residual):
+    epi = (_C.EPI_BIAS if bias is not None else 0) | (_C.EPI_SILU if silu else 0) | (_C.EPI_GEGLU if geglu else 0)
+    ldr = 0
+    if residual is not None:
+        assert residual.dtype == torch.bfloat16
+        residual, _, ldr = ops._rows2d(residual)
+        epi |= _C.EPI_RESIDUAL
+    return epi, residual, ldr
+
+
+def linear_fp8_into(out, xq, row_scale, wq, w_scale, bias=None, *, silu=False, geglu=False, residual=None):
+    """st_linear_fp8 of e4m3 bytes xq (M, K) (row stride free, a multiple of 16) with one fp32 scale per row and contiguous
+    (N or 2N, K) wq with one per weight row into the dense bf16 (M, N) `out`."""
+    _C, ops = _ops()
+    M, K = xq.shape
+    N = wq.shape[0] // 2 if geglu else wq.shape[0]
+    assert xq.dtype == wq.dtype == torch.uint8 and xq.stride(1) == 1 and wq.is_contiguous() and wq.shape[1] == K
+    assert row_scale.dtype == w_scale.dtype == torch.float32 and row_scale.numel() == M and w_scale.numel() == wq.shape[0]
+    assert out.is_contiguous() and out.numel() == M * N and out.dtype == torch.bfloat16 and (bias is None or bias.dtype == torch.bfloat16)
+    epi, residual, ldr = _fp8_epilogue(_C, ops, bias, silu, geglu, residual)
+    gws = ops._gemm_workspace(wq.device)
+    _C.check(_C.load().st_linear_fp8(xq.data_ptr(), row_scale.data_ptr(), wq.data_ptr(), w_scale.data_ptr(), ops._ptr(bias), ops._ptr(residual),
+                                     out.data_ptr(), M, N, K, xq.stride(0), N, ldr, epi, gws.data_ptr(), gws.numel(), None, 0, _C.stream_ptr()),
+             "linear_fp8")
+    return out
+
+
+def linear_fp8x_into(out, xq, a_scale, wq, w_scale, bias=None, *, geglu=False, residual=None, ln=None, row_stats=None, q8=None,
+                     q8_inv_scale=None, q8_amax=None):
+    """st_linear_fp8x: activation scale per tensor (a_scale has one entry) or per row (M entries); ln = (RowStats partials
+    (M, chunks, 2), c, d, eps) folds a LayerNorm; `out` dense bf16 (M, N) or None (only the copy: the GEGLU form); row_stats:
+    an fp32 (M, capacity, 2) buffer for the output's row partials; q8 dense uint8 (M, N) with its inverse scale (one fp32) and
+    its amax slots (ops.FP8_AMAX_SLOTS int32).  Returns the number of statistics chunks written per row (0 without row_stats)."""
+    import ctypes
+    _C, ops = _ops()
+    M, K = xq.shape
+    N = wq.shape[0] // 2 if geglu else wq.shape[0]
+    assert xq.dtype == wq.dtype == torch.uint8 and xq.stride(1) == 1 and wq.is_contiguous() and wq.shape[1] == K
+    assert a_scale.dtype == w_scale.dtype == torch.float32 and a_scale.numel() in (1, M) and w_scale.numel() == wq.shape[0]
+    assert out is None or (out.is_contiguous() and out.numel() == M * N and out.dtype == torch.bfloat16)
+    assert q8 is None or (q8.is_contiguous() and q8.numel() == M * N and q8.dtype == torch.uint8 and q8_inv_scale.dtype == torch.float32
+                          and q8_amax.numel() == ops.FP8_AMAX_SLOTS and q8_amax.dtype == torch.int32)
+    stride = 1 if (a_scale.numel() == M and M > 1) else 0
+    epi, residual, ldr = _fp8_epilogue(_C, ops, bias, False, geglu, residual)
+    st_in, chunks_in, c, d, eps = (None, 0, None, None, 0.0) if ln is None else (ln[0], ln[0].shape[1], ln[1], ln[2], ln[3])
+    assert st_in is None or (st_in.is_contiguous() and st_in.dtype == c.dtype == d.dtype == torch.float32)
+    chunks = ctypes.c_int(0)
+    gws = ops._gemm_workspace(wq.device)
+    _C.check(_C.load().st_linear_fp8x(xq.data_ptr(), a_scale.data_ptr(), stride, wq.data_ptr(), w_scale.data_ptr(), ops._ptr(bias), ops._ptr(residual),
+                                      ops._ptr(out), M, N, K, xq.stride(0), N, ldr, epi, ops._ptr(st_in), chunks_in, ops._ptr(c), ops._ptr(d), float(eps),
+                                      ops._ptr(row_stats), 0 if row_stats is None else row_stats.shape[1],
+                                      None if row_stats is None else ctypes.byref(chunks), ops._ptr(q8), N, ops._ptr(q8_inv_scale),
+                                      ops._ptr(q8_amax), gws.data_ptr(), gws.numel(), None, 0, _C.stream_ptr()), "linear_fp8x")
+    return chunks.value
 
 
 def conv2d_into(out, x, w, bias, stride, padding, *, upsample2x=False, rowbias=None, residual=None):
@@ -1107,3 +1178,243 @@ def colstats_ratios(buf, rows, stored, bm, exact, what):
     r2 = float(((s[..., 1] - s2).abs() / b2.clamp_min(1e-300)).max())
     assert r1 <= 1.0 and r2 <= 1.0, f"{what}: column partials {r1:.3g} (sums) / {r2:.3g} (squares) x their budget"
     return r1, r2
+
+
+# ------------------------------------------------------------------------------------------------ the fp8 GEMM family: dispatch restated, cases, operands
+# (tests/test_fp8_gate_host.py proves the gate on a CPU emulation of the e4m3 path; tests/test_fp8_edges_gpu.py applies it.)
+FP8_WORKSPACE_BYTES = 192 << 20           # ops.GEMM_WORKSPACE_BYTES: what a K split may use (the GPU tests assert the two agree)
+FP8_KB = 128                              # k per K tile: 128 bytes of e4m3
+
+
+def dense_plan(M, K, N, geglu=False, ln=False, *, kb=FP8_KB, f8=True, workspace_bytes=FP8_WORKSPACE_BYTES):
+    """gemm_dispatch<T, CONV = false> restated for a K that is a whole number of K tiles: (tile, BM, BN, sk, tiles).
+      small_model  the candidates of IGEMM_CANDS in their order, a later one must be strictly cheaper; no BN = 320 for 32-byte
+                   fragments (e4m3), no BN = 80 under GEGLU; every ST_TW_* factor is 1.0; a K trip is 128 bytes whatever the
+                   type (kb = 128 k in e4m3, 64 in 16 bit); no K split with a folded LayerNorm; a slice keeps nk / sk >= 4 K tiles;
+      eight-phase  gemm8p_applies (whole 256-row tiles, whole BN columns over value + gate rows, K >= 2 K tiles, N % 8 == 0),
+                   c256 / c160 = rounds x (nk x 1.65 | 1.52 + 4), taken where the cheaper one is under ST_TW_8P = 1.1 x the
+                   small tiles' best (c256 wins a tie).
+    The column split of a 256 x 256 launch needs a launch without row scales: an e4m3 launch always has them; the 16-bit
+    restatement (f8 = False: the lists of the LDS-DMA gate, which the CPU test holds this function to) refuses a shape
+    that could take it."""
+    rows = 2 * N if geglu else N
+    nk = K // kb
+    assert K % kb == 0 and nk >= 1
+    best, pick = 1e30, None
+    for name, bm, bn, trip in IGEMM_CANDS:
+        if (f8 and bn == 320) or (geglu and bn % 32 != 0):
+            continue
+        nt = _cdiv(M, bm) * _cdiv(rows, bn)
+        for s in IGEMM_SKS:
+            if s > 1 and (ln or nk // s < 4 or nt > 16384):
+                break
+            slab_mb = float(s) * nt * bm * bn * 4.0 / 1e6
+            if s > 1 and slab_mb * 1e6 + 65536 > workspace_bytes:
+                break
+            rounds = float((nt * s + 255) // 256)
+            trip_bw = float(min(nt * s, 256)) * (bm + bn) * 128.0 / 14.0e6
+            cost = rounds * (_cdiv(nk, s) * max(trip, trip_bw) + 3.0) * (1.3 if rounds > 1.0 else 1.0) + \
+                (2.1 + 0.4 * slab_mb if s > 1 else 0.0)
+            if cost < best:
+                best, pick = cost, (name, bm, bn, s, nt)
+    c = {}
+    for bn, per_trip in ((256, 1.65), (160, 1.52)):
+        applies = M % 256 == 0 and rows % bn == 0 and K >= 2 * kb and N % 8 == 0
+        nt = _cdiv(M, 256) * _cdiv(rows, bn)
+        c[bn] = (float((nt + 255) // 256) * (nk * per_trip + 4.0), nt) if applies else (1e30, nt)
+    if not f8 and c[256][0] < 1e29:
+        total, tm = c[256][1], M // 256
+        assert not (total > 256 and 0 < total % 256 <= 128 and 256 % tm == 0), "dense_plan: the column split is not restated"
+    if c[256][0] < 1e29 and c[256][0] <= c[160][0] and c[256][0] < 1.1 * best:
+        return "256x256", 256, 256, 1, c[256][1]
+    if c[160][0] < 1e29 and c[160][0] < c[256][0] and c[160][0] < 1.1 * best:
+        return "256x160", 256, 160, 1, c[160][1]
+    return pick
+
+
+def fp8_plan(M, K, N, geglu=False, ln=False):
+    """(tile, BM, BN, sk, tiles) of gemm_dispatch<f8, false> (st_linear_fp8, st_linear_fp8x)."""
+    return dense_plan(M, K, N, geglu, ln, kb=FP8_KB, f8=True)
+
+
+# ---- the cases: (tile the dispatch takes, (M, K, N)); every label is asserted against fp8_plan on the CPU ---------------------------
+# one K tile (K = 128), a partial last M tile and a partial last N tile on every tile the e4m3 GEMM is offered, N % 8 == 0
+FP8_PLAIN = [("64x64", (1, 128, 8)), ("64x64", (70, 128, 200)), ("128x64", (197, 128, 4128)), ("64x128", (259, 128, 4128)),
+             ("128x128", (400, 128, 5128)), ("128x80", (450, 128, 3368)), ("128x160", (771, 128, 4648)), ("256x128", (1027, 128, 4488))]
+FP8_GEGLU = [("64x64", (1, 128, 8)), ("64x64", (100, 128, 40)), ("128x64", (71, 128, 4168)), ("64x128", (134, 128, 3088)),
+             ("128x128", (197, 128, 4128)), ("128x160", (400, 128, 4128)), ("256x128", (400, 128, 5128))]      # (BN = 80 is not offered to GEGLU)
+FP8_WIDE_TILES = ("128x160", "256x128")
+# K tiles against ring stages (four; 256 x 128 three): 2, 3, 4, 5 K tiles - odd and even trip counts of a loop that runs two
+# trips an iteration (one fragment set per stage)
+FP8_RING_K = (256, 384, 512, 640)
+# the uneven K splits of the 16-bit gate with K doubled: the same nk, the same tile, the same sk
+FP8_UNEVEN_SPLITS = [(sk, t, (M, 2 * K, N)) for sk, t, (M, K, N) in DMA_UNEVEN_SPLITS]
+FP8_LN_K = (256, 1280)
+FP8_PER_TENSOR_TILES = ("64x64", "128x80", "256x128")
+# row statistics: the buffer holds 64 N tiles (ops.STATS_MAX_CHUNKS): 128 x 64 at N = 4128 (65 tiles) cannot emit them and has a
+# shape of its own, as in DMA_STATS
+FP8_STATS = [(t, (257, 128, 3272) if t == "128x64" else s) for t, s in FP8_PLAIN]
+# eight-phase kernel (whole tiles only), the smallest shapes the model gives it: (tile, (M, K, N), geglu, folded LayerNorm)
+FP8_GEMM8P = [("256x256", (768, 256, 11008), False, False), ("256x256", (768, 640, 11008), False, False),
+              ("256x160", (5632, 256, 1440), False, False), ("256x160", (5632, 640, 1440), False, False),
+              ("256x256", (768, 256, 5504), True, False), ("256x160", (5632, 256, 720), True, False),
+              ("256x256", (768, 640, 5504), True, True), ("256x160", (5632, 640, 720), True, True)]
+FP8_FAMILIES = ("normal", "exact")
+
+
+def fp8_ring():
+    """The plain shape of every tile with M > 1 at 2, 3, 4 and 5 K tiles."""
+    return [(t, (M, k, N)) for t, (M, _, N) in FP8_PLAIN if M > 1 for k in FP8_RING_K]
+
+
+def fp8_wide():
+    return [(t, s) for t, s in FP8_PLAIN if t in FP8_WIDE_TILES]
+
+
+def fp8_ln():
+    """(tile, shape, geglu): the plain and the GEGLU shape of every tile with M > 1 at K = 256 and 1280."""
+    return [(t, (M, k, N), g) for g, lst in ((False, FP8_PLAIN), (True, FP8_GEGLU)) for t, (M, _, N) in lst if M > 1 for k in FP8_LN_K]
+
+
+def fp8_per_tensor():
+    return [(t, s) for t, s in FP8_PLAIN if t in FP8_PER_TENSOR_TILES and s[0] > 1]
+
+
+# ---- operands: the bytes and the scales themselves ----------------------------------------------------------------------------------
+# The GEMM's operands are e4m3 bytes and fp32 scales, made on the host: no test of the GEMM depends on a quantiser kernel.
+# "normal": seeded normal values; activation row m carries the factor 1.7^-(m % 7), weight row n 1.7^-(n % 5) (at most 1: the
+#     pre-activations keep about unit variance, under ACT_RANGE among millions).  7 and 5 are coprime to every tile dimension, and
+#     neighbours in either cycle differ by 1.7 or more (the wrap by 1.7^6 / 1.7^4): quantised to amax / 448 per row, a scale
+#     taken from ANY other row or column of a tile is off by far more than 2^-8.  Per tensor: one scale for the whole activation.
+#     Budget: assert_elementwise at n_terms = K + what the launch form spends beyond EPI_OPS (fp8_n_terms).  A product of two
+#     e4m3 values has 8 significand bits: exact in fp32.
+# "exact": activation bytes from {-1, 0, 1} at density 16 / K, weight bytes, bias and residual multiples of 1/8 below 2 (each an e4m3
+#     value: asserted), row scales 2^(m % 7), column scales 2^(n % 5) (per tensor: 4).  Every term is a multiple of rs cs / 8 >= 1/8, so
+#     every partial sum, slab and scaled value is exact in fp32 while 8 sum |terms| < 2^24 (asserted on the reference): the
+#     budget is the bf16 store alone, U_OUT |ref| with mag = 0.  ONE dropped or doubled term is at least rs cs / 8 and shows
+#     wherever U_OUT |ref| < rs cs / 16 - asserted for 99 % of the elements (measured on the reference alone: 0.04 - 0.08 % are
+#     blind).  No scale below 1: with 2^-j scales a bias of eighths would leave 59 % of the elements blind (measured).
+# How v_mfma_scale_f32_16x16x128_f8f6f4 rounds inside its 128-term sum has not been measured on the instruction alone
+# (profiles/r05_mfma_accumulation.txt covers the f16 and f32 instructions): ACC_FACTOR = 2 is the assumption here as elsewhere.
+# The exact family does not depend on it (no sum of it rounds); the normal family's budget is led by the bf16 store except
+# under cancellation.  Should the normal family ever exceed its budget on the device while the exact family holds bit for bit,
+# the instruction's own summation is the suspect: measure it alone (tools/mfma_acc_probe.py is the style), never fit it here.
+E4M3 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+
+
+def e4m3_bytes(t):
+    q = t.float().to(E4M3)
+    assert bool(torch.isfinite(q.float()).all()), "a value beyond the e4m3 range"
+    return q.view(torch.uint8)
+
+
+def e4m3_f64(q):
+    return q.view(E4M3).double()
+
+
+def quantise_rows(t, per_tensor=False):
+    """(bytes, fp32 scales): amax / 448 per row, or one scale for the whole tensor."""
+    amax = t.abs().amax().reshape(1) if per_tensor else t.abs().amax(1)
+    scale = amax.float().clamp_min(1e-12) / FP8_MAX
+    return e4m3_bytes(t / scale[:, None]), scale.contiguous()
+
+
+def _cycle(n, period):
+    return torch.pow(torch.tensor(1.7), -(torch.arange(n) % period).float())
+
+
+def _signs_at_density(name, shape, density):
+    g = torch.Generator().manual_seed(int.from_bytes(name.encode(), "little") % (2 ** 63 - 1))
+    return (torch.rand(*shape, generator=g) < density).float() * (torch.randint(0, 2, shape, generator=g).float() * 2 - 1)
+
+
+class Fp8Problem:
+    """Bytes, scales, bias and the float64 products of one (M, K, weight rows) problem in a family: shared between epilogues."""
+
+    def __init__(self, M, K, rows, family, per_tensor=False):
+        self.M, self.K, self.rows, self.family, self.per_tensor = M, K, rows, family, per_tensor
+        if family == "normal":
+            x = normal(f"8.x{M}.{K}", (M, K)) * _cycle(M, 7)[:, None]
+            w = normal(f"8.w{rows}.{K}", (rows, K), K ** -0.5) * _cycle(rows, 5)[:, None]
+            self.xq, self.rs = quantise_rows(x, per_tensor)
+            self.wq, self.cs = quantise_rows(w)
+            self.bias = normal(f"8.b{rows}", (rows,), 0.5)
+        else:
+            assert family == "exact"
+            x, w = _signs_at_density(f"8.ex{M}.{K}", (M, K), min(1.0, 16.0 / K)), _eighths(f"8.ew{rows}.{K}", (rows, K))
+            self.xq, self.wq = e4m3_bytes(x), e4m3_bytes(w)
+            assert torch.equal(e4m3_f64(self.xq), x.double()) and torch.equal(e4m3_f64(self.wq), w.double())      # every value IS an e4m3 value
+            self.rs = torch.full((1,), 4.0) if per_tensor else torch.pow(torch.tensor(2.0), (torch.arange(M) % 7).float())
+            self.cs = torch.pow(torch.tensor(2.0), (torch.arange(rows) % 5).float())
+            self.bias = _eighths(f"8.eb{rows}", (rows,))
+        xd, wd = e4m3_f64(self.xq), e4m3_f64(self.wq)
+        self.unit = self.rs.double()[:, None] * self.cs.double()[None, :]          # (M | 1, rows): what one unit of the byte product is worth
+        self.prod, self.magprod = (xd @ wd.T) * self.unit, (xd.abs() @ wd.abs().T) * self.unit
+
+    def residual(self, N):
+        return normal(f"8.r{self.M}.{N}", (self.M, N)) if self.family == "normal" else _eighths(f"8.er{self.M}.{N}", (self.M, N))
+
+
+def fp8_n_terms(K, *, sk=1, bias=False, residual=False, act=False, ln=False):
+    """n_terms of the budget: K, plus the fp32 operations of the launch form beyond the EPI_OPS the budget has already: sk - 1
+    slab adds, two multiplies for the scales (rs * cs, then the product with the sum), the two FMAs of a fold, bias, the two of
+    a SiLU / GEGLU (the activation's product and the gate's bias), residual."""
+    ops_ = (sk - 1) + 2 + (2 if ln else 0) + int(bias) + (2 if act else 0) + int(residual)
+    return K + max(0, ops_ - EPI_OPS)
+
+
+def fp8_expect(prob, *, bias=True, silu=False, geglu=False, residual=None, sk=1):
+    """(ref64, mag64, extra64, n_terms) of st_linear_fp8 / st_linear_fp8x (no fold) on a problem's operands: the scaled product,
+    then linear_ref64's epilogue.  Exact family: mag = 0, after the conditions of the family have been asserted on the reference."""
+    dt = torch.bfloat16
+    ref, mag, extra = linear_ref64(None, None, prob.bias if bias else None, dt, silu=silu, geglu=geglu, residual=residual,
+                                   products=(prob.prod, prob.magprod), K=prob.K)
+    n_terms = fp8_n_terms(prob.K, sk=sk, bias=bias, residual=residual is not None, act=silu or geglu)
+    if prob.family == "exact":
+        assert not silu and not geglu, "the exact family has plain, bias and residual epilogues only"
+        assert 8.0 * float(mag.max()) < 2.0 ** 24, f"fp8 {(prob.M, prob.K, prob.rows)}: exact-sum operands are not exact in fp32"
+        blind = float((U_OUT[dt] * ref.abs() >= prob.unit / 16.0).double().mean())
+        assert blind <= 0.01, f"fp8 {(prob.M, prob.K, prob.rows)}: {blind:.3%} of the outputs could hide a one-term error"
+        return ref, torch.zeros_like(ref), None, n_terms
+    return ref, mag, extra, n_terms
+
+
+# ---- the fold's activation: a bf16 tensor as its producer stored it, its row partials, its e4m3 copy under a delayed scale ----------
+def fp8_ln_operands(M, K, rows):
+    """(x, gamma, beta, w, bias) of a LayerNorm-fold case: rows with a non-zero mean whose size cycles with period 7 (rstd differs
+    from row to row by 1.7 and more), weight rows that cycle with period 5."""
+    x, g, be, w, b = dma_ln_operands(M, K, rows)
+    return x * (_cycle(M, 7) * 1.7 ** 3)[:, None], g, be, w * _cycle(rows, 5)[:, None], b
+
+
+def fp8_delayed_scale(amax):
+    """(scale, 1 / scale) as st_fp8_update_scales leaves them for a tensor whose producer saw max |value| = amax: fp32 arithmetic,
+    margin 2 (ops.FP8_MARGIN)."""
+    s = torch.tensor(2.0, dtype=torch.float32) * torch.as_tensor(amax, dtype=torch.float32) / torch.tensor(FP8_MAX, dtype=torch.float32)
+    return s, torch.tensor(1.0, dtype=torch.float32) / s
+
+
+def e4m3_copy(stored, inv_scale):
+    """The copy an epilogue leaves: e4m3(clamp(fp32(stored) * inv_scale)) - bytes."""
+    return (stored.float() * inv_scale).clamp(-FP8_MAX, FP8_MAX).to(E4M3).view(torch.uint8)
+
+
+def fp8_fold(gamma, beta, w, bias):
+    """ops.fold_layer_norm_fp8 on the CPU (the same torch arithmetic on bf16-rounded parameters): (bytes, scales, c, d)."""
+    g, be, wt, b = (t.to(torch.bfloat16).float() for t in (gamma, beta, w, bias))
+    wq, ws = quantise_rows(wt * g[None, :])
+    c = (wq.view(E4M3).float().sum(1) * ws).contiguous()
+    return wq, ws, c, (wt @ be + b).contiguous()
+
+
+def fp8_ln_reference(x_stored, q, scale, wq, ws, c, d, eps, geglu):
+    """(ref64, mag64, extra64, n_terms) of st_linear_fp8x with a folded LayerNorm: the row statistics are those of the bf16
+    tensor its producer stored, the product is that of the tensor's e4m3 copy q under its one scale and the folded weight's
+    bytes under their per-row scales; c and d are fold_layer_norm_fp8's."""
+    K = q.shape[1]
+    unit = float(scale) * ws.double()[None, :]
+    xd, wd = e4m3_f64(q), e4m3_f64(wq)
+    ref, mag, extra = ln_linear_ref64(x_stored.float(), None, c, d, torch.bfloat16, eps, geglu=geglu,
+                                      products=((xd @ wd.T) * unit, (xd.abs() @ wd.abs().T) * unit))
+    return ref, mag, extra, fp8_n_terms(K, ln=True, act=geglu)
