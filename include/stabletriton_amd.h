@@ -530,6 +530,26 @@ int st_pag_sde_step(float* latent, const void* eps, void* next_in, float* histor
                     const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- T2I-Adapter residual sites (no reference counterpart: diffusers' `down_intrablock_additional_residuals`, ComfyUI's
+ * `control["input"]` / `["middle"]` entries of a T2I adapter).  Added after ABI 18 without a bump: a new entry point, no existing
+ * signature or contract changed.
+ *
+ * st_residual_add: x (rows, HW, C) dense NHWC of `dtype`, written IN PLACE; f (f_rows, HW, C) of the same type, f_rows a divisor of
+ * rows (1: one feature map for every row; the batch: the row blocks [negative | positive | perturbed] of a guided call share one
+ * copy; rows: one each).  With i = *step clamped to [0, n_steps) and s = scale_table[i], both read on the device when the kernel
+ * runs (a captured graph sees new values):
+ *   s == 0: beyond `*step` and that table entry nothing is read, and nothing is written - x and `stats` keep their bits ("off");
+ *   else    x[n][p][c] = round(fma(s, f[n % f_rows][p][c], x[n][p][c])), fp32 arithmetic, one rounding to `dtype`,
+ * and, with stats != NULL, the GroupNorm partials of x are REWRITTEN for the new values: stats is the `col_stats` buffer the
+ * producer of x wrote (st_linear / st_conv2d), stat_tiles x C float2 = per tile of stat_rows consecutive pixel rows and per channel
+ * (sum, sum of squares) of the values as stored (after the rounding), the producers' own convention; stat_rows is what the
+ * producer returned through col_stats_rows (it divides HW) and stat_tiles = rows * HW / stat_rows.  Every (tile, channel) partial is
+ * written by one workgroup from sums of a fixed shape: no atomics, two launches give the same bits.  stats == NULL (stat_rows =
+ * stat_tiles = 0): add only.  C a multiple of one 16-byte vector, x and f 16-byte aligned and not overlapping.  One launch, its
+ * grid split over pixel tiles and channel ranges (csrc/t2i_adapter.hip). */
+int st_residual_add(void* x, const void* f, int rows, int f_rows, long HW, int C, const float* scale_table, int n_steps,
+                    const int* step, int dtype, float* stats, int stat_rows, int stat_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@ class _HoistedUNet(nn.Module):
         self._ip_images = {}                      # set_ip_adapter_image: slot -> (tokens, negative_tokens, chunks)
         self._ip_masks = {}                       # set_ip_adapter_masks: slot -> masks
         self._ip_applied = {}                     # ... rows -> the latent size the buffers of that row count were last written for
+        self._t2i_last = None                     # T2I-Adapter: (rows, the residual tensors last copied - HELD, not their addresses -, their versions)
 
     def refresh_weights(self) -> int:
         """Re-derive fused / folded weight buffers after an in-place weight update (also done at every new prompt).
@@ -277,6 +278,44 @@ class _HoistedUNet(nn.Module):
             state.set_masks(masks, slot, rows)
         self._ip_applied[rows] = hw
 
+    # ---- T2I-Adapter residuals (t2i_adapter.py): static buffers the residual sites read by address; the captured graphs stay ----
+    def _t2i_state(self):
+        from . import t2i_adapter
+        state = getattr(self.compiled, "t2i_adapter", None)
+        return state if isinstance(state, t2i_adapter.T2IAdapterState) else None
+
+    def _apply_t2i(self, sample: torch.Tensor, features) -> None:
+        """Bind the buffers of this call's batch and latent size (outside any capture) and write this call's residuals: one tensor
+        per site (None: zeros there), already scaled by the caller, so the scale is 1; `features` None: scale 0, nothing else is
+        touched.  The very tensors of the previous call at their versions are not copied again: the wrapper HOLDS those tensors until
+        the next call with others (identity is only safe while the objects live; at 1024 x 1024, bf16, two rows that is about 26 MB
+        kept alive), and the rule looks at the caller's tensors alone - somebody who writes the shared buffers through
+        `gm.t2i_adapter.set` in between, and then calls with the same tensor objects, is not noticed."""
+        state = self._t2i_state()
+        if state is None:
+            return
+        rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
+        if not torch.cuda.is_current_stream_capturing():
+            state.bind(rows, hw, sample.device, dtype=self.compute_dtype)
+        if features is None:
+            if state.host_scale != 0.0:
+                state.clear()
+            return
+        if len(features) != len(state.sites):
+            raise ValueError(f"T2I-Adapter residuals: {len(state.sites)} tensors expected, one per site {state.sites}, got {len(features)}")
+        versions = tuple(None if f is None else f._version for f in features)
+        last = self._t2i_last
+        same = (last is not None and last[0] == rows and last[2] == versions and len(last[1]) == len(features)
+                and all(a is b for a, b in zip(last[1], features)))
+        if not same:
+            shapes = state.site_shapes(hw)
+            full = [torch.zeros((1,) + shapes[k], dtype=self.compute_dtype, device=sample.device) if f is None else f
+                    for k, f in enumerate(features)]
+            state.set(full, None, rows)
+            self._t2i_last = (rows, list(features), versions)
+        if state.host_scale != 1.0:
+            state.set_scale(1.0)
+
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
         version it had then.  A different object of the same shape (ComfyUI re-concatenates cond | uncond on every call) is
@@ -342,13 +381,14 @@ class _HoistedUNet(nn.Module):
                     run_once()          # the very first evaluation creates the scale slots; after it this trajectory starts like every later one
             recalibrate_fp8(self.compiled, run_once)
 
-    def _run(self, sample, timesteps, ehs, cond):
+    def _run(self, sample, timesteps, ehs, cond, t2i=None):
         # (.to() is the identity when the caller already computes in this dtype: an fp16 pipeline over an fp16 module)
         io_dtype = sample.dtype
         dev = sample.device
         self._apply_regions(sample)
         self._apply_ip_adapter(sample)
         self._apply_seg(sample)
+        self._apply_t2i(sample, t2i)
         self._context_for(ehs)
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor(float(timesteps), dtype=torch.float32)
@@ -381,7 +421,9 @@ class DiffusersUNet(_HoistedUNet):
         return self.compute_dtype
 
     def forward(self, sample, timestep, encoder_hidden_states=None, class_labels=None, timestep_cond=None,
-                attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None, return_dict: bool = False, **ignored):
+                attention_mask=None, cross_attention_kwargs=None, added_cond_kwargs=None, return_dict: bool = False,
+                down_block_additional_residuals=None, mid_block_additional_residual=None, down_intrablock_additional_residuals=None,
+                **ignored):
         if encoder_hidden_states is None or added_cond_kwargs is None:
             raise ValueError("the SDXL UNet needs encoder_hidden_states and added_cond_kwargs{text_embeds, time_ids}")
         for name, val in (("class_labels", class_labels), ("timestep_cond", timestep_cond), ("attention_mask", attention_mask)):
@@ -404,9 +446,18 @@ class DiffusersUNet(_HoistedUNet):
             if extra:
                 raise NotImplementedError(f"cross_attention_kwargs {sorted(extra)} (attention processors / a LoRA scale other than 1) are not "
                                           "supported: load the adapter with load_lora(name, state_dict, scale) and the scale is honoured")
+        t2i = None
+        if self._t2i_state() is not None:
+            # compiled with t2i_adapter=True: the T2I-Adapter pipeline's residuals (already scaled by adapter_conditioning_scale) are
+            # honoured, ControlNet's are refused; a wrapper compiled without the flag ignores all three, as it always has
+            if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
+                raise NotImplementedError("down_block_additional_residuals / mid_block_additional_residual (ControlNet) are not supported "
+                                          "by the compiled UNet: only down_intrablock_additional_residuals (T2I-Adapter) are")
+            if down_intrablock_additional_residuals is not None:
+                t2i = list(down_intrablock_additional_residuals)
         cd = self.compute_dtype
         cond = {"text_embeds": added_cond_kwargs["text_embeds"].to(cd), "time_ids": added_cond_kwargs["time_ids"].to(cd)}
-        out = self._run(sample, timestep, encoder_hidden_states, cond)
+        out = self._run(sample, timestep, encoder_hidden_states, cond, t2i)
         if return_dict:
             from types import SimpleNamespace
             return SimpleNamespace(sample=out)
@@ -415,7 +466,7 @@ class DiffusersUNet(_HoistedUNet):
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                                 region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> DiffusersUNet:
+                                 region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
@@ -427,7 +478,9 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     concatenated along the token axis as `encoder_hidden_states`; `set_regions(masks, chunks)` / `clear_regions()` drive it.
     `ip_adapter=N` (or a tuple of token counts, one per adapter) compiles IP-Adapter image attention in (ip_adapter.py):
     `load_ip_adapter`, `set_ip_adapter_image`, `set_ip_adapter_scale`, `set_ip_adapter_masks`, `unload_ip_adapter` drive it;
-    `added_cond_kwargs["image_embeds"]` is not read."""
+    `added_cond_kwargs["image_embeds"]` is not read.
+    `t2i_adapter=True` compiles the T2I-Adapter residual sites in (t2i_adapter.py): `down_intrablock_additional_residuals` of a call
+    are then added at the sites (None: off, at no cost), ControlNet's residual arguments raise."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
@@ -435,17 +488,18 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
-                              ip_adapter=ip_adapter, seg_layers=seg_layers)
+                              ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                        regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None):
+                        regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
-                                             regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers)
+                                             regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers,
+                                             t2i_adapter=t2i_adapter)
     return pipe
 
 
@@ -455,18 +509,23 @@ class ComfyUNet(_HoistedUNet):
     def forward(self, x, timesteps=None, context=None, y=None, control=None, transformer_options: Optional[dict] = None, **kwargs):
         if timesteps is None or context is None or y is None:
             raise ValueError("ComfyUNet needs timesteps, context (text states) and y (pooled text | size/crop features)")
+        t2i = None
         if control is not None:
-            raise NotImplementedError("ControlNet residuals (`control`) are not supported by the compiled UNet")
+            state = self._t2i_state()
+            if state is None:
+                raise NotImplementedError("ControlNet residuals (`control`) are not supported by the compiled UNet")
+            from . import t2i_adapter
+            t2i = t2i_adapter.comfy_features(state, control)      # a T2I adapter's input / middle entries; anything else raises
         patches = (transformer_options or {}).get("patches") or (transformer_options or {}).get("patches_replace")
         if patches:
             raise NotImplementedError("transformer_options patches are not supported by the compiled UNet")
         if y.shape[0] != x.shape[0] or context.shape[0] != x.shape[0]:
             raise ValueError("x, context and y must share the batch dimension")
-        return self._run(x, timesteps, context, y.to(self.compute_dtype))
+        return self._run(x, timesteps, context, y.to(self.compute_dtype), t2i)
 
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                       region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> ComfyUNet:
+                       region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
@@ -474,16 +533,17 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
     the token axis, `set_regions(masks, chunks)` / `clear_regions()` drive it.  `ip_adapter=N`: with IP-Adapter image attention
     (the IPAdapter nodes), driven by `load_ip_adapter` / `set_ip_adapter_image` / `set_ip_adapter_scale` / `set_ip_adapter_masks` /
     `unload_ip_adapter`.  `seg_layers=("mid",)`: with smoothed-energy sites (the SEG node); its extra, fully perturbed call is
-    `enable_seg(1, sigma)`."""
+    `enable_seg(1, sigma)`.  `t2i_adapter=True`: with T2I-Adapter residual sites: `control={"input": [...], "middle": [...]}` of a call
+    is consumed the way ComfyUI's apply_control does (from the end of each list, None entries skipped) and must land on the sites."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                              region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers)
+                              region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                      regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> ComfyUNet:
+                      regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens, ip_adapter, seg_layers)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens, ip_adapter, seg_layers, t2i_adapter)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -1906,3 +1906,53 @@ def freeu(h: torch.Tensor, skip: torch.Tensor, params: torch.Tensor, slot: int):
     if rows > 0:
         return h_out, s_out, ColStats(st_h, rows, Ch), ColStats(st_s, rows, Cs)
     return h_out, s_out, None, None
+
+
+# ----------------------------------------------------------------------------- T2I-Adapter residual sites
+def _forget_split(x: torch.Tensor) -> None:
+    """Drop the split image a producer noted for x's memory: a launch that writes x through its raw pointer leaves `x._version`
+    as it was, so the note would still be honoured and the consumer would read the image of the OLD values."""
+    lst = _split_notes(x.device)
+    if lst:
+        at = x.data_ptr()
+        lst[:] = [ent for ent in lst if ent[1] != at]
+
+
+def residual_add(x: torch.Tensor, f: torch.Tensor, scale_table: torch.Tensor, step: torch.Tensor, stats: Optional["ColStats"] = None):
+    """x[n] += s * f[n % f_rows] IN PLACE, s = scale_table[*step] read on the device (csrc/t2i_adapter.hip): x (rows, C, H, W)
+    channels_last, f (f_rows, C, H, W) channels_last of the same dtype with f_rows a divisor of rows, scale_table fp32 and step an
+    int32 device tensor of one entry.  `stats`: the ColStats x's producer emitted; with s != 0 the kernel rewrites them in place for
+    the new values (sums of the values as stored, the epilogues' convention), with s == 0 nothing at all is written.  Returns the
+    statistics that describe x afterwards: `stats` itself, or None (none given, or they do not fit the shape - the GroupNorm behind
+    then makes its own pass).  Anything the kernel does not take (not dense NHWC, a channel count that is not a whole number of
+    16-byte vectors) goes through `x.add_(s * f)` in torch and returns no statistics; that route cannot see s on the host either, so
+    at s == 0 it still runs the add (of zeros: the same values, but x IS written and its version moves).
+    The note of a producer's split image for x's memory is dropped on EVERY call, whatever s is (the host cannot read it without a
+    synchronisation): in strict fp32 the consumer behind a site splits its own operand, one more launch per site, also at scale 0."""
+    _C.require_device(x, f, scale_table, step)
+    if x.dim() != 4 or f.dim() != 4 or f.dtype != x.dtype or tuple(f.shape[1:]) != tuple(x.shape[1:]) or f.shape[0] < 1 \
+            or x.shape[0] % f.shape[0]:
+        raise BackendError(f"residual_add: x {tuple(x.shape)} {x.dtype} and f {tuple(f.shape)} {f.dtype} must be (rows, C, H, W) and "
+                           "(f_rows, C, H, W) of one dtype with f_rows a divisor of rows")
+    if scale_table.dtype != torch.float32 or scale_table.dim() != 1 or not scale_table.is_contiguous() or scale_table.numel() < 1:
+        raise BackendError("residual_add: scale_table must be a contiguous 1-D fp32 tensor")
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise BackendError("residual_add: step must be an int32 tensor of one entry")
+    rows, Cc, H, W = x.shape
+    cl = torch.channels_last
+    vec = 4 if x.dtype == torch.float32 else 8
+    _forget_split(x)
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or Cc % vec or not x.is_contiguous(memory_format=cl):
+        s = scale_table.index_select(0, step.reshape(1).long().clamp(0, scale_table.numel() - 1))
+        x.add_((f.float() * s).to(x.dtype).repeat(rows // f.shape[0], 1, 1, 1))
+        return None
+    if not f.is_contiguous(memory_format=cl):
+        f = f.contiguous(memory_format=cl)
+    HW = H * W
+    ok = stats is not None and stats.channels == Cc and stats.rows > 0 and HW % stats.rows == 0 \
+        and stats.buf.numel() >= (rows * HW // stats.rows) * Cc * 2
+    tiles = rows * HW // stats.rows if ok else 0
+    _C.check(_C.load().st_residual_add(x.data_ptr(), f.data_ptr(), rows, f.shape[0], HW, Cc, scale_table.data_ptr(), scale_table.numel(),
+                                       step.data_ptr(), _C.dtype_code(x.dtype), stats.buf.data_ptr() if ok else None,
+                                       stats.rows if ok else 0, tiles, _C.stream_ptr()), "residual_add")
+    return stats if ok else None

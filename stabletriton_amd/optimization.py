@@ -16,17 +16,18 @@ import torch
 from torch import fx, nn
 
 from . import _C, ops
+from . import t2i_adapter as _t2i
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_ip_adapter, insert_pag, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
-                    ip_adapter=None, seg_layers=None) -> fx.GraphModule:
+                    ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> fx.GraphModule:
     """Pass pipeline.  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
@@ -42,12 +43,17 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     ip_adapter.py); the same cost per site as regions; not with `regions` or `fp8`.  `seg_layers` (addition, off by default,
     likewise): regular expressions selecting the self-attention sites whose perturbed batch entries take blurred queries (smoothed
     energy guidance; optimizers/insert_seg.py, seg.py); the state, `gm.seg`, starts with chunks 0 = ordinary attention; not with
-    `pag_layers` (both claim the perturbed row block, and a site carries one leaf)."""
+    `pag_layers` (both claim the perturbed row block, and a site carries one leaf).  `t2i_adapter=True` (addition, off by default,
+    likewise): a residual site behind every down block and the middle block (optimizers/insert_t2i_adapter.py, t2i_adapter.py); the
+    state, `gm.t2i_adapter`, starts at scale 0 = the bits of the module without sites; not with `fp8`."""
     _check_seg_and_pag(seg_layers, pag_layers)
     if regions is not None and fp8:
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
     check_combination(ip_adapter, regions, fp8)
+    _t2i.check_combination(t2i_adapter, fp8)
     stats: Dict[str, int] = {}
+    if t2i_adapter:      # first of all: module paths are readable, and FreeU's sites then read skips that carry the residual
+        stats["t2i_adapter_sites"] = insert_t2i_adapter(gm)
     if freeu:      # first: the readers of a concatenation still carry their module paths
         stats["freeu_sites"] = insert_freeu(gm)
     stats["dropout"] = remove_dropout(gm)
@@ -101,8 +107,17 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
-                   pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None) -> fx.GraphModule:
-    """`seg_layers=("mid",)` (addition): smoothed energy guidance (seg.py).  The selected self-attention sites can treat the last
+                   pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None,
+                   t2i_adapter: bool = False) -> fx.GraphModule:
+    """`t2i_adapter=True` (addition): T2I-Adapter structural control (t2i_adapter.py).  The UNet adds `s * f_k` to its activation
+    behind every down block and the middle block (diffusers' `down_intrablock_additional_residuals` places), in place, in one launch
+    per site that also rewrites the producer's GroupNorm partials.  `gm.t2i_adapter` - `bind(rows, latent_hw, device)` once, then
+    `set(features, scale)`, `set_scale(scale)`, `clear()` in place, no new capture; `using(step, table)` around the caller's own
+    calls for per-step scales; scale 0, the state after `bind`, writes nothing: the bits of the module compiled without sites.
+    `t2i_adapter.FullAdapterXL` turns a control image into the features.  Not with `fp8=True`.  (With `cuda_graph=True` a captured
+    call keeps reading the table and counter it was captured with - the state's own, outside `using` -, and `bind` must precede the
+    first call; DenoiseLoop and the hooks capture their own graphs over a `cuda_graph=False` module.)
+    `seg_layers=("mid",)` (addition): smoothed energy guidance (seg.py).  The selected self-attention sites can treat the last
     B // chunks batch entries of a call as perturbed: their queries are Gaussian-blurred over the latent grid (sigma = infinity: the
     spatial mean).  `gm.seg.bind(latent_hw, device)` once per latent size, `gm.seg.using(chunks, latent_hw)` around the caller's own
     calls, `gm.seg.set_sigma(sigma)` in place, no new capture; chunks 0, the initial state, is ordinary attention.  Not with
@@ -143,8 +158,9 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
     check_combination(ip_adapter, regions, fp8)
     _check_seg_and_pag(seg_layers, pag_layers)
+    _t2i.check_combination(t2i_adapter, fp8)
     gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                         region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers)
+                         region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

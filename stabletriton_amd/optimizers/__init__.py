@@ -13,6 +13,7 @@ from .plan_fp8 import plan_fp8
 from .fuse_groupnorm_stats import fuse_groupnorm_stats
 from .fuse_skip_cat import fuse_skip_cat
 from .insert_freeu import insert_freeu
+from .insert_t2i_adapter import insert_t2i_adapter
 from .insert_pag import insert_pag
 from .insert_seg import insert_seg
 from .insert_regions import insert_regions

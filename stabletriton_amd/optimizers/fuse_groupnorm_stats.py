@@ -17,6 +17,7 @@ import torch
 from torch import fx
 
 from ..freeu import freeu_wrapper
+from ..t2i_adapter import t2i_site
 from .wrappers import conv2d_wrapper, group_norm_stats_wrapper, group_norm_wrapper, linear_residual_wrapper
 
 _VIEWS = ("reshape", "view", "permute", "contiguous")
@@ -39,6 +40,9 @@ def _can_emit(n: fx.Node) -> bool:
         return not (len(n.args) > 3 and n.args[3]) and not n.kwargs.get("emit_stats")
     if _freeu_output(n):          # h' / r' of a FreeU site: the site always returns the partials of both (items 2 and 3)
         return True
+    if _is_fn(n, t2i_site):       # a T2I-Adapter site rewrites the partials of the launch that produced its input
+        inner = _producers(n.args[0])
+        return inner is not None and len(inner) == 1
     return False
 
 
@@ -75,6 +79,10 @@ def _stats_of(gm: fx.GraphModule, prod: fx.Node) -> fx.Node:
                 return u
         with gm.graph.inserting_after(prod):
             return gm.graph.call_function(operator.getitem, (site, want))
+    if _is_fn(prod, t2i_site) and not prod.kwargs.get("emit_colstats"):
+        # the inner producer's partials go INTO the site (which rewrites them in place when its scale is not 0) and come out of it
+        inner = _stats_of(gm, _producers(prod.args[0])[0])
+        prod.kwargs = {**prod.kwargs, "src_stats": inner}      # (and on into the (out, stats) form, like any producer)
     if not prod.kwargs.get("emit_colstats"):
         prod.kwargs = {**prod.kwargs, "emit_colstats": True}
         with gm.graph.inserting_after(prod):

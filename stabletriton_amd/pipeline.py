@@ -61,6 +61,12 @@ image tokens of each adapter slot, in the same launch, under per-site scales in 
 and masks are device buffers the sites read by address: every one of the five calls is an in-place write, before or after
 `capture()`.  A slot at scale 0 - the state until `set_ip_adapter_scale` - is skipped by the kernel: the bits of a UNet compiled
 without `ip_adapter`.
+
+T2I-Adapter structural control (`set_t2i_adapter`, `set_t2i_adapter_scale`; t2i_adapter.py) on a UNet compiled with
+`t2i_adapter=True`: four feature maps per control image, written once into static buffers, are added at the UNet's residual sites
+under a per-step scale table (`scale` for the first int(n_steps * factor) steps, 0 after).  The sites read the table at
+`step_ids[i:i+1]` (modes loop / eager) or at the step counter (mode step); a step at scale 0 - every step until `set_t2i_adapter` -
+writes nothing: the bits of a UNet compiled without sites.
 """
 from __future__ import annotations
 
@@ -128,6 +134,14 @@ class DenoiseLoop:
         self._ip_state = getattr(unet, "ip_adapter", None) if isinstance(getattr(unet, "ip_adapter", None), _ip.IPAdapter) else None
         if self._ip_state is not None:                     # scale table, mask weights, image K/V of this row count: allocated once, "off"
             self._ip_state.bind(rows, (lh, lw), dev)
+        # T2I-Adapter residual sites: feature buffers of `batch` rows shared by every row block, and this loop's own per-step scale
+        # table (0 = off), both read by address: allocated once, outside capture
+        from . import t2i_adapter as _t2i
+        self._t2i_state = getattr(unet, "t2i_adapter", None) if isinstance(getattr(unet, "t2i_adapter", None), _t2i.T2IAdapterState) else None
+        self.t2i_table = None
+        if self._t2i_state is not None:
+            self._t2i_state.bind(rows, (lh, lw), dev, dtype=dtype, feature_rows=batch)
+            self.t2i_table = torch.zeros(n, dtype=torch.float32, device=dev)
         self._latent_hw = (lh, lw)
         if self._seg_state is not None:                    # the blur's parameter rows of this latent size: allocated once, outside capture
             self._seg_state.bind((lh, lw), dev)
@@ -401,6 +415,29 @@ class DenoiseLoop:
         """Slot `slot` back to "off": scale 0, weights and image K/V zero, masks 1 - the bits of the loop before the adapter."""
         self._ip("unload_ip_adapter").unload(slot)
 
+    # ---- T2I-Adapter (t2i_adapter.py): in-place writes of buffers the residual sites read by address, no new capture ---------
+    def set_t2i_adapter(self, features, scale: float = 1.0, factor: float = 1.0) -> None:
+        """The adapter's feature maps, one per site, each (B or 1, C_k, h_k, w_k) (t2i_adapter.FullAdapterXL on the control image;
+        several adapters: the sum of their features), and the per-step scale table: `scale` for the steps i < int(n_steps * factor),
+        0 after (diffusers' `adapter_conditioning_scale` / `adapter_conditioning_factor`).  Every row block of the UNet batch reads the
+        same copy.  `set_t2i_adapter(None)` is "off": the bits of a UNet compiled without sites.  In-place writes, legal before or
+        after `capture()`.  The UNet must have been compiled with `t2i_adapter=True`; a loop that shares its UNet and its row count
+        with another shares the feature buffers (not the scales)."""
+        from . import t2i_adapter
+        state = t2i_adapter.state_of(self.unet, "set_t2i_adapter")
+        if features is None:
+            self.t2i_table.zero_()
+            return
+        table = t2i_adapter.scale_table(self.n_steps, scale, factor)
+        state.set(features, None, self.x_in.shape[0])
+        self.t2i_table.copy_(table)
+
+    def set_t2i_adapter_scale(self, scale: Union[float, Sequence[float]]) -> None:
+        """The sites' scale per step: a float, or n_steps floats.  Written into the device table in place: no new capture."""
+        from . import t2i_adapter
+        t2i_adapter.state_of(self.unet, "set_t2i_adapter_scale")
+        self.t2i_table.copy_(self._step_table(scale, "scale", "set_t2i_adapter_scale"))
+
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
         s + B - 1 (mod 2^64).  Written into the device table in place: a captured graph reads it by address."""
@@ -497,7 +534,13 @@ class DenoiseLoop:
     def _cond(self) -> Dict[str, torch.Tensor]:
         return {"text_embeds": self.text_embeds, "time_ids": self.time_ids}
 
-    def _unet(self, t, time_row=None):
+    def _unet(self, t, time_row=None, step=None):
+        if self._t2i_state is not None:      # the residual sites read this loop's scale table at `step`, for this loop's own calls only
+            with self._t2i_state.using(self.step_ids[0:1] if step is None else step, self.t2i_table):
+                return self._unet_guided(t, time_row)
+        return self._unet_guided(t, time_row)
+
+    def _unet_guided(self, t, time_row=None):
         if self._pag_state is not None:      # the last B rows are the perturbed block, for this loop's own calls only
             with self._pag_state.using(self._pag_chunks):
                 return self._unet_call(t, time_row)
@@ -517,14 +560,14 @@ class DenoiseLoop:
 
     def _step_const(self, i: int) -> None:
         row = tuple(tbl[i] for tbl in self.time_tables) if self._tsplit else None      # static views: no launch
-        eps = self._unet(self.timesteps[i], row)
+        eps = self._unet(self.timesteps[i], row, self.step_ids[i:i + 1])
         self._update(eps, self.step_ids[i:i + 1])
 
     def _step_counted(self) -> None:
         idx = self.step.long()
         t = self.timesteps.index_select(0, idx)[0]
         row = tuple(tbl.index_select(0, idx)[0] for tbl in self.time_tables) if self._tsplit else None
-        eps = self._unet(t, row)
+        eps = self._unet(t, row, self.step)
         self._update(eps, self.step)
         ops.step_advance(self.step, self.n_steps)
 
