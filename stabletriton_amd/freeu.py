@@ -27,6 +27,8 @@ import math
 import torch
 from torch import nn
 
+from .state import require_state
+
 NEUTRAL = (1.0, 1.0, 1.0, 1.0, 1.0)       # (b1, s1, b2, s2, version)
 
 
@@ -143,8 +145,4 @@ torch.fx.wrap("freeu_wrapper")
 
 def state_of(module, what: str) -> FreeU:
     """The FreeU state of a compiled module, or a ValueError that names the missing compile argument."""
-    st = getattr(module, "freeu", None)
-    if not isinstance(st, FreeU):
-        raise ValueError(f"{what}: this UNet was compiled without FreeU sites; compile it with freeu=True "
-                         "(optimize_model / compile_unet_from_state_dict / attach_to_diffusers / compile_comfy_unet / patch_comfy_model)")
-    return st
+    return require_state(module, "freeu", FreeU, what, "FreeU sites", "freeu=True")

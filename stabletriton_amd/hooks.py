@@ -21,6 +21,7 @@ Both packages are duck-typed (neither is a dependency).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, Optional
 
 import torch
@@ -28,6 +29,7 @@ from torch import nn
 
 from .optimization import optimize_model
 from .optimizers.graphs import make_dynamic_graphed_callable
+from .state import compiled_state
 from .unet import SDXL_BASE, UNet2DConditionModel, UNetSpec, UNetWithLabelVector, make_config
 
 
@@ -52,8 +54,7 @@ class _HoistedUNet(nn.Module):
         self._steps: Dict[tuple, object] = {}     # ehs shape -> (graphed) step function
         self._new_prompt = False                  # set when a context was (re)projected: the fp8 plan measures its scales again
         self._last_t = None                       # fp8 plan only: the last call's (largest) timestep, to tell where a trajectory starts
-        self._pag_chunks = 0                      # enable_pag: the last B // chunks rows of a call are perturbed (0: none)
-        self._seg_chunks = 0                      # enable_seg: likewise, for the smoothed-energy sites (blurred queries)
+        self._perturbed_chunks = 0                # enable_pag / enable_seg: the last B // chunks rows of a call are perturbed (0: none)
         self._regions = None                      # set_regions: (masks, chunks), applied to the buffers of a call's (rows, latent size)
         self._regions_applied = {}                # ... rows -> the latent size the buffers of that row count were last written for
         self._ip_images = {}                      # set_ip_adapter_image: slot -> (tokens, negative_tokens, chunks)
@@ -111,17 +112,18 @@ class _HoistedUNet(nn.Module):
         pag.state_of(self.compiled, "enable_pag")
         if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 1:
             raise ValueError(f"enable_pag: chunks must be a positive integer (3, 2 or 1), got {chunks!r}")
-        self._pag_chunks = chunks             # (the state's own `chunks` is set around this wrapper's calls only: _pag_scope)
+        self._perturbed_chunks = chunks       # (the state's own `chunks` is set around this wrapper's calls only: _perturbed_scope)
 
     def disable_pag(self) -> None:
         from . import pag
         pag.state_of(self.compiled, "disable_pag")
-        self._pag_chunks = 0
+        self._perturbed_chunks = 0
 
-    def _pag_scope(self, chunks: int):
-        import contextlib
-        state = getattr(self.compiled, "pag", None)
-        return state.using(chunks) if state is not None else contextlib.nullcontext()
+    def _perturbed_scope(self, chunks: int, latent_hw):
+        """The PAG or SEG state's `using` (a module has at most one of them) around this wrapper's own calls."""
+        from . import pag, seg
+        state = compiled_state(self.compiled, "pag", pag.PAG) or compiled_state(self.compiled, "seg", seg.SEG)
+        return state.using(chunks, latent_hw) if state is not None else contextlib.nullcontext()
 
     # ---- smoothed energy guidance (seg.py): which rows of a call take blurred queries; sigma is a device row, written in place ----
     def enable_seg(self, chunks: int, sigma: float = float("inf")) -> None:
@@ -135,7 +137,7 @@ class _HoistedUNet(nn.Module):
         if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 1:
             raise ValueError(f"enable_seg: chunks must be a positive integer (3, 2 or 1), got {chunks!r}")
         state.set_sigma(sigma)
-        self._seg_chunks = chunks             # (the state's own `chunks` is set around this wrapper's calls only: _seg_scope)
+        self._perturbed_chunks = chunks
 
     def set_seg_sigma(self, sigma: float) -> None:
         """The blur's sigma for the following calls: an in-place write of the parameter rows the captured graphs read by address."""
@@ -145,17 +147,13 @@ class _HoistedUNet(nn.Module):
     def disable_seg(self) -> None:
         from . import seg
         seg.state_of(self.compiled, "disable_seg")
-        self._seg_chunks = 0
-
-    def _seg_scope(self, chunks: int, latent_hw):
-        import contextlib
-        state = getattr(self.compiled, "seg", None)
-        return state.using(chunks, latent_hw) if state is not None else contextlib.nullcontext()
+        self._perturbed_chunks = 0
 
     def _apply_seg(self, sample: torch.Tensor) -> None:
         """Allocate the parameter rows of this call's latent size, outside any capture (the sites only look them up)."""
-        state = getattr(self.compiled, "seg", None)
-        if state is None or not self._seg_chunks or torch.cuda.is_current_stream_capturing():
+        from . import seg
+        state = compiled_state(self.compiled, "seg", seg.SEG)
+        if state is None or not self._perturbed_chunks or torch.cuda.is_current_stream_capturing():
             return
         state.bind((int(sample.shape[-2]), int(sample.shape[-1])), sample.device)
 
@@ -188,8 +186,8 @@ class _HoistedUNet(nn.Module):
         weights are written again whenever the geometry of a row count changes, and masks of another size than the call's
         latent raise.  Without masks nothing is written: new buffers are "off", and another owner's setting is left alone."""
         from . import regions
-        state = getattr(self.compiled, "regions", None)
-        if not isinstance(state, regions.Regions) or torch.cuda.is_current_stream_capturing():
+        state = compiled_state(self.compiled, "regions", regions.Regions)
+        if state is None or torch.cuda.is_current_stream_capturing():
             return
         rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
         state.bind(rows, hw, sample.device)
@@ -262,8 +260,8 @@ class _HoistedUNet(nn.Module):
     def _apply_ip_adapter(self, sample: torch.Tensor) -> None:
         """Bind the buffers of this call's batch and latent size and write what was set for this geometry (as _apply_regions)."""
         from . import ip_adapter
-        state = getattr(self.compiled, "ip_adapter", None)
-        if not isinstance(state, ip_adapter.IPAdapter) or torch.cuda.is_current_stream_capturing():
+        state = compiled_state(self.compiled, "ip_adapter", ip_adapter.IPAdapter)
+        if state is None or torch.cuda.is_current_stream_capturing():
             return
         rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
         state.bind(rows, hw, sample.device)
@@ -281,8 +279,7 @@ class _HoistedUNet(nn.Module):
     # ---- T2I-Adapter residuals (t2i_adapter.py): static buffers the residual sites read by address; the captured graphs stay ----
     def _t2i_state(self):
         from . import t2i_adapter
-        state = getattr(self.compiled, "t2i_adapter", None)
-        return state if isinstance(state, t2i_adapter.T2IAdapterState) else None
+        return compiled_state(self.compiled, "t2i_adapter", t2i_adapter.T2IAdapterState)
 
     def _apply_t2i(self, sample: torch.Tensor, features) -> None:
         """Bind the buffers of this call's batch and latent size (outside any capture) and write this call's residuals: one tensor
@@ -348,8 +345,8 @@ class _HoistedUNet(nn.Module):
         if fn is None:
             ctx = self._ctx[shape]                 # closed over: the graph reads these buffers in place
 
-            def step(sample, timesteps, cond, pag_chunks=0, seg_chunks=0):      # (plain integers: part of the graph cache's key)
-                with self._pag_scope(pag_chunks), self._seg_scope(seg_chunks, tuple(sample.shape[-2:])):
+            def step(sample, timesteps, cond, chunks=0):      # (a plain integer: part of the graph cache's key)
+                with self._perturbed_scope(chunks, tuple(sample.shape[-2:])):
                     return self.compiled.forward_with_context(sample, timesteps, ctx, cond)[0]
 
             fn = make_dynamic_graphed_callable(step) if self.cuda_graph else step
@@ -372,7 +369,7 @@ class _HoistedUNet(nn.Module):
             from .optimization import recalibrate_fp8
             ctx = self._ctx[shape]
             def run_once():
-                with self._pag_scope(self._pag_chunks), self._seg_scope(self._seg_chunks, tuple(x.shape[-2:])):
+                with self._perturbed_scope(self._perturbed_chunks, tuple(x.shape[-2:])):
                     return self.compiled.forward_with_context(x, timesteps, ctx, cond)
 
             ectx = getattr(self.compiled, "exec_context", None)
@@ -400,12 +397,8 @@ class _HoistedUNet(nn.Module):
             self._fp8_restart(x, timesteps, tuple(ehs.shape), cond)
         self._new_prompt = False
         with torch.no_grad():
-            if self._seg_chunks:
-                out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond, self._pag_chunks, self._seg_chunks)
-            elif self._pag_chunks:
-                out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond, self._pag_chunks)
-            else:
-                out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond)
+            extra = (self._perturbed_chunks,) if self._perturbed_chunks else ()      # (0 keeps the cache entry of a call without it)
+            out = self._step_fn(tuple(ehs.shape))(x, timesteps, cond, *extra)
         return out.to(io_dtype)
 
 
@@ -544,6 +537,7 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                       regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
-    adapter = compile_comfy_unet(unet, cuda_graph, freeu, pag_layers, regions, region_tokens, ip_adapter, seg_layers, t2i_adapter)
+    adapter = compile_comfy_unet(unet, cuda_graph, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
+                                 ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
     model_patcher.model.diffusion_model = adapter
     return adapter

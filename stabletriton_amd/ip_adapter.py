@@ -37,10 +37,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from .regions import site_levels
+from .state import RowBound, require_state
 
 MAX_SLOTS = 4              # adapters per compiled module (1 text + 4 image segments of st_attention_segments' 8)
 MAX_TOKENS = 255           # keys per segment (the text-context kernel's range)
-_FALLBACK_LEVELS = 4       # levels tried when the site paths do not spell their stage
 
 _NUMBERED = re.compile(r"^(\d+)\.to_([kv])_ip\.weight$")
 _PATHED = re.compile(r"^(.*?)(?:\.processor)?\.to_([kv])_ip(?:\.(\d+))?\.weight$")
@@ -107,8 +107,9 @@ def project_image_embeds(image_proj_state_dict: Mapping[str, torch.Tensor], imag
     return F.layer_norm(y, (cross,), g, beta, 1e-5)
 
 
-class IPAdapter(nn.Module):
+class IPAdapter(RowBound, nn.Module):
     """State of one compiled module: the slots' token counts, the attn2 site paths with their widths, and the device buffers."""
+    label = "ip_adapter"
 
     def __init__(self, tokens: Sequence[int], sites: Sequence[str], dims: Sequence[Tuple[int, int]], levels=None, like=None):
         super().__init__()
@@ -156,51 +157,27 @@ class IPAdapter(nn.Module):
         self._static()
         return self._scales
 
-    def _levels_for(self, lh: int, lw: int):
-        cand = self.levels if self.levels is not None else range(_FALLBACK_LEVELS)
-        out = [l for l in cand if lh % (1 << l) == 0 and lw % (1 << l) == 0 and (lh >> l) and (lw >> l)]
-        if self.levels is not None and len(out) != len(self.levels):
-            raise ValueError(f"ip_adapter: a {lh} x {lw} latent does not divide into the attention levels {self.levels} of this UNet")
-        return out
-
     def bind(self, rows: int, latent_hw, device) -> None:
         """Allocate every buffer of a UNet batch of `rows` rows at this latent size: mask weights 1, image K / V zero, and (once) the
         scale table and the adapter weights.  Outside any capture; what exists is kept, so binding twice is free."""
-        lh, lw = (int(latent_hw[0]), int(latent_hw[1])) if isinstance(latent_hw, (tuple, list, torch.Size)) else (int(latent_hw),) * 2
-        rows = int(rows)
-        if rows < 1 or lh < 1 or lw < 1:
-            raise ValueError(f"ip_adapter.bind: rows {rows}, latent {lh} x {lw}")
-        device = torch.device(device)
+        rows, lh, lw, device = self._parse_bind(rows, latent_hw, device)
         dev, dtype = self._model()
         if torch.device(dev).type != device.type:
             raise ValueError(f"ip_adapter.bind: the module lives on {dev}, not {device}")
-        capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
         self._static()
         for l in self._levels_for(lh, lw):
             T = (lh >> l) * (lw >> l)
             if (rows, T) not in self._weights:
-                if capturing:
-                    raise RuntimeError("ip_adapter.bind: allocate the buffers before the capture starts")
+                self._refuse_capture(dev)
                 self._weights[(rows, T)] = torch.ones((rows, 1 + self.slots, T), dtype=torch.float32, device=dev)
         for i, (c, _) in enumerate(self.dims):
             for a, n in enumerate(self.tokens):
                 if (rows, i, a) not in self._kv:
-                    if capturing:
-                        raise RuntimeError("ip_adapter.bind: allocate the buffers before the capture starts")
+                    self._refuse_capture(dev)
                     self._kv[(rows, i, a)] = torch.zeros((rows, n, 2 * c), dtype=dtype, device=dev)
 
     def bound_rows(self):
         return sorted({r for r, _, _ in self._kv})
-
-    def _rows(self, rows: Optional[int], what: str) -> int:
-        have = self.bound_rows()
-        if rows is None:
-            if len(have) != 1:
-                raise ValueError(f"{what}: pass rows=: this state is bound for the row counts {have} (bind(rows, latent_hw, device) first)")
-            return have[0]
-        if int(rows) not in have:
-            raise ValueError(f"{what}: no buffers for {rows} rows (bound: {have}); call bind(rows, latent_hw, device) first")
-        return int(rows)
 
     def _slot(self, slot, what: str) -> int:
         if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < self.slots:
@@ -433,11 +410,7 @@ torch.fx.wrap("attention_ip_wrapper")
 
 def state_of(module, what: str) -> IPAdapter:
     """The IP-Adapter state of a compiled module, or a ValueError that names the missing compile argument."""
-    st = getattr(module, "ip_adapter", None)
-    if not isinstance(st, IPAdapter):
-        raise ValueError(f"{what}: this UNet was compiled without IP-Adapter cross-attention sites; compile it with ip_adapter=N "
-                         "(optimize_model / compile_unet_from_state_dict / attach_to_diffusers / compile_comfy_unet / patch_comfy_model)")
-    return st
+    return require_state(module, "ip_adapter", IPAdapter, what, "IP-Adapter cross-attention sites", "ip_adapter=N")
 
 
 def check_combination(ip_adapter, regions, fp8) -> None:

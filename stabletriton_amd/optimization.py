@@ -10,7 +10,7 @@ callable with the original forward signature; the caller re-attaches `.config`
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Union
 
 import torch
 from torch import fx, nn
@@ -25,10 +25,11 @@ from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention,
                          replace_linear, replace_linear_activ)
 
 
-def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
+def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
                     ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> fx.GraphModule:
-    """Pass pipeline.  The first eight passes and their order are the reference's
+    """Pass pipeline over a traced module; an untraced nn.Module is traced here, after the flags were checked against each other
+    (optimize_model relies on it: a bad combination raises before the trace).  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
     product here), replace_conv / epilogue fusions / layout are additions.
     `xattn_fusion` / `gn_stats` switch two of the added fusions off (A/B measurements).  `freeu` (addition, off by default:
@@ -46,11 +47,9 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     `pag_layers` (both claim the perturbed row block, and a site carries one leaf).  `t2i_adapter=True` (addition, off by default,
     likewise): a residual site behind every down block and the middle block (optimizers/insert_t2i_adapter.py, t2i_adapter.py); the
     state, `gm.t2i_adapter`, starts at scale 0 = the bits of the module without sites; not with `fp8`."""
-    _check_seg_and_pag(seg_layers, pag_layers)
-    if regions is not None and fp8:
-        raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
-    check_combination(ip_adapter, regions, fp8)
-    _t2i.check_combination(t2i_adapter, fp8)
+    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter)
+    if not isinstance(gm, fx.GraphModule):
+        gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
     if t2i_adapter:      # first of all: module paths are readable, and FreeU's sites then read skips that carry the residual
         stats["t2i_adapter_sites"] = insert_t2i_adapter(gm)
@@ -62,7 +61,7 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     stats["attention"] = fuse_attention(gm)
     if pag_layers is not None:      # directly after: the query projections still carry their module paths
         stats["pag_sites"] = insert_pag(gm, pag_layers)
-    if seg_layers is not None:      # likewise (never both: _check_seg_and_pag)
+    if seg_layers is not None:      # likewise (never both: check_feature_combination)
         stats["seg_sites"] = insert_seg(gm, seg_layers)
     if regions is not None:         # likewise
         stats["region_sites"] = insert_regions(gm, regions, region_tokens)
@@ -96,10 +95,15 @@ def replace_backend(gm: fx.GraphModule, fuse: bool = True, fp8: bool = False, xa
     return gm
 
 
-def _check_seg_and_pag(seg_layers, pag_layers) -> None:
+def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter) -> None:
+    """The compile flags that exclude each other."""
     if seg_layers is not None and pag_layers is not None:
         raise ValueError("seg_layers cannot be combined with pag_layers: smoothed energy guidance and perturbed-attention guidance both "
                          "claim the perturbed row block of a call, and a self-attention site carries one leaf")
+    if regions is not None and fp8:
+        raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
+    check_combination(ip_adapter, regions, fp8)
+    _t2i.check_combination(t2i_adapter, fp8)
 
 
 def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
@@ -154,12 +158,7 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     model = model.eval().to(memory_format=torch.channels_last)      # conv weights -> (Cout,R,S,Cin) strides
     if fp8 and p0.dtype != torch.bfloat16:
         raise RuntimeError("fp8 projections need a bfloat16 model")
-    if regions is not None and fp8:
-        raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
-    check_combination(ip_adapter, regions, fp8)
-    _check_seg_and_pag(seg_layers, pag_layers)
-    _t2i.check_combination(t2i_adapter, fp8)
-    gm = replace_backend(fx.symbolic_trace(model), fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
+    gm = replace_backend(model, fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
                          region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
@@ -178,33 +177,25 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
             return _run_step(gm, lambda: plain(*args, **kwargs))
 
         gm.forward = forward
-    if cuda_graph and pag_layers is not None:
-        # the perturbed range is host state the launches are captured with: it is part of the graph cache's key
-        state, inner = gm.pag, gm.forward
+    if cuda_graph and (pag_layers is not None or seg_layers is not None):
+        # the perturbed range - and for SEG the call's latent size, the sites' token grids - is host state the launches are captured
+        # with: it is part of the graph cache's key
+        state, inner = (gm.pag if pag_layers is not None else gm.seg), gm.forward
 
-        def run_with_chunks(*args, _pag_chunks: int = 0, **kwargs):
-            with state.using(_pag_chunks):
+        def run_perturbed(*args, _chunks: int = 0, _latent=None, **kwargs):
+            with state.using(_chunks, _latent):
                 return inner(*args, **kwargs)
 
-        graphed = make_dynamic_graphed_callable(run_with_chunks, before_replay=gm.exec_context.refresh_derived)
-        gm.forward = lambda *args, **kwargs: graphed(*args, _pag_chunks=state.chunks, **kwargs)
-    elif cuda_graph and seg_layers is not None:
-        # likewise: the perturbed range and the call's latent size (the sites' token grids) are host state of the captured launches
-        seg_state, seg_inner = gm.seg, gm.forward
+        graphed = make_dynamic_graphed_callable(run_perturbed, before_replay=gm.exec_context.refresh_derived)
 
-        def run_with_seg(*args, _seg_chunks: int = 0, _seg_latent=None, **kwargs):
-            with seg_state.using(_seg_chunks, _seg_latent):
-                return seg_inner(*args, **kwargs)
-
-        seg_graphed = make_dynamic_graphed_callable(run_with_seg, before_replay=gm.exec_context.refresh_derived)
-
-        def seg_forward(*args, **kwargs):
-            if seg_state.chunks and seg_state.latent_hw is not None:      # rows are allocated outside the capture the cache may start
+        def perturbed_forward(*args, **kwargs):
+            latent = state.latent_hw if seg_layers is not None and state.chunks else None
+            if latent is not None:      # SEG's rows are allocated outside the capture the cache may start
                 sample = args[0] if args else kwargs["sample"]
-                seg_state.bind(seg_state.latent_hw, sample.device)
-            return seg_graphed(*args, _seg_chunks=seg_state.chunks, _seg_latent=seg_state.latent_hw if seg_state.chunks else None, **kwargs)
+                state.bind(latent, sample.device)
+            return graphed(*args, _chunks=state.chunks, _latent=latent, **kwargs)
 
-        gm.forward = seg_forward
+        gm.forward = perturbed_forward
     elif cuda_graph:
         gm.forward = make_dynamic_graphed_callable(gm.forward, before_replay=gm.exec_context.refresh_derived)
     return gm

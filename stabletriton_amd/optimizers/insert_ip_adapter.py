@@ -18,30 +18,18 @@ from torch import fx
 
 from ..ip_adapter import IPAdapter, attention_ip_wrapper, parse_token_counts
 from ..regions import site_levels
-from .insert_regions import _attn2_path
-from .wrappers import attention_wrapper
+from .attention_sites import attention_sites, replace_sites
 
 
 def insert_ip_adapter(gm: fx.GraphModule, ip_adapter) -> int:
     """Rewrite every cross-attention site and install the state as `gm.ip_adapter` (unbound; every slot "off"); returns the number
     of sites."""
     tokens = parse_token_counts(ip_adapter)
-    chosen = [(n, path) for n in gm.graph.nodes
-              if n.op == "call_function" and n.target is attention_wrapper and not n.kwargs
-              for path in (_attn2_path(n),) if path is not None]
+    chosen = attention_sites(gm, "attn2")
     if not chosen:
         raise ValueError("ip_adapter: this UNet has no cross-attention (attn2) site")
     sites = [p for _, p in chosen]
     keys = [gm.get_submodule(p + ".to_k").weight for p in sites]
     dims = [(int(w.shape[0]), int(w.shape[1])) for w in keys]
     state = IPAdapter(tokens, sites, dims, site_levels(sites, [name for name, _ in gm.named_modules()]), like=keys[0])
-    gm.add_submodule("ip_adapter", state)
-    for i, (n, _) in enumerate(chosen):
-        with gm.graph.inserting_before(n):
-            attr = gm.graph.get_attr("ip_adapter")
-            new = gm.graph.call_function(attention_ip_wrapper, tuple(n.args) + (attr, i))
-        n.replace_all_uses_with(new)
-        gm.graph.erase_node(n)
-    gm.graph.lint()
-    gm.recompile()
-    return len(chosen)
+    return replace_sites(gm, chosen, "ip_adapter", state, attention_ip_wrapper, lambda i: (i,))

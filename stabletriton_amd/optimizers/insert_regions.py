@@ -13,42 +13,18 @@ launch more per site than the fused form.
 """
 from __future__ import annotations
 
-import re
-
 from torch import fx
 
 from ..regions import Regions, attention_regions_wrapper, site_levels
-from .wrappers import attention_wrapper
-
-_CROSS_QUERY = re.compile(r"^(.*(?:^|\.)attn2)\.to_q$")
-
-
-def _attn2_path(att: fx.Node):
-    """Module path of the cross-attention whose to_q feeds `att`'s query, else None."""
-    q = att.args[0]
-    if not (isinstance(q, fx.Node) and q.op == "call_module"):
-        return None
-    m = _CROSS_QUERY.match(str(q.target))
-    return m.group(1) if m else None
+from .attention_sites import attention_sites, replace_sites
 
 
 def insert_regions(gm: fx.GraphModule, R: int, seg_len: int = 77) -> int:
     """Rewrite every cross-attention site and install the state as `gm.regions` (unbound; "off" once bound); returns the number of
     sites."""
-    chosen = [(n, path) for n in gm.graph.nodes
-              if n.op == "call_function" and n.target is attention_wrapper and not n.kwargs
-              for path in (_attn2_path(n),) if path is not None]
+    chosen = attention_sites(gm, "attn2")
     sites = [p for _, p in chosen]
     state = Regions(R, seg_len, sites, site_levels(sites, [name for name, _ in gm.named_modules()]))      # (validates R, seg_len)
     if not chosen:
         raise ValueError("regions: this UNet has no cross-attention (attn2) site")
-    gm.add_submodule("regions", state)
-    for n, _ in chosen:
-        with gm.graph.inserting_before(n):
-            attr = gm.graph.get_attr("regions")
-            new = gm.graph.call_function(attention_regions_wrapper, tuple(n.args) + (attr,))
-        n.replace_all_uses_with(new)
-        gm.graph.erase_node(n)
-    gm.graph.lint()
-    gm.recompile()
-    return len(chosen)
+    return replace_sites(gm, chosen, "regions", state, attention_regions_wrapper)

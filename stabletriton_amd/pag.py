@@ -23,45 +23,58 @@ from typing import Sequence
 import torch
 from torch import nn
 
+from .state import require_state
+
 TRAIN_TIMESTEPS = 1000      # diffusers' adaptive rule counts down from the training schedule's length
 
 
-class PAG(nn.Module):
-    """State of one compiled module: the selected site names (attn1 module paths) and the host integer `chunks`."""
+class PerturbedRows(nn.Module):
+    """State of one compiled module whose selected self-attention sites perturb the last B // chunks batch entries of a call (PAG
+    here, seg.SEG): the selected site names (attn1 module paths) and the host values `chunks` and `latent_hw` of the current call."""
+    label = ""
 
     def __init__(self, sites: Sequence[str] = (), layers: Sequence[str] = ()):
         super().__init__()
         self.sites = tuple(sites)
         self.layers = tuple(layers)
         self.chunks = 0
+        self.latent_hw = None
 
     def set_chunks(self, chunks: int) -> None:
         if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 0:
-            raise ValueError(f"PAG: chunks must be a non-negative integer (0: off; the last B // chunks batch entries are perturbed), got {chunks!r}")
+            raise ValueError(f"{self.label}: chunks must be a non-negative integer (0: off; the last B // chunks batch entries are perturbed), got {chunks!r}")
         self.chunks = chunks
 
     @contextlib.contextmanager
-    def using(self, chunks: int):
-        """`chunks` for the calls made inside the block; the previous value comes back afterwards (owners that share one
-        compiled module do not disturb each other)."""
-        before = self.chunks
+    def using(self, chunks: int, latent_hw=None):
+        """`chunks` and the latent size of the calls made inside the block; the previous values come back afterwards (owners that
+        share one compiled module do not disturb each other)."""
+        before = (self.chunks, self.latent_hw)
         self.set_chunks(chunks)
+        if latent_hw is not None:
+            self.latent_hw = (int(latent_hw[0]), int(latent_hw[1]))
         try:
             yield self
         finally:
-            self.chunks = before
+            self.chunks, self.latent_hw = before
 
-    def ident_count(self, batch: int) -> int:
+    def tail_count(self, batch: int) -> int:
         """How many trailing batch entries of a call with `batch` entries are perturbed."""
         c = self.chunks
         if c == 0:
             return 0
         if batch % c != 0:
-            raise ValueError(f"PAG: a UNet batch of {batch} rows does not divide into {c} chunks")
+            raise ValueError(f"{self.label}: a UNet batch of {batch} rows does not divide into {c} chunks")
         return batch // c
 
     def extra_repr(self) -> str:
         return f"sites={len(self.sites)}, chunks={self.chunks}"
+
+
+class PAG(PerturbedRows):
+    """The perturbed rows return v; nothing depends on the latent size (`latent_hw` is carried and never read)."""
+    label = "PAG"
+    ident_count = PerturbedRows.tail_count
 
 
 def identity_attention_reference(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, sm_scale: float, ident: int) -> torch.Tensor:
@@ -108,8 +121,4 @@ def adaptive_scales(timesteps, pag_scale: float, pag_adaptive_scale: float = 0.0
 
 def state_of(module, what: str) -> PAG:
     """The PAG state of a compiled module, or a ValueError that names the missing compile argument."""
-    st = getattr(module, "pag", None)
-    if not isinstance(st, PAG):
-        raise ValueError(f"{what}: this UNet was compiled without perturbed-attention sites; compile it with pag_layers=(\"mid\",) "
-                         "(optimize_model / compile_unet_from_state_dict / attach_to_diffusers / compile_comfy_unet / patch_comfy_model)")
-    return st
+    return require_state(module, "pag", PAG, what, "perturbed-attention sites", 'pag_layers=("mid",)')

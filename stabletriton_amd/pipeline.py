@@ -70,14 +70,16 @@ writes nothing: the bits of a UNet compiled without sites.
 """
 from __future__ import annotations
 
+import contextlib
 import numbers
 from typing import Callable, Dict, Optional, Sequence, Union
 
 import torch
 
-from . import ops
+from . import ops, seg
 from .optimizers.graphs import no_gc_during_capture
 from .scheduler import DPMSolverTables, EulerTables, SDETables, euler_discrete_tables
+from .state import compiled_state
 
 
 class DenoiseLoop:
@@ -93,25 +95,21 @@ class DenoiseLoop:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
         if guidance_rescale is not None and guidance_scale is None:
             raise ValueError("guidance_rescale needs guidance_scale")
+        from . import ip_adapter as _ip, pag, regions as _regions, t2i_adapter as _t2i
         # perturbed-attention guidance: the UNet's sites must exist (compiled in), and the loop names the perturbed row block
         # around its own UNet calls only (chunks 3 = [neg | pos | pert], 2 = [pos | pert])
-        self._pag_state = None
+        self._perturbed = None
         if pag_scale is not None:
-            from . import pag
-            self._pag_state = pag.state_of(unet, "DenoiseLoop(pag_scale=...)")
-        self._pag_chunks = 0 if pag_scale is None else (3 if guidance_scale is not None else 2)
+            self._perturbed = pag.state_of(unet, "DenoiseLoop(pag_scale=...)")
         # smoothed energy guidance: the same perturbed row block under another perturbation (blurred queries); everything below
         # that speaks of `pag_scale` - rows, conditioning, the scale table, the update launches - serves both
-        self._seg_state, self._seg_chunks = None, 0
         if seg_scale is not None:
-            from . import seg
-            self._seg_state = seg.state_of(unet, "DenoiseLoop(seg_scale=...)")
+            self._perturbed = seg.state_of(unet, "DenoiseLoop(seg_scale=...)")
             seg.check_sigma(seg_sigma)
-            self._seg_chunks = 3 if guidance_scale is not None else 2
             pag_scale = seg_scale
+        self._perturbed_chunks = 0 if pag_scale is None else (3 if guidance_scale is not None else 2)
         # regional prompts: the sites are part of the compiled UNet, the text context carries its R prompts side by side
-        from . import regions as _regions
-        self._regions_state = getattr(unet, "regions", None) if isinstance(getattr(unet, "regions", None), _regions.Regions) else None
+        self._regions_state = compiled_state(unet, "regions", _regions.Regions)
         if self._regions_state is not None and tokens != self._regions_state.R * self._regions_state.seg_len:
             st = self._regions_state
             raise ValueError(f"DenoiseLoop: this UNet was compiled with regions={st.R}, region_tokens={st.seg_len}: build the loop with "
@@ -130,22 +128,20 @@ class DenoiseLoop:
         rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
         if self._regions_state is not None:                # the weight buffers of this row count: allocated once, "off"
             self._regions_state.bind(rows, (lh, lw), dev)
-        from . import ip_adapter as _ip
-        self._ip_state = getattr(unet, "ip_adapter", None) if isinstance(getattr(unet, "ip_adapter", None), _ip.IPAdapter) else None
+        self._ip_state = compiled_state(unet, "ip_adapter", _ip.IPAdapter)
         if self._ip_state is not None:                     # scale table, mask weights, image K/V of this row count: allocated once, "off"
             self._ip_state.bind(rows, (lh, lw), dev)
         # T2I-Adapter residual sites: feature buffers of `batch` rows shared by every row block, and this loop's own per-step scale
         # table (0 = off), both read by address: allocated once, outside capture
-        from . import t2i_adapter as _t2i
-        self._t2i_state = getattr(unet, "t2i_adapter", None) if isinstance(getattr(unet, "t2i_adapter", None), _t2i.T2IAdapterState) else None
+        self._t2i_state = compiled_state(unet, "t2i_adapter", _t2i.T2IAdapterState)
         self.t2i_table = None
         if self._t2i_state is not None:
             self._t2i_state.bind(rows, (lh, lw), dev, dtype=dtype, feature_rows=batch)
             self.t2i_table = torch.zeros(n, dtype=torch.float32, device=dev)
         self._latent_hw = (lh, lw)
-        if self._seg_state is not None:                    # the blur's parameter rows of this latent size: allocated once, outside capture
-            self._seg_state.bind((lh, lw), dev)
-            self._seg_state.set_sigma(seg_sigma)
+        if isinstance(self._perturbed, seg.SEG):           # the blur's parameter rows of this latent size: allocated once, outside capture
+            self._perturbed.bind((lh, lw), dev)
+            self._perturbed.set_sigma(seg_sigma)
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
         self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
         self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
@@ -181,7 +177,7 @@ class DenoiseLoop:
         self.pag = None
         if pag_scale is not None:
             self.pag = torch.zeros(n, dtype=torch.float32, device=dev)
-            self.pag.copy_(self._step_table(pag_scale, "scale", "set_seg" if self._seg_state is not None else "set_pag"))
+            self.pag.copy_(self._step_table(pag_scale, "scale", "set_seg" if isinstance(self._perturbed, seg.SEG) else "set_pag"))
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -222,7 +218,7 @@ class DenoiseLoop:
         """Perturbed-attention guidance scale per step: a float, or n_steps floats (pag.adaptive_scales gives diffusers' adaptive
         table).  Written into the device table in place: no new capture.  Scale 0 keeps the perturbed rows and gives the value
         the loop would compute without them."""
-        if self.pag is None or self._seg_state is not None:
+        if self.pag is None or isinstance(self._perturbed, seg.SEG):
             raise ValueError("set_pag: this loop was built without pag_scale")
         self.pag.copy_(self._step_table(scale, "scale", "set_pag"))
 
@@ -231,11 +227,11 @@ class DenoiseLoop:
         spatial mean).  Both are in-place writes of device buffers the captured graph reads by address: no new capture.  Scale 0
         keeps the perturbed rows and gives the value the loop would compute without them.  sigma belongs to the UNet's SEG state:
         loops that share one compiled UNet share it."""
-        if self._seg_state is None:
+        if not isinstance(self._perturbed, seg.SEG):
             raise ValueError("set_seg: this loop was built without seg_scale")
         table = self._step_table(scale, "scale", "set_seg") if scale is not None else None
         if sigma is not None:
-            self._seg_state.set_sigma(sigma)
+            self._perturbed.set_sigma(sigma)
         if table is not None:
             self.pag.copy_(table)
 
@@ -535,19 +531,12 @@ class DenoiseLoop:
         return {"text_embeds": self.text_embeds, "time_ids": self.time_ids}
 
     def _unet(self, t, time_row=None, step=None):
-        if self._t2i_state is not None:      # the residual sites read this loop's scale table at `step`, for this loop's own calls only
-            with self._t2i_state.using(self.step_ids[0:1] if step is None else step, self.t2i_table):
-                return self._unet_guided(t, time_row)
-        return self._unet_guided(t, time_row)
-
-    def _unet_guided(self, t, time_row=None):
-        if self._pag_state is not None:      # the last B rows are the perturbed block, for this loop's own calls only
-            with self._pag_state.using(self._pag_chunks):
-                return self._unet_call(t, time_row)
-        if self._seg_state is not None:      # likewise, with the latent size the sites derive their token grids from
-            with self._seg_state.using(self._seg_chunks, self._latent_hw):
-                return self._unet_call(t, time_row)
-        return self._unet_call(t, time_row)
+        with contextlib.ExitStack() as scopes:      # both for this loop's own calls only
+            if self._t2i_state is not None:      # the residual sites read this loop's scale table at `step`
+                scopes.enter_context(self._t2i_state.using(self.step_ids[0:1] if step is None else step, self.t2i_table))
+            if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
+                scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
+            return self._unet_call(t, time_row)
 
     def _unet_call(self, t, time_row=None):
         if self._split:

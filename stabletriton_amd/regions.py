@@ -30,9 +30,10 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .state import RowBound, require_state
+
 MAX_REGIONS = 8            # st_attention_regions: segments per launch
 MAX_SEG_LEN = 255          # ... and keys per segment (the text-context kernel's range)
-_FALLBACK_LEVELS = 4       # levels tried when the site paths do not spell their stage (see Regions.levels)
 
 
 def _as_batched(masks: torch.Tensor, R: int, what: str) -> torch.Tensor:
@@ -87,8 +88,9 @@ def row_weights(masks: torch.Tensor, level: int, rows: int, positive_rows: Seque
     return out
 
 
-class Regions(nn.Module):
+class Regions(RowBound, nn.Module):
     """State of one compiled module: R, seg_len, the attn2 site paths, the attention levels, and the weight buffers."""
+    label = "regions"
 
     def __init__(self, R: int, seg_len: int = 77, sites: Sequence[str] = (), levels: Optional[Sequence[int]] = None):
         super().__init__()
@@ -107,43 +109,21 @@ class Regions(nn.Module):
         self._weights: Dict[Tuple[int, int], torch.Tensor] = {}
 
     # ---- buffers ---------------------------------------------------------------------------------
-    def _levels_for(self, lh: int, lw: int):
-        cand = self.levels if self.levels is not None else range(_FALLBACK_LEVELS)
-        out = [l for l in cand if lh % (1 << l) == 0 and lw % (1 << l) == 0 and (lh >> l) and (lw >> l)]
-        if self.levels is not None and len(out) != len(self.levels):
-            raise ValueError(f"regions: a {lh} x {lw} latent does not divide into the attention levels {self.levels} of this UNet")
-        return out
-
     def bind(self, rows: int, latent_hw, device) -> None:
         """Allocate the weight buffers of a UNet batch of `rows` rows at this latent size, initialised to "off".  Outside any
         capture; a buffer that exists is kept as it is (its address is what captured graphs read), so binding twice is free."""
-        lh, lw = (int(latent_hw[0]), int(latent_hw[1])) if isinstance(latent_hw, (tuple, list, torch.Size)) else (int(latent_hw),) * 2
-        rows = int(rows)
-        if rows < 1 or lh < 1 or lw < 1:
-            raise ValueError(f"regions.bind: rows {rows}, latent {lh} x {lw}")
-        device = torch.device(device)
+        rows, lh, lw, device = self._parse_bind(rows, latent_hw, device)
         for l in self._levels_for(lh, lw):
             T = (lh >> l) * (lw >> l)
             buf = self._weights.get((rows, T))
             if buf is None:
-                if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("regions.bind: allocate the weight buffers before the capture starts")
+                self._refuse_capture(device, "the weight buffers")
                 self._weights[(rows, T)] = off_weights(rows, self.R, T).to(device)
             elif buf.device != device:
                 raise ValueError(f"regions.bind: the buffers of {rows} rows live on {buf.device}, not {device}")
 
     def bound_rows(self):
         return sorted({r for r, _ in self._weights})
-
-    def _rows(self, rows: Optional[int], what: str) -> int:
-        have = self.bound_rows()
-        if rows is None:
-            if len(have) != 1:
-                raise ValueError(f"{what}: pass rows=: this state is bound for the row counts {have} (bind(rows, latent_hw, device) first)")
-            return have[0]
-        if int(rows) not in have:
-            raise ValueError(f"{what}: no buffers for {rows} rows (bound: {have}); call bind(rows, latent_hw, device) first")
-        return int(rows)
 
     def weights_for(self, rows: int, T: int) -> torch.Tensor:
         buf = self._weights.get((int(rows), int(T)))
@@ -242,11 +222,7 @@ torch.fx.wrap("attention_regions_wrapper")
 
 def state_of(module, what: str) -> Regions:
     """The regions state of a compiled module, or a ValueError that names the missing compile argument."""
-    st = getattr(module, "regions", None)
-    if not isinstance(st, Regions):
-        raise ValueError(f"{what}: this UNet was compiled without regional cross-attention sites; compile it with regions=R "
-                         "(optimize_model / compile_unet_from_state_dict / attach_to_diffusers / compile_comfy_unet / patch_comfy_model)")
-    return st
+    return require_state(module, "regions", Regions, what, "regional cross-attention sites", "regions=R")
 
 
 def positive_rows(rows: int, chunks: int):

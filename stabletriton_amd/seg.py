@@ -33,7 +33,9 @@ import numbers
 from typing import Dict, List, Sequence, Tuple
 
 import torch
-from torch import nn
+
+from .pag import PerturbedRows
+from .state import require_state
 
 MEAN_SIGMA = 9999.0          # sigma at or beyond this is infinity: the plane's mean
 MAX_SIDE = 128               # st_seg_blur's largest token grid side (ST_SEG_MAX_SIDE)
@@ -107,48 +109,22 @@ def blur_reference(q: torch.Tensor, grid_hw, sigma: float) -> torch.Tensor:
     return planes.reshape(n, T, C)
 
 
-class SEG(nn.Module):
-    """State of one compiled module: the selected site names (attn1 module paths), the host values `chunks` and `latent_hw` of the
-    current call, sigma, and the device parameter rows by (device, token grid)."""
+class SEG(PerturbedRows):
+    """pag.PerturbedRows (site names, `chunks` and `latent_hw` of the current call) with sigma and the device parameter rows by
+    (device, token grid)."""
+    label = "SEG"
 
     def __init__(self, sites: Sequence[str] = (), layers: Sequence[str] = ()):
-        super().__init__()
-        self.sites = tuple(sites)
-        self.layers = tuple(layers)
-        self.chunks = 0
-        self.latent_hw = None
+        super().__init__(sites, layers)
         self.sigma = float("inf")
         self._rows: Dict[tuple, torch.Tensor] = {}
 
-    # ---- host state of the current call ----
-    def set_chunks(self, chunks: int) -> None:
-        if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 0:
-            raise ValueError(f"SEG: chunks must be a non-negative integer (0: off; the last B // chunks batch entries are perturbed), got {chunks!r}")
-        self.chunks = chunks
-
     @contextlib.contextmanager
     def using(self, chunks: int, latent_hw=None):
-        """`chunks` and the latent size of the calls made inside the block; the previous values come back afterwards (owners that
-        share one compiled module do not disturb each other)."""
-        before = (self.chunks, self.latent_hw)
         if chunks and latent_hw is None:
             raise ValueError("SEG: using(chunks, latent_hw) needs the call's latent size: the sites derive their token grids from it")
-        self.set_chunks(chunks)
-        if latent_hw is not None:
-            self.latent_hw = (int(latent_hw[0]), int(latent_hw[1]))
-        try:
+        with super().using(chunks, latent_hw):
             yield self
-        finally:
-            self.chunks, self.latent_hw = before
-
-    def tail_count(self, batch: int) -> int:
-        """How many trailing batch entries of a call with `batch` entries are perturbed."""
-        c = self.chunks
-        if c == 0:
-            return 0
-        if batch % c != 0:
-            raise ValueError(f"SEG: a UNet batch of {batch} rows does not divide into {c} chunks")
-        return batch // c
 
     # ---- device parameter rows ----
     @staticmethod
@@ -229,8 +205,4 @@ torch.fx.wrap("attention_seg_wrapper")
 
 def state_of(module, what: str) -> SEG:
     """The SEG state of a compiled module, or a ValueError that names the missing compile argument."""
-    st = getattr(module, "seg", None)
-    if not isinstance(st, SEG):
-        raise ValueError(f"{what}: this UNet was compiled without smoothed-energy sites; compile it with seg_layers=(\"mid\",) "
-                         "(optimize_model / compile_unet_from_state_dict / attach_to_diffusers / compile_comfy_unet / patch_comfy_model)")
-    return st
+    return require_state(module, "seg", SEG, what, "smoothed-energy sites", 'seg_layers=("mid",)')

@@ -33,11 +33,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 from torch import nn
 
-
-def _hw(latent_hw) -> Tuple[int, int]:
-    if isinstance(latent_hw, (tuple, list, torch.Size)):
-        return int(latent_hw[0]), int(latent_hw[1])
-    return int(latent_hw), int(latent_hw)
+from .state import RowBound, latent_size, require_state
 
 
 def scale_table(n_steps: int, scale: float = 1.0, factor: float = 1.0) -> torch.Tensor:
@@ -52,8 +48,9 @@ def scale_table(n_steps: int, scale: float = 1.0, factor: float = 1.0) -> torch.
     return torch.tensor([scale if i < on else 0.0 for i in range(n_steps)], dtype=torch.float32)
 
 
-class T2IAdapterState(nn.Module):
+class T2IAdapterState(RowBound, nn.Module):
     """State of one compiled module: the sites (name, channels, latent halvings, ComfyUI input-block index) and their buffers."""
+    label = "t2i_adapter"
 
     def __init__(self, sites: Sequence[Tuple[str, int, int, Optional[int]]], dtype: Optional[torch.dtype] = None):
         super().__init__()
@@ -73,7 +70,7 @@ class T2IAdapterState(nn.Module):
     def site_shapes(self, latent_hw):
         """(C, h, w) of every site's feature map at this latent size: each halving is the UNet's stride-2 convolution, ceil(n / 2)
         (the adapter's AvgPool2d(ceil_mode=True) and PixelUnshuffle of a multiple of 16 pixels give the same sizes)."""
-        lh, lw = _hw(latent_hw)
+        lh, lw = latent_size(latent_hw)
         out = []
         for c, l in zip(self.channels, self.levels):
             h, w = lh, lw
@@ -90,22 +87,19 @@ class T2IAdapterState(nn.Module):
         (its address is what captured graphs read), so binding twice is free."""
         rows = int(rows)
         f_rows = rows if feature_rows is None else int(feature_rows)
-        lh, lw = _hw(latent_hw)
-        if rows < 1 or lh < 1 or lw < 1 or f_rows < 1 or rows % f_rows:
+        lh, lw = latent_size(latent_hw)
+        if rows < 1 or lh < 1 or lw < 1 or f_rows < 1 or rows % f_rows:      # (not _parse_bind: this text names feature_rows too)
             raise ValueError(f"t2i_adapter.bind: rows {rows}, latent {lh} x {lw}, feature_rows {f_rows} (a divisor of rows)")
         device = torch.device(device)
         dtype = dtype or self.dtype or torch.float32
-        capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
         if device not in self._tables:
-            if capturing:
-                raise RuntimeError("t2i_adapter.bind: allocate the buffers before the capture starts")
+            self._refuse_capture(device)
             self._tables[device] = (torch.full((1,), self.host_scale, dtype=torch.float32, device=device),
                                     torch.zeros(1, dtype=torch.int32, device=device))
         for k, (c, h, w) in enumerate(self.site_shapes((lh, lw))):
             buf = self._features.get((rows, k, h, w))
             if buf is None:
-                if capturing:
-                    raise RuntimeError("t2i_adapter.bind: allocate the buffers before the capture starts")
+                self._refuse_capture(device)
                 self._features[(rows, k, h, w)] = torch.zeros((f_rows, c, h, w), dtype=dtype, device=device).contiguous(
                     memory_format=torch.channels_last)
             elif buf.device != device or buf.dtype != dtype or buf.shape[0] != f_rows:
@@ -114,16 +108,6 @@ class T2IAdapterState(nn.Module):
 
     def bound_rows(self):
         return sorted({key[0] for key in self._features})
-
-    def _rows(self, rows: Optional[int], what: str) -> int:
-        have = self.bound_rows()
-        if rows is None:
-            if len(have) != 1:
-                raise ValueError(f"{what}: pass rows=: this state is bound for the row counts {have} (bind(rows, latent_hw, device) first)")
-            return have[0]
-        if int(rows) not in have:
-            raise ValueError(f"{what}: no buffers for {rows} rows (bound: {have}); call bind(rows, latent_hw, device) first")
-        return int(rows)
 
     def features_for(self, rows: int, k: int, h: int, w: int) -> torch.Tensor:
         buf = self._features.get((int(rows), int(k), int(h), int(w)))
@@ -234,11 +218,7 @@ torch.fx.wrap("t2i_site")
 
 def state_of(module, what: str) -> T2IAdapterState:
     """The T2I-Adapter state of a compiled module, or a ValueError that names the missing compile argument."""
-    st = getattr(module, "t2i_adapter", None)
-    if not isinstance(st, T2IAdapterState):
-        raise ValueError(f"{what}: this UNet was compiled without T2I-Adapter sites; compile it with t2i_adapter=True "
-                         "(optimize_model / compile_unet_from_state_dict / attach_to_diffusers / compile_comfy_unet / patch_comfy_model)")
-    return st
+    return require_state(module, "t2i_adapter", T2IAdapterState, what, "T2I-Adapter sites", "t2i_adapter=True")
 
 
 def check_combination(t2i_adapter, fp8) -> None:

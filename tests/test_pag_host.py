@@ -147,6 +147,29 @@ def test_state_validation_and_state_of():
         pag.state_of(torch.nn.Linear(2, 2), "enable_pag")
 
 
+def test_using_takes_a_latent_size_and_ignores_it():
+    """PAG and SEG share `using(chunks, latent_hw)` (pag.PerturbedRows): PAG carries the latent size, restores it, and computes
+    the same with it as without."""
+    st = pag.PAG()
+    assert isinstance(st, pag.PerturbedRows) and st.latent_hw is None
+    with st.using(2, (16, 16)) as inside:
+        assert inside is st and st.chunks == 2 and st.latent_hw == (16, 16) and st.ident_count(6) == st.tail_count(6) == 3
+        with st.using(3):
+            assert st.chunks == 3 and st.latent_hw == (16, 16) and st.ident_count(6) == 2
+        assert st.chunks == 2 and st.latent_hw == (16, 16)
+    assert st.chunks == 0 and st.latent_hw is None
+    q, k, v = (torch.randn(4, 5, 8, generator=torch.Generator().manual_seed(i)) for i in range(3))
+    with st.using(2):
+        want = pag.attention_pag_wrapper(q, k, v, None, 0.5, 2, 4, st)
+    with st.using(2, (16, 16)):
+        got = pag.attention_pag_wrapper(q, k, v, None, 0.5, 2, 4, st)
+    assert torch.equal(got, want) and torch.equal(got[2:], v[2:]) and not torch.equal(got[:2], v[:2])
+    with pytest.raises(ValueError, match="PAG: chunks must be a non-negative integer"):
+        st.set_chunks(-1)
+    with st.using(4), pytest.raises(ValueError, match="PAG: a UNet batch of 6 rows does not divide into 4 chunks"):
+        st.ident_count(6)
+
+
 # ------------------------------------------------------------------------------------------------ 3. scales and formulas
 def test_adaptive_scales_against_hand_computed_values():
     ts = [999.0, 800.0, 500.0, 1.0]
@@ -195,7 +218,7 @@ def test_loop_rows_conditioning_and_input_blocks(guided):
     lp = _loop(pag_scale=3.0, mode="step", **kw)
     blocks = 3 if guided else 2
     assert lp.x_in.shape[0] == lp.ehs.shape[0] == lp.text_embeds.shape[0] == lp.time_ids.shape[0] == 2 * blocks
-    assert lp.latent.shape[0] == 2 and torch.equal(lp.pag, torch.full((10,), 3.0)) and lp._pag_chunks == blocks
+    assert lp.latent.shape[0] == 2 and torch.equal(lp.pag, torch.full((10,), 3.0)) and lp._perturbed_chunks == blocks and isinstance(lp._perturbed, pag.PAG)
     pos = (torch.randn(2, 3, 8), torch.randn(2, 6), torch.randn(2, 6))
     neg = (torch.randn(2, 3, 8), torch.randn(2, 6), torch.randn(2, 6))
     lp.set_conditioning(*pos, *(neg if guided else ()))
@@ -223,7 +246,7 @@ def test_loop_error_cases_on_the_host():
     with pytest.raises(ValueError, match="guidance_rescale needs guidance_scale"):
         _loop(pag_scale=3.0, guidance_rescale=0.7)
     plain = _loop(_NoUNet(with_pag=False), guidance_scale=5.0)          # without pag_scale nothing about the loop changes
-    assert plain.pag is None and plain.x_in.shape[0] == 4 and plain._pag_chunks == 0
+    assert plain.pag is None and plain.x_in.shape[0] == 4 and plain._perturbed_chunks == 0 and plain._perturbed is None
 
 
 # ------------------------------------------------------------------------------------------------ 5. the C entry points

@@ -171,6 +171,38 @@ def test_state_bind_set_clear_in_place():
         regions.positive_rows(4, 3)
 
 
+def _row_bound_states():
+    from stabletriton_amd import ip_adapter, t2i_adapter
+    return {"regions": lambda: regions.Regions(2, 77, levels=(1, 2)),
+            "ip_adapter": lambda: ip_adapter.IPAdapter((4,), ("mid_block.attn2",), [(8, 8)], levels=(1, 2), like=torch.zeros(1)),
+            "t2i_adapter": lambda: t2i_adapter.T2IAdapterState([("mid_block", 8, 2, None)])}
+
+
+@pytest.mark.parametrize("name", ["regions", "ip_adapter", "t2i_adapter"])
+def test_row_lookup_messages_of_the_three_row_bound_states(name):
+    """`_rows(rows, what)` is one function for the three states that bind buffers per row count: the texts are the ones each state
+    had of its own."""
+    st = _row_bound_states()[name]()
+    want = "who.set: pass rows=: this state is bound for the row counts {} (bind(rows, latent_hw, device) first)"
+    with pytest.raises(ValueError) as e:
+        st._rows(None, "who.set")
+    assert str(e.value) == want.format([])
+    st.bind(2, (4, 4), "cpu")
+    assert st._rows(None, "who.set") == 2 and st._rows(2, "who.set") == 2
+    st.bind(4, (4, 4), "cpu")
+    with pytest.raises(ValueError) as e:
+        st._rows(None, "who.set")
+    assert str(e.value) == want.format([2, 4])
+    with pytest.raises(ValueError) as e:
+        st._rows(3, "who.set")
+    assert str(e.value) == "who.set: no buffers for 3 rows (bound: [2, 4]); call bind(rows, latent_hw, device) first"
+    assert st._rows(4, "who.set") == 4
+    with pytest.raises(ValueError) as e:
+        st.bind(0, (4, 4), "cpu")
+    tail = ", feature_rows 0 (a divisor of rows)" if name == "t2i_adapter" else ""
+    assert str(e.value) == f"{name}.bind: rows 0, latent 4 x 4" + tail
+
+
 def test_weights_are_not_module_state():
     """The weight buffers are not registered with torch: state_dict() / buffers() of a bound compiled module (and of anything
     that holds it) work and do not list them, and a dtype cast of the module leaves them fp32 at their addresses - captured

@@ -99,6 +99,23 @@ def test_seg_and_pag_together_raise():
         replace_backend(fx.symbolic_trace(_meta(TINY)), seg_layers=("mid",), pag_layers=("down_blocks.1",))
 
 
+@pytest.mark.parametrize("layers", [("mid",), ("down_blocks.1", "mid"), (r"up_blocks\.0.*transformer_blocks\.1",)])
+def test_pag_and_seg_choose_the_same_sites(layers):
+    """One site rule and one selection by regular expressions serve both passes."""
+    from stabletriton_amd import pag
+    from stabletriton_amd.optimizers import fuse_attention, insert_pag, insert_seg
+    a, b = fx.symbolic_trace(_meta(TINY)), fx.symbolic_trace(_meta(TINY))
+    fuse_attention(a), fuse_attention(b)
+    assert insert_pag(a, layers) == insert_seg(b, layers) == len(a.pag.sites) > 0
+    assert a.pag.sites == b.seg.sites and a.pag.layers == b.seg.layers == layers
+    at = [i for i, n in enumerate(a.graph.nodes) if n.target is pag.attention_pag_wrapper]
+    assert at == [i for i, n in enumerate(b.graph.nodes) if n.target is seg.attention_seg_wrapper] and len(at) == len(a.pag.sites)
+    for layers_, flag in ((("nowhere",), "pag_layers"), ((), "seg_layers")):
+        insert = insert_pag if flag == "pag_layers" else insert_seg
+        with pytest.raises(ValueError, match=f"^{flag}: "):
+            insert(fx.symbolic_trace(_meta(TINY)), layers_)
+
+
 @pytest.mark.parametrize("spec", [SDXL_BASE, TINY])
 def test_default_graph_is_unchanged_and_other_passes_still_fire(spec):
     a = replace_backend(fx.symbolic_trace(_meta(spec)))
@@ -202,6 +219,22 @@ def test_state_validation_and_state_of():
         seg.state_of(torch.nn.Linear(2, 2), "enable_seg")
 
 
+def test_using_without_a_latent_size_raises_and_changes_nothing():
+    from stabletriton_amd import pag
+    st = seg.SEG()
+    assert isinstance(st, pag.PerturbedRows) and not hasattr(st, "ident_count")
+    with pytest.raises(ValueError, match="SEG: using\\(chunks, latent_hw\\) needs the call's latent size"), st.using(2):
+        pass
+    assert st.chunks == 0 and st.latent_hw is None
+    with st.using(0):                                          # chunks 0 needs none: ordinary attention
+        assert st.chunks == 0 and st.latent_hw is None and st.tail_count(6) == 0
+    with pytest.raises(ValueError, match="SEG: chunks must be a non-negative integer"), st.using(-1, (16, 16)):
+        pass
+    assert st.chunks == 0 and st.latent_hw is None
+    with st.using(4, (16, 16)), pytest.raises(ValueError, match="SEG: a UNet batch of 6 rows does not divide into 4 chunks"):
+        st.tail_count(6)
+
+
 def test_parameter_rows_are_written_in_place():
     st = seg.SEG()
     st.bind((16, 16), "cpu")
@@ -245,7 +278,7 @@ def test_loop_rows_tables_and_bound_state(guided):
     lp = _loop(unet, seg_scale=3.0, seg_sigma=1.0, mode="step", **kw)
     blocks = 3 if guided else 2
     assert lp.x_in.shape[0] == lp.ehs.shape[0] == 2 * blocks and lp.latent.shape[0] == 2
-    assert torch.equal(lp.pag, torch.full((10,), 3.0)) and lp._seg_chunks == blocks and lp._pag_chunks == 0
+    assert torch.equal(lp.pag, torch.full((10,), 3.0)) and lp._perturbed_chunks == blocks and lp._perturbed is unet.seg
     assert unet.seg.sigma == 1.0 and sorted(g for _, _, g in unet.seg._rows) == [(3, 2), (6, 4), (12, 8), (24, 16)]
     pos = (torch.randn(2, 3, 8), torch.randn(2, 6), torch.randn(2, 6))
     neg = (torch.randn(2, 3, 8), torch.randn(2, 6), torch.randn(2, 6))
@@ -279,7 +312,7 @@ def test_loop_error_cases_on_the_host():
     with pytest.raises(ValueError, match="set_seg"):
         _loop(seg_scale=[1.0, 2.0])
     plain = _loop(_NoUNet(with_seg=False), guidance_scale=5.0)      # without seg_scale nothing about the loop changes
-    assert plain.pag is None and plain.x_in.shape[0] == 4 and plain._seg_chunks == 0 and plain._seg_state is None
+    assert plain.pag is None and plain.x_in.shape[0] == 4 and plain._perturbed_chunks == 0 and plain._perturbed is None
 
 
 # ------------------------------------------------------------------------------------------------ 6. the C entry points

@@ -139,7 +139,7 @@ def main():
                  "cfg_2b": make_loop(gm, spec, latent, dt, dev, args.steps, x),
                  "plain_3b": make_loop(gm, spec, latent, dt, dev, args.steps, x, pag_scale=S),
                  "pag0_3b": make_loop(gm, spec, latent, dt, dev, args.steps, x, pag_scale=0.0)}
-        loops["plain_3b"]._pag_chunks = 0          # the same 3B rows and update, every attention ordinary (set before its capture)
+        loops["plain_3b"]._perturbed_chunks = 0    # the same 3B rows and update, every attention ordinary (set before its capture)
         times = {k: [] for k in loops}
         finite = True
         for i in range(args.runs + 1):                             # (round 0 captures and warms every graph up)

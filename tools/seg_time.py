@@ -115,7 +115,7 @@ def main():
     with torch.no_grad():
         seg_loop = make_loop(gm, spec, latent, dt, dev, args.steps, x, seg_scale=S, seg_sigma=INF)
         plain = make_loop(gm, spec, latent, dt, dev, args.steps, x, seg_scale=S)
-        plain._seg_chunks = 0                    # the same 3B rows and update, every attention ordinary (set before its capture)
+        plain._perturbed_chunks = 0              # the same 3B rows and update, every attention ordinary (set before its capture)
         pag_loop = make_loop(gm_pag, spec, latent, dt, dev, args.steps, x, pag_scale=S)
         # (name, loop, sigma to set before the run: the two SEG entries are ONE captured graph under two parameter rows)
         order = [("seg_inf_3b", seg_loop, INF), ("seg_10_3b", seg_loop, 10.0), ("plain_3b", plain, None), ("pag_3b", pag_loop, None)]
