@@ -550,6 +550,29 @@ int st_pag_sde_step(float* latent, const void* eps, void* next_in, float* histor
 int st_residual_add(void* x, const void* f, int rows, int f_rows, long HW, int C, const float* scale_table, int n_steps,
                     const int* step, int dtype, float* stats, int stat_rows, int stat_tiles, void* stream);
 
+/* ---- Tiled denoising (no reference counterpart: MultiDiffusion / Mixture of Diffusers, diffusers' StableDiffusionPanoramaPipeline,
+ * ComfyUI's "Tiled Diffusion").  Added after ABI 18 without a bump: new entry points, no existing signature or contract changed.
+ *
+ * A canvas (rows, H, W, C) and its T = ny * nx windows (rows * T, h, w, C), both dense NHWC of `dtype` (ST_BF16, ST_F16, ST_F32), C a
+ * multiple of 4; window t = iy * nx + ix starts at row ys[iy] and column xs[ix], and with wrap_w its columns are taken mod W.  ys and
+ * xs are HOST arrays of 1 to 16 ints each: the entry points check them and pass them by value in the launch arguments.  Rejected
+ * before any launch: a window outside the canvas (ys[i] + h > H, xs[i] + w > W; with wrap_w xs[i] outside [0, W)), a canvas row or
+ * column no window covers, h > H or w > W, a pointer not aligned to one 4-element vector, canvas and windows whose byte ranges
+ * overlap (st_tile_blend: also a weight map that overlaps the canvas).
+ *
+ * st_tile_gather: windows[r * T + t][py][px][:] = canvas[r][ys[iy] + py][(xs[ix] + px) mod W][:], a copy, bit exact.
+ * st_tile_blend:  for every canvas pixel (Y, X) of row r, over the n windows that cover it in ascending t, with e_t the window's
+ *   element there and w_t = weights[py * w + px] at the pixel's position inside window t (weights: fp32 (h, w) DEVICE map, read when
+ *   the kernel runs - a captured graph sees new values):
+ *     n == 1: canvas = e_t, the bits unchanged whatever the weight;
+ *     else    num = fma(w_t, float(e_t), num) from 0, den += w_t, canvas = round(num / den) to `dtype`.
+ *   One thread per canvas pixel vector, no atomics: two launches give the same bits.  Weights are expected finite and positive.
+ * 64-bit index arithmetic throughout (csrc/tiles.hip). */
+int st_tile_gather(const void* canvas, void* windows, int rows, int H, int W, int h, int w, int C, const int* ys, int ny,
+                   const int* xs, int nx, int wrap_w, int dtype, void* stream);
+int st_tile_blend(const void* windows, void* canvas, const float* weights, int rows, int H, int W, int h, int w, int C,
+                  const int* ys, int ny, const int* xs, int nx, int wrap_w, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -70,6 +70,8 @@ SIGNATURES = {
     "st_seg_blur": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _i, _p, _z, _p]),
     "st_attention_seg": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _i, _i, _p, _p, _z, _p]),
     "st_residual_add": (_i, [_p, _p, _i, _i, _l, _i, _p, _i, _p, _i, _p, _i, _i, _p]),
+    "st_tile_gather": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
+    "st_tile_blend": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
 }
 
 

@@ -1956,3 +1956,45 @@ def residual_add(x: torch.Tensor, f: torch.Tensor, scale_table: torch.Tensor, st
                                        step.data_ptr(), _C.dtype_code(x.dtype), stats.buf.data_ptr() if ok else None,
                                        stats.rows if ok else 0, tiles, _C.stream_ptr()), "residual_add")
     return stats if ok else None
+
+
+# ----------------------------------------------------------------------------- tiled denoising: windows of a canvas
+def _tile_arguments(what: str, canvas: torch.Tensor, windows: torch.Tensor, ys, xs):
+    """Shape and layout checks shared by tile_gather / tile_blend; the geometry itself (windows inside the canvas, every pixel covered,
+    alignment, disjoint byte ranges) is checked by the C entry point before it launches."""
+    _C.require_device(canvas, windows)
+    import ctypes
+    ys, xs = [int(v) for v in ys], [int(v) for v in xs]
+    T = len(ys) * len(xs)
+    cl = torch.channels_last
+    if canvas.dim() != 4 or windows.dim() != 4 or canvas.dtype != windows.dtype or T == 0 or windows.shape[0] != canvas.shape[0] * T \
+            or windows.shape[1] != canvas.shape[1]:
+        raise BackendError(f"{what}: canvas {tuple(canvas.shape)} {canvas.dtype} and windows {tuple(windows.shape)} {windows.dtype} must be "
+                           f"(rows, C, H, W) and (rows * {T}, C, h, w) of one dtype")
+    if not (canvas.is_contiguous(memory_format=cl) and windows.is_contiguous(memory_format=cl)):
+        raise BackendError(f"{what}: canvas and windows must be dense channels_last (NHWC) tensors")
+    if canvas.shape[1] % 4:
+        raise BackendError(f"{what}: channel count {canvas.shape[1]} must be a multiple of 4")
+    rows, Cc, H, W = canvas.shape
+    geometry = (rows, H, W, windows.shape[2], windows.shape[3], Cc, (ctypes.c_int * len(ys))(*ys), len(ys), (ctypes.c_int * len(xs))(*xs), len(xs))
+    return geometry
+
+
+def tile_gather(canvas: torch.Tensor, windows: torch.Tensor, ys, xs, wrap_w: bool = False) -> None:
+    """windows[r * T + t, :, py, px] = canvas[r, :, ys[iy] + py, (xs[ix] + px) mod W], t = iy * len(xs) + ix (csrc/tiles.hip): a bit-exact
+    copy.  canvas (rows, C, H, W) and windows (rows * T, C, h, w) channels_last of one dtype, C a multiple of 4; ys, xs host ints."""
+    g = _tile_arguments("tile_gather", canvas, windows, ys, xs)
+    _C.check(_C.load().st_tile_gather(canvas.data_ptr(), windows.data_ptr(), *g, int(bool(wrap_w)), _C.dtype_code(canvas.dtype),
+                                      _C.stream_ptr()), "tile_gather")
+
+
+def tile_blend(windows: torch.Tensor, canvas: torch.Tensor, weights: torch.Tensor, ys, xs, wrap_w: bool = False) -> None:
+    """canvas = the per-pixel weighted mean of the windows that cover it, in ascending t, fp32 fma chain and one division (a pixel
+    under one window takes that window's bits); `weights` an fp32 (h, w) device map the kernel reads when it runs."""
+    g = _tile_arguments("tile_blend", canvas, windows, ys, xs)
+    _C.require_device(weights)
+    if weights.dtype != torch.float32 or tuple(weights.shape) != tuple(windows.shape[2:]) or not weights.is_contiguous():
+        raise BackendError(f"tile_blend: weights must be a contiguous fp32 (h, w) = {tuple(windows.shape[2:])} map, got {weights.dtype} "
+                           f"{tuple(weights.shape)}")
+    _C.check(_C.load().st_tile_blend(windows.data_ptr(), canvas.data_ptr(), weights.data_ptr(), *g, int(bool(wrap_w)),
+                                     _C.dtype_code(canvas.dtype), _C.stream_ptr()), "tile_blend")

@@ -67,6 +67,20 @@ T2I-Adapter structural control (`set_t2i_adapter`, `set_t2i_adapter_scale`; t2i_
 under a per-step scale table (`scale` for the first int(n_steps * factor) steps, 0 after).  The sites read the table at
 `step_ids[i:i+1]` (modes loop / eager) or at the step counter (mode step); a step at scale 0 - every step until `set_t2i_adapter` -
 writes nothing: the bits of a UNet compiled without sites.
+
+Tiled denoising (`tile_hw`, `tile_stride`, `tile_wrap_w`, `tile_weights`, `set_tile_weights`; tiles.py) makes `latent_hw` a canvas
+larger than the UNet denoises in one piece (MultiDiffusion; with Gaussian weights Mixture of Diffusers): the UNet runs on the T
+overlapping windows of the canvas as batch rows - `x_in`, the conditioning buffers, the hoisted context and the time tables have
+B * blocks * T rows, row (blk * B + b) * T + t - while `latent`, `history`, the seeds' noise, the canvas noise prediction and a
+canvas-sized `x_step` keep the canvas shape.  One step is UNet on the windows -> `st_tile_blend` (per canvas pixel the weighted mean of
+the covering windows' predictions) -> the loop's own update kernel, unchanged, on the canvas -> `st_tile_gather` (the next input cut
+into windows): two more launches per step, every sampler and guidance form as before.  Guidance rescale therefore takes its statistics
+over the canvas, not per window.  The weight map is a device buffer the blend reads by address: `set_tile_weights` is an in-place write,
+before or after `capture()`.  `set_conditioning` takes B rows (one prompt for all of a sample's windows) or B * T rows (one prompt per
+window, sample-major).  PAG and SEG work (their row block is outermost; the perturbed scope and SEG's blur see the window size).  UNets
+compiled with `regions`, `ip_adapter` or `t2i_adapter` are refused: their states bind per latent size and row count, and cropping them
+per window is not built.  The fp8 plan is allowed with tiles and not covered by tests.  `tile_hw=None` is the untiled loop exactly:
+`x_step is x_in`, no further buffers or launches.
 """
 from __future__ import annotations
 
@@ -89,7 +103,8 @@ class DenoiseLoop:
                  guidance_scale: Optional[Union[float, Sequence[float]]] = None,
                  guidance_rescale: Optional[Union[float, Sequence[float]]] = None,
                  pag_scale: Optional[Union[float, Sequence[float]]] = None,
-                 seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf")):
+                 seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf"),
+                 tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform"):
         assert mode in ("loop", "step", "eager")
         if seg_scale is not None and pag_scale is not None:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
@@ -124,8 +139,24 @@ class DenoiseLoop:
         # both sides multiples of 4: the UNet halves the latent twice (Downsample2D, unet_pt.py:246-256) and doubles it back
         lh, lw = (int(latent_hw[0]), int(latent_hw[1])) if isinstance(latent_hw, (tuple, list)) else (int(latent_hw), int(latent_hw))
         self.batch = batch
+        # tiled denoising: (lh, lw) is the canvas, the UNet sees its T windows of (th, tw) as batch rows (window-minor)
+        self.tile_grid = None
+        th, tw, T = lh, lw, 1
+        if tile_hw is not None:
+            from . import tiles as _tiles
+            for name, cls in (("regions", _regions.Regions), ("ip_adapter", _ip.IPAdapter), ("t2i_adapter", _t2i.T2IAdapterState)):
+                if compiled_state(unet, name, cls) is not None:
+                    raise ValueError(f"DenoiseLoop: tile_hw cannot be combined with a UNet compiled with {name}: its state binds per latent "
+                                     "size and row count, and cropping it per window is not built")
+            self.tile_grid = _tiles.TileGrid((lh, lw), tile_hw, tile_stride, tile_wrap_w)
+            (th, tw), T = self.tile_grid.tile_hw, self.tile_grid.T
+            tile_map = _tiles.weight_map(tile_weights, (th, tw))
+        elif tile_stride is not None or tile_wrap_w or not (isinstance(tile_weights, str) and tile_weights == "uniform"):
+            raise ValueError("DenoiseLoop: tile_stride, tile_wrap_w and tile_weights need tile_hw")
+        self._T = T
         # guidance: the UNet sees [negative | positive]; with pag_scale one more block, [.. | perturbed]
-        rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
+        canvas_rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
+        rows = canvas_rows * T
         if self._regions_state is not None:                # the weight buffers of this row count: allocated once, "off"
             self._regions_state.bind(rows, (lh, lw), dev)
         self._ip_state = compiled_state(unet, "ip_adapter", _ip.IPAdapter)
@@ -138,12 +169,19 @@ class DenoiseLoop:
         if self._t2i_state is not None:
             self._t2i_state.bind(rows, (lh, lw), dev, dtype=dtype, feature_rows=batch)
             self.t2i_table = torch.zeros(n, dtype=torch.float32, device=dev)
-        self._latent_hw = (lh, lw)
+        self._latent_hw = (th, tw)                         # what the UNet sees: the window when tiled
         if isinstance(self._perturbed, seg.SEG):           # the blur's parameter rows of this latent size: allocated once, outside capture
-            self._perturbed.bind((lh, lw), dev)
+            self._perturbed.bind((th, tw), dev)
             self._perturbed.set_sigma(seg_sigma)
         self.latent = torch.zeros((batch, 4, lh, lw), dtype=torch.float32, device=dev).contiguous(memory_format=cl)
-        self.x_in = torch.zeros((rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
+        self.x_in = torch.zeros((rows, 4, th, tw), dtype=dtype, device=dev).contiguous(memory_format=cl)
+        # what the update kernels write: the UNet's own input, or - tiled - a canvas the windows are gathered from; with it the
+        # canvas noise prediction the windows' predictions are blended into, and the blend's weight map
+        self.x_step, self.eps_canvas, self.tile_weights = self.x_in, None, None
+        if self.tile_grid is not None:
+            self.x_step = torch.zeros((canvas_rows, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
+            self.eps_canvas = torch.zeros_like(self.x_step)
+            self.tile_weights = tile_map.to(dev)
         self.ehs = torch.zeros((rows, tokens, cross_dim), dtype=dtype, device=dev)
         self.text_embeds = torch.zeros((rows, pooled_dim), dtype=dtype, device=dev)
         self.time_ids = torch.zeros((rows, n_time_ids), dtype=dtype, device=dev)
@@ -239,14 +277,19 @@ class DenoiseLoop:
                          negative_text_embeds=None, negative_time_ids=None) -> None:
         """Prompt conditioning, B rows each.  With guidance the negative prompt's rows go first; a missing negative text
         state or pooled embedding is zeros (SDXL's force_zeros_for_empty_prompt), missing negative time ids copy the
-        positive ones."""
+        positive ones.  A tiled loop takes B rows (repeated over a sample's T windows) or B * T rows (one prompt per window,
+        sample-major and window-minor), for the negatives likewise."""
         st = self._regions_state
         if (st is not None and negative_encoder_hidden_states is not None and st.R > 1
                 and negative_encoder_hidden_states.shape[1] == st.seg_len):
             # one negative prompt for the whole picture: the same text in every segment
             negative_encoder_hidden_states = negative_encoder_hidden_states.repeat(1, st.R, 1)
         negatives = (negative_encoder_hidden_states, negative_text_embeds, negative_time_ids)
-        b = self.batch
+        b = self.batch * self._T                           # rows of one block
+        if self.tile_grid is not None:
+            encoder_hidden_states, text_embeds, time_ids, *negatives = (
+                self._window_rows(t) for t in (encoder_hidden_states, text_embeds, time_ids, *negatives))
+            negative_encoder_hidden_states, negative_text_embeds, negative_time_ids = negatives
         if self.guidance is None:
             if any(t is not None for t in negatives):
                 raise ValueError("set_conditioning: negative conditioning needs a loop built with guidance_scale")
@@ -267,6 +310,27 @@ class DenoiseLoop:
                     buf[:b].copy_(neg)
         self._conditioned = True
         self._rederive_conditioning()
+
+    def _window_rows(self, t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """Tiled: B rows -> each repeated over its sample's T windows; B * T rows -> as they are."""
+        if t is None:
+            return None
+        B, T = self.batch, self._T
+        if t.shape[0] == B * T:
+            return t
+        if t.shape[0] == B:
+            return t.repeat_interleave(T, dim=0)
+        raise ValueError(f"set_conditioning: a tiled loop takes B = {B} rows (one prompt per sample) or B * T = {B * T} rows (one per "
+                         f"window), got {t.shape[0]}")
+
+    def set_tile_weights(self, weights) -> None:
+        """The blend's weight map: "uniform", "gaussian" (tiles.gaussian_weights, sigma 0.1) or an (h, w) tensor, finite and positive
+        (checked here, on the host).  An in-place write of the device map the blend kernel reads by address: legal before or after
+        `capture()`, never a new capture."""
+        if self.tile_grid is None:
+            raise ValueError("set_tile_weights: this loop was built without tile_hw")
+        from . import tiles
+        self.tile_weights.copy_(tiles.weight_map(weights, self.tile_grid.tile_hw))
 
     def _rederive_conditioning(self) -> None:
         """Everything the loop computes once per prompt from the weights and its own static `ehs`, `text_embeds` and
@@ -511,11 +575,17 @@ class DenoiseLoop:
 
     def _write_input(self, scale: float) -> None:
         if self.guidance is None and self.pag is None:
-            self.x_in.copy_(self.latent * scale)
-            return
-        v = self.latent * scale
-        for r in range(self.x_in.shape[0] // self.batch):      # every row block sees the same latent
-            self.x_in[r * self.batch:(r + 1) * self.batch].copy_(v)
+            self.x_step.copy_(self.latent * scale)
+        else:
+            v = self.latent * scale
+            for r in range(self.x_step.shape[0] // self.batch):      # every row block sees the same latent
+                self.x_step[r * self.batch:(r + 1) * self.batch].copy_(v)
+        self._gather_windows()
+
+    def _gather_windows(self) -> None:
+        if self.tile_grid is not None:                     # the UNet's input: the windows of the canvas the update wrote
+            g = self.tile_grid
+            ops.tile_gather(self.x_step, self.x_in, g.ys, g.xs, g.wrap_w)
 
     def _recalibrate(self, i: int) -> None:
         """fp8 plan only: a trajectory starts from scales measured on its own first evaluation (not on the last step of
@@ -561,33 +631,42 @@ class DenoiseLoop:
         ops.step_advance(self.step, self.n_steps)
 
     def _update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
+        if self.tile_grid is not None:                     # the windows' predictions -> one prediction per canvas pixel
+            g = self.tile_grid
+            ops.tile_blend(eps, self.eps_canvas, self.tile_weights, g.ys, g.xs, g.wrap_w)
+            eps = self.eps_canvas
+        self._sampler_update(eps, step)
+        self._gather_windows()
+
+    def _sampler_update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
         if self.pag is not None:
             if isinstance(self.tables, SDETables):
-                ops.pag_sde_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+                ops.pag_sde_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
                                  self.pag, self.guidance, self.rescale, self.cfg_workspace)
             elif self.coef is not None:
-                ops.pag_dpmpp2m_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.pag,
+                ops.pag_dpmpp2m_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.pag,
                                      self.guidance, self.rescale, self.cfg_workspace)
             else:
-                ops.pag_euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.guidance, self.pag, step, self.rescale,
+                ops.pag_euler_step(self.latent, eps, self.x_step, self.dsigma, self.in_scale, self.guidance, self.pag, step, self.rescale,
                                    self.cfg_workspace)
         elif isinstance(self.tables, SDETables):
-            ops.sde_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+            ops.sde_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
                          self.guidance, self.rescale, self.cfg_workspace)
         elif self.coef is not None:
-            ops.dpmpp2m_step(self.latent, eps, self.x_in, self.history, self.coef, self.in_scale, step, self.start, self.guidance,
+            ops.dpmpp2m_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.guidance,
                              self.rescale, self.cfg_workspace)
         elif self.guidance is None:
-            ops.euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, step)
+            ops.euler_step(self.latent, eps, self.x_step, self.dsigma, self.in_scale, step)
         else:
-            ops.cfg_euler_step(self.latent, eps, self.x_in, self.dsigma, self.in_scale, self.guidance, step, self.rescale,
+            ops.cfg_euler_step(self.latent, eps, self.x_step, self.dsigma, self.in_scale, self.guidance, step, self.rescale,
                                self.cfg_workspace)
 
     # ---- capture / run -------------------------------------------------------------------
     def capture(self, warmup: int = 1) -> None:
         if self.mode == "eager" or self.graph is not None:
             return
-        keep = (self.latent.clone(), self.x_in.clone(), self.step.clone(), None if self.history is None else self.history.clone())
+        keep = (self.latent.clone(), self.x_in.clone(), self.step.clone(), None if self.history is None else self.history.clone(),
+                None if self.tile_grid is None else self.x_step.clone())
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
@@ -616,6 +695,8 @@ class DenoiseLoop:
         self.latent.copy_(keep[0]); self.x_in.copy_(keep[1]); self.step.copy_(keep[2])
         if keep[3] is not None:
             self.history.copy_(keep[3])
+        if keep[4] is not None:
+            self.x_step.copy_(keep[4])
 
     def run_steps(self, k: int) -> None:
         """Advance exactly k denoise steps from the current state (asynchronous)."""
