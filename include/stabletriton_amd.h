@@ -550,6 +550,22 @@ int st_pag_sde_step(float* latent, const void* eps, void* next_in, float* histor
 int st_residual_add(void* x, const void* f, int rows, int f_rows, long HW, int C, const float* scale_table, int n_steps,
                     const int* step, int dtype, float* stats, int stat_rows, int stat_tiles, void* stream);
 
+/* st_residual_add_grouped (ControlNet's skip and middle residuals; likewise added after ABI 18 without a bump): 1..16 sites of
+ * st_residual_add in ONE launch whose grid is the concatenation of the sites' own grids.  `sites` is a HOST array of descriptors,
+ * read at the call and passed to the kernel by value (a captured launch keeps them): per site x, r (the residual, r_rows a divisor
+ * of rows, row n reads r[n % r_rows]), stats / stat_rows / stat_tiles as in st_residual_add (stats NULL, 0, 0: add only).
+ * `site_weights` is DEVICE memory of n_sites fp32 values, or NULL = all 1; scale_table, n_steps and step as in st_residual_add.
+ * Site k runs under s_k = fl32(scale_table[i] * site_weights[k]):
+ *   s_k == 0: the site's workgroups leave after reading those two values; nothing of its x, r, stats is read or written;
+ *   else      st_residual_add's arithmetic on that site with s = s_k: the same bits in x and in the partials as that entry point
+ *             gives with a table entry s_k (one fp32 fma and one rounding per element; partials of the values as stored over the
+ *             producer's own tiles; fixed reduction shape, no atomics, two launches give the same bits).
+ * Per site the requirements of st_residual_add; over the whole call no two byte ranges among every x, r and stats may overlap.
+ * All sites share `dtype` (csrc/t2i_adapter.hip). */
+typedef struct { void* x; const void* r; float* stats; int rows, r_rows; long HW; int C; int stat_rows, stat_tiles; } st_residual_site;
+int st_residual_add_grouped(const st_residual_site* sites, int n_sites, const float* site_weights, const float* scale_table,
+                            int n_steps, const int* step, int dtype, void* stream);
+
 /* ---- Tiled denoising (no reference counterpart: MultiDiffusion / Mixture of Diffusers, diffusers' StableDiffusionPanoramaPipeline,
  * ComfyUI's "Tiled Diffusion").  Added after ABI 18 without a bump: new entry points, no existing signature or contract changed.
  *

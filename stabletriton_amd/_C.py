@@ -70,6 +70,7 @@ SIGNATURES = {
     "st_seg_blur": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _i, _p, _z, _p]),
     "st_attention_seg": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _i, _i, _p, _p, _z, _p]),
     "st_residual_add": (_i, [_p, _p, _i, _i, _l, _i, _p, _i, _p, _i, _p, _i, _i, _p]),
+    "st_residual_add_grouped": (_i, [_p, _i, _p, _p, _i, _p, _i, _p]),
     "st_tile_gather": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
     "st_tile_blend": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
 }
@@ -80,6 +81,14 @@ class KVSegment(C.Structure):
     """st_kv_segment: one key/value segment of st_attention_segments (strides in elements; bs*: between batch entries)."""
     _fields_ = [("k", _p), ("v", _p), ("ldk", _l), ("ldv", _l), ("bsk", _l), ("bsv", _l), ("len", _i)]
 
+
+class ResidualSite(C.Structure):
+    """st_residual_site: one site of st_residual_add_grouped (stats None, stat_rows = stat_tiles = 0: add only)."""
+    _fields_ = [("x", _p), ("r", _p), ("stats", _p), ("rows", _i), ("r_rows", _i), ("HW", _l), ("C", _i), ("stat_rows", _i),
+                ("stat_tiles", _i)]
+
+
+RESIDUAL_MAX_SITES = 16      # st_residual_add_grouped's largest site count
 
 _lib = None
 

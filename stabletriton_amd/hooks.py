@@ -61,6 +61,7 @@ class _HoistedUNet(nn.Module):
         self._ip_masks = {}                       # set_ip_adapter_masks: slot -> masks
         self._ip_applied = {}                     # ... rows -> the latent size the buffers of that row count were last written for
         self._t2i_last = None                     # T2I-Adapter: (rows, the residual tensors last copied - HELD, not their addresses -, their versions)
+        self._cn_last = None                      # ControlNet: likewise
 
     def refresh_weights(self) -> int:
         """Re-derive fused / folded weight buffers after an in-place weight update (also done at every new prompt).
@@ -313,6 +314,42 @@ class _HoistedUNet(nn.Module):
         if state.host_scale != 1.0:
             state.set_scale(1.0)
 
+    # ---- ControlNet residuals (controlnet.py): static buffers the sites' one launch reads by address; the captured graphs stay ----
+    def _cn_state(self):
+        from . import controlnet
+        return compiled_state(self.compiled, "controlnet", controlnet.ControlNetState)
+
+    def _apply_controlnet(self, sample: torch.Tensor, residuals) -> None:
+        """As `_apply_t2i`, for the ControlNet sites: one tensor per site, the skips' in encoder order and the middle block's last
+        (None: zeros there), already scaled by the pipeline and summed over a MultiControlNet, so the scale is 1; `residuals` None:
+        scale 0, nothing else is touched.  The very tensors of the previous call at their versions are not copied again (the wrapper
+        HOLDS them until the next call with others)."""
+        state = self._cn_state()
+        if state is None:
+            return
+        rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
+        if not torch.cuda.is_current_stream_capturing():
+            state.bind(rows, hw, sample.device, dtype=self.compute_dtype)
+        if residuals is None:
+            if state.host_scale != 0.0:
+                state.clear()
+            return
+        if len(residuals) != len(state.sites):
+            raise ValueError(f"ControlNet residuals: {len(state.sites)} tensors expected, {len(state.sites) - 1} skip residuals and the middle "
+                             f"block's, got {len(residuals)}")
+        versions = tuple(None if r is None else r._version for r in residuals)
+        last = self._cn_last
+        same = (last is not None and last[0] == rows and last[2] == versions and len(last[1]) == len(residuals)
+                and all(a is b for a, b in zip(last[1], residuals)))
+        if not same:
+            shapes = state.site_shapes(hw)
+            full = [torch.zeros((1,) + shapes[k], dtype=self.compute_dtype, device=sample.device) if r is None else r
+                    for k, r in enumerate(residuals)]
+            state.set(full, None, rows)
+            self._cn_last = (rows, list(residuals), versions)
+        if state.host_scale != 1.0:
+            state.set_scale(1.0)
+
     def _context_for(self, ehs: torch.Tensor) -> tuple:
         """Static K/V context buffers for this prompt.  Fast path: the very tensor object the cache was built from, at the
         version it had then.  A different object of the same shape (ComfyUI re-concatenates cond | uncond on every call) is
@@ -378,7 +415,7 @@ class _HoistedUNet(nn.Module):
                     run_once()          # the very first evaluation creates the scale slots; after it this trajectory starts like every later one
             recalibrate_fp8(self.compiled, run_once)
 
-    def _run(self, sample, timesteps, ehs, cond, t2i=None):
+    def _run(self, sample, timesteps, ehs, cond, t2i=None, controlnet=None):
         # (.to() is the identity when the caller already computes in this dtype: an fp16 pipeline over an fp16 module)
         io_dtype = sample.dtype
         dev = sample.device
@@ -386,6 +423,7 @@ class _HoistedUNet(nn.Module):
         self._apply_ip_adapter(sample)
         self._apply_seg(sample)
         self._apply_t2i(sample, t2i)
+        self._apply_controlnet(sample, controlnet)
         self._context_for(ehs)
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor(float(timesteps), dtype=torch.float32)
@@ -448,9 +486,20 @@ class DiffusersUNet(_HoistedUNet):
                                           "by the compiled UNet: only down_intrablock_additional_residuals (T2I-Adapter) are")
             if down_intrablock_additional_residuals is not None:
                 t2i = list(down_intrablock_additional_residuals)
+        cn = None
+        cn_state = self._cn_state()
+        if cn_state is not None:
+            # compiled with controlnet=True: the ControlNet pipeline's residuals (already scaled by controlnet_conditioning_scale and
+            # summed over a MultiControlNet) are honoured, the T2I-Adapter's are refused
+            if down_intrablock_additional_residuals is not None:
+                raise NotImplementedError("down_intrablock_additional_residuals (T2I-Adapter) are not supported by a UNet compiled with "
+                                          "controlnet=True: only down_block_additional_residuals / mid_block_additional_residual are")
+            if down_block_additional_residuals is not None or mid_block_additional_residual is not None:
+                down = list(down_block_additional_residuals) if down_block_additional_residuals is not None else [None] * (len(cn_state.sites) - 1)
+                cn = down + [mid_block_additional_residual]
         cd = self.compute_dtype
         cond = {"text_embeds": added_cond_kwargs["text_embeds"].to(cd), "time_ids": added_cond_kwargs["time_ids"].to(cd)}
-        out = self._run(sample, timestep, encoder_hidden_states, cond, t2i)
+        out = self._run(sample, timestep, encoder_hidden_states, cond, t2i, cn)
         if return_dict:
             from types import SimpleNamespace
             return SimpleNamespace(sample=out)
@@ -459,7 +508,8 @@ class DiffusersUNet(_HoistedUNet):
 
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                                 region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> DiffusersUNet:
+                                 region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
+                                 controlnet: bool = False) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
@@ -473,7 +523,9 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     `load_ip_adapter`, `set_ip_adapter_image`, `set_ip_adapter_scale`, `set_ip_adapter_masks`, `unload_ip_adapter` drive it;
     `added_cond_kwargs["image_embeds"]` is not read.
     `t2i_adapter=True` compiles the T2I-Adapter residual sites in (t2i_adapter.py): `down_intrablock_additional_residuals` of a call
-    are then added at the sites (None: off, at no cost), ControlNet's residual arguments raise."""
+    are then added at the sites (None: off, at no cost), ControlNet's residual arguments raise.
+    `controlnet=True` compiles the ControlNet sites in (controlnet.py; not with `t2i_adapter`): `down_block_additional_residuals` and
+    `mid_block_additional_residual` of a call are then added for the decoder (None: off), the T2I-Adapter's argument raises."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
@@ -481,18 +533,19 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
-                              ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
+                              ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                        regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False):
+                        regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
+                        controlnet: bool = False):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
                                              regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers,
-                                             t2i_adapter=t2i_adapter)
+                                             t2i_adapter=t2i_adapter, controlnet=controlnet)
     return pipe
 
 
@@ -502,8 +555,11 @@ class ComfyUNet(_HoistedUNet):
     def forward(self, x, timesteps=None, context=None, y=None, control=None, transformer_options: Optional[dict] = None, **kwargs):
         if timesteps is None or context is None or y is None:
             raise ValueError("ComfyUNet needs timesteps, context (text states) and y (pooled text | size/crop features)")
-        t2i = None
-        if control is not None:
+        t2i = cn = None
+        if control is not None and self._cn_state() is not None:
+            from . import controlnet
+            cn = controlnet.comfy_residuals(self._cn_state(), control)      # a ControlNet's output / middle entries; anything else raises
+        elif control is not None:
             state = self._t2i_state()
             if state is None:
                 raise NotImplementedError("ControlNet residuals (`control`) are not supported by the compiled UNet")
@@ -514,11 +570,12 @@ class ComfyUNet(_HoistedUNet):
             raise NotImplementedError("transformer_options patches are not supported by the compiled UNet")
         if y.shape[0] != x.shape[0] or context.shape[0] != x.shape[0]:
             raise ValueError("x, context and y must share the batch dimension")
-        return self._run(x, timesteps, context, y.to(self.compute_dtype), t2i)
+        return self._run(x, timesteps, context, y.to(self.compute_dtype), t2i, cn)
 
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
-                       region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> ComfyUNet:
+                       region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
+                       controlnet: bool = False) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
@@ -527,17 +584,22 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
     (the IPAdapter nodes), driven by `load_ip_adapter` / `set_ip_adapter_image` / `set_ip_adapter_scale` / `set_ip_adapter_masks` /
     `unload_ip_adapter`.  `seg_layers=("mid",)`: with smoothed-energy sites (the SEG node); its extra, fully perturbed call is
     `enable_seg(1, sigma)`.  `t2i_adapter=True`: with T2I-Adapter residual sites: `control={"input": [...], "middle": [...]}` of a call
-    is consumed the way ComfyUI's apply_control does (from the end of each list, None entries skipped) and must land on the sites."""
+    is consumed the way ComfyUI's apply_control does (from the end of each list, None entries skipped) and must land on the sites.
+    `controlnet=True`: with ControlNet sites (not with `t2i_adapter`): `control={"output": [...], "middle": [...]}` of a call, entry i of
+    `output` being skip i in encoder order (ComfyUI pops from the end while the decoder consumes its skips last-first); a non-empty
+    `"input"` raises."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                              region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
+                              region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
+                              controlnet=controlnet)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
-                      regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> ComfyUNet:
+                      regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
+                      controlnet: bool = False) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
     adapter = compile_comfy_unet(unet, cuda_graph, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
-                                 ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
+                                 ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -1958,6 +1958,66 @@ def residual_add(x: torch.Tensor, f: torch.Tensor, scale_table: torch.Tensor, st
     return stats if ok else None
 
 
+def residual_add_grouped(xs, rs, scale_table: torch.Tensor, step: torch.Tensor, stats_list=None, weights: Optional[torch.Tensor] = None):
+    """`residual_add` for up to 16 sites in ONE launch (csrc/t2i_adapter.hip, st_residual_add_grouped): xs[k][n] += s_k * rs[k][n % r_rows]
+    IN PLACE with s_k = fl32(scale_table[*step] * weights[k]) read on the device; `weights` an fp32 device tensor of len(xs) values or
+    None (all 1).  A site at s_k == 0 is neither read nor written.  `stats_list[k]`: the ColStats xs[k]'s producer emitted, or None;
+    returns, per site, the statistics that describe xs[k] afterwards (the given ones, rewritten) or None.  A site the kernel does not
+    take (not dense NHWC, a channel count that is not a whole number of 16-byte vectors) goes through `residual_add`'s torch route on
+    its own, the rest still in the one launch.  The split notes of every x are dropped, as there."""
+    n = len(xs)
+    if n < 1 or n > _C.RESIDUAL_MAX_SITES or len(rs) != n or (stats_list is not None and len(stats_list) != n):
+        raise BackendError(f"residual_add_grouped: {n} sites, {len(rs)} residuals, {None if stats_list is None else len(stats_list)} "
+                           f"statistics entries; one launch takes 1..{_C.RESIDUAL_MAX_SITES} sites with one entry each")
+    stats_list = [None] * n if stats_list is None else list(stats_list)
+    _C.require_device(scale_table, step, weights, *xs, *rs)
+    if scale_table.dtype != torch.float32 or scale_table.dim() != 1 or not scale_table.is_contiguous() or scale_table.numel() < 1:
+        raise BackendError("residual_add_grouped: scale_table must be a contiguous 1-D fp32 tensor")
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise BackendError("residual_add_grouped: step must be an int32 tensor of one entry")
+    if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 1 or weights.numel() != n or not weights.is_contiguous()):
+        raise BackendError(f"residual_add_grouped: weights must be a contiguous fp32 tensor of {n} values, one per site")
+    dtype = xs[0].dtype
+    cl = torch.channels_last
+    vec = 4 if dtype == torch.float32 else 8
+    out, taken, routed, sites, keep = [None] * n, [], [], [], []
+    for k, (x, r) in enumerate(zip(xs, rs)):
+        if x.dim() != 4 or r.dim() != 4 or r.dtype != x.dtype or x.dtype != dtype or tuple(r.shape[1:]) != tuple(x.shape[1:]) \
+                or r.shape[0] < 1 or x.shape[0] % r.shape[0]:
+            raise BackendError(f"residual_add_grouped: site {k}: x {tuple(x.shape)} {x.dtype} and r {tuple(r.shape)} {r.dtype} must be "
+                               f"(rows, C, H, W) and (r_rows, C, H, W) of one dtype ({dtype}, the call's) with r_rows a divisor of rows")
+    for k, (x, r) in enumerate(zip(xs, rs)):                 # nothing is written, and no note dropped, before the entry point has validated the launch
+        rows, Cc, H, W = x.shape
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16) or Cc % vec or not x.is_contiguous(memory_format=cl):
+            routed.append(k)
+            continue
+        if not r.is_contiguous(memory_format=cl):
+            r = r.contiguous(memory_format=cl)
+        HW, st = H * W, stats_list[k]
+        ok = st is not None and st.channels == Cc and st.rows > 0 and HW % st.rows == 0 and st.buf.numel() >= (rows * HW // st.rows) * Cc * 2
+        sites.append(_C.ResidualSite(x.data_ptr(), r.data_ptr(), st.buf.data_ptr() if ok else None, rows, r.shape[0], HW, Cc,
+                                     st.rows if ok else 0, rows * HW // st.rows if ok else 0))
+        keep.append(r)                                     # (a channels_last copy lives until the launch is queued)
+        taken.append(k)
+        out[k] = st if ok else None
+    if sites:
+        w = weights
+        if w is not None and len(taken) != n:              # the launch's sites are a subset: their weights, side by side
+            w = torch.cat([weights[k:k + 1] for k in taken])
+        arr = (_C.ResidualSite * len(sites))(*sites)
+        _C.check(_C.load().st_residual_add_grouped(arr, len(sites), _ptr(w), scale_table.data_ptr(), scale_table.numel(), step.data_ptr(),
+                                                   _C.dtype_code(dtype), _C.stream_ptr()), "residual_add_grouped")
+    for x in xs:
+        _forget_split(x)
+    for k in routed:                                       # torch's route, one site at a time
+        x, r = xs[k], rs[k]
+        s = scale_table.index_select(0, step.reshape(1).long().clamp(0, scale_table.numel() - 1))
+        if weights is not None:
+            s = s * weights[k:k + 1]
+        x.add_((r.float() * s).to(x.dtype).repeat(x.shape[0] // r.shape[0], 1, 1, 1))
+    return out
+
+
 # ----------------------------------------------------------------------------- tiled denoising: windows of a canvas
 def _tile_arguments(what: str, canvas: torch.Tensor, windows: torch.Tensor, ys, xs):
     """Shape and layout checks shared by tile_gather / tile_blend; the geometry itself (windows inside the canvas, every pixel covered,

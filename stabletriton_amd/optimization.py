@@ -16,18 +16,19 @@ import torch
 from torch import fx, nn
 
 from . import _C, ops
+from . import controlnet as _controlnet
 from . import t2i_adapter as _t2i
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
-                    ip_adapter=None, seg_layers=None, t2i_adapter: bool = False) -> fx.GraphModule:
+                    ip_adapter=None, seg_layers=None, t2i_adapter: bool = False, controlnet: bool = False) -> fx.GraphModule:
     """Pass pipeline over a traced module; an untraced nn.Module is traced here, after the flags were checked against each other
     (optimize_model relies on it: a bad combination raises before the trace).  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
@@ -46,13 +47,18 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     energy guidance; optimizers/insert_seg.py, seg.py); the state, `gm.seg`, starts with chunks 0 = ordinary attention; not with
     `pag_layers` (both claim the perturbed row block, and a site carries one leaf).  `t2i_adapter=True` (addition, off by default,
     likewise): a residual site behind every down block and the middle block (optimizers/insert_t2i_adapter.py, t2i_adapter.py); the
-    state, `gm.t2i_adapter`, starts at scale 0 = the bits of the module without sites; not with `fp8`."""
-    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter)
+    state, `gm.t2i_adapter`, starts at scale 0 = the bits of the module without sites; not with `fp8`.  `controlnet=True` (addition,
+    off by default, likewise): one leaf behind the middle block that adds a ControlNet's residuals to the skip tensors and the middle
+    block's output, for the decoder's readers only (optimizers/insert_controlnet.py, controlnet.py); the state, `gm.controlnet`,
+    starts at scale 0 = the bits of the module without sites; not with `t2i_adapter` or `fp8`."""
+    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet)
     if not isinstance(gm, fx.GraphModule):
         gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
     if t2i_adapter:      # first of all: module paths are readable, and FreeU's sites then read skips that carry the residual
         stats["t2i_adapter_sites"] = insert_t2i_adapter(gm)
+    if controlnet:       # likewise first (never both): FreeU's sites then read the leaf's outputs
+        stats["controlnet_sites"] = insert_controlnet(gm)
     if freeu:      # first: the readers of a concatenation still carry their module paths
         stats["freeu_sites"] = insert_freeu(gm)
     stats["dropout"] = remove_dropout(gm)
@@ -95,7 +101,7 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     return gm
 
 
-def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter) -> None:
+def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet=False) -> None:
     """The compile flags that exclude each other."""
     if seg_layers is not None and pag_layers is not None:
         raise ValueError("seg_layers cannot be combined with pag_layers: smoothed energy guidance and perturbed-attention guidance both "
@@ -104,6 +110,7 @@ def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, 
         raise ValueError("regions=R cannot be combined with fp8=True: the fp8 plan does not cover regional cross-attention sites")
     check_combination(ip_adapter, regions, fp8)
     _t2i.check_combination(t2i_adapter, fp8)
+    _controlnet.check_combination(controlnet, t2i_adapter, fp8)
 
 
 def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
@@ -112,8 +119,15 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
                    pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None,
-                   t2i_adapter: bool = False) -> fx.GraphModule:
-    """`t2i_adapter=True` (addition): T2I-Adapter structural control (t2i_adapter.py).  The UNet adds `s * f_k` to its activation
+                   t2i_adapter: bool = False, controlnet: bool = False) -> fx.GraphModule:
+    """`controlnet=True` (addition): ControlNet structural control (controlnet.py).  One launch behind the middle block adds the
+    residuals of a ControlNet branch to the UNet's skip tensors and to the middle block's output, in place, for the decoder's readers
+    only, and rewrites the producers' GroupNorm partials.  `gm.controlnet` - `bind(rows, latent_hw, device)` once, then
+    `set(residuals, scale)`, `set_scale(scale)`, `set_site_weights(weights)`, `clear()` in place, no new capture;
+    `using(step, table, residuals=...)` around the caller's own calls for per-step scales and residuals that are new every step;
+    scale 0, the state after `bind`, writes nothing: the bits of the module compiled without sites.  `controlnet.ControlNetXL` is the
+    branch network; `optimize_model(ControlNetXL(...), cuda_graph=False)` compiles it.  Not with `t2i_adapter=True` or `fp8=True`.
+    `t2i_adapter=True` (addition): T2I-Adapter structural control (t2i_adapter.py).  The UNet adds `s * f_k` to its activation
     behind every down block and the middle block (diffusers' `down_intrablock_additional_residuals` places), in place, in one launch
     per site that also rewrites the producer's GroupNorm partials.  `gm.t2i_adapter` - `bind(rows, latent_hw, device)` once, then
     `set(features, scale)`, `set_scale(scale)`, `clear()` in place, no new capture; `using(step, table)` around the caller's own
@@ -159,11 +173,17 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     if fp8 and p0.dtype != torch.bfloat16:
         raise RuntimeError("fp8 projections need a bfloat16 model")
     gm = replace_backend(model, fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
-                         region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter)
+                         region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
+                         controlnet=controlnet)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()
     gm.fp8_plan = bool(fp8 and fuse)
+    if isinstance(model, _controlnet.ControlNetXL):
+        # a ControlNet branch: its control-image embedding is no part of forward, so the trace drops it; the compiled module keeps the
+        # eager module's bound method (DenoiseLoop.set_controlnet embeds an image through it).  Limitation: the embedding's weights stay
+        # with the eager module - move / cast that module BEFORE compiling, a later .to() of the compiled branch leaves them behind
+        gm.embed_condition = model.embed_condition
     # the host's tables of the sinusoidal timestep features (ops._timestep_table): built now, eagerly, so that no first call
     # inside somebody's stream capture has to compute them the other way
     from .optimizers.wrappers import timestep_embedding_wrapper

@@ -14,6 +14,7 @@ from .fuse_groupnorm_stats import fuse_groupnorm_stats
 from .fuse_skip_cat import fuse_skip_cat
 from .insert_freeu import insert_freeu
 from .insert_t2i_adapter import insert_t2i_adapter
+from .insert_controlnet import insert_controlnet
 from .insert_pag import insert_pag
 from .insert_seg import insert_seg
 from .insert_regions import insert_regions

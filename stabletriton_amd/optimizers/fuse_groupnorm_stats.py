@@ -16,6 +16,7 @@ from typing import List, Optional
 import torch
 from torch import fx
 
+from ..controlnet import controlnet_sites
 from ..freeu import freeu_wrapper
 from ..t2i_adapter import t2i_site
 from .wrappers import conv2d_wrapper, group_norm_stats_wrapper, group_norm_wrapper, linear_residual_wrapper
@@ -43,7 +44,22 @@ def _can_emit(n: fx.Node) -> bool:
     if _is_fn(n, t2i_site):       # a T2I-Adapter site rewrites the partials of the launch that produced its input
         inner = _producers(n.args[0])
         return inner is not None and len(inner) == 1
+    if _controlnet_output(n):     # likewise the ControlNet leaf, for each of its sites
+        inner = _producers(_controlnet_input(n))
+        return inner is not None and len(inner) == 1
     return False
+
+
+def _controlnet_output(n) -> bool:
+    """Value k of the ControlNet leaf (its outputs: the n values, then the n sets of partials)."""
+    return (_is_fn(n, operator.getitem) and _is_fn(n.args[0], controlnet_sites) and isinstance(n.args[1], int)
+            and 0 <= n.args[1] <= len(n.args[0].args[1]))
+
+
+def _controlnet_input(n: fx.Node) -> fx.Node:
+    """What site k of the leaf reads: skip k, or (the last site) the middle block's output."""
+    leaf, k = n.args[0], n.args[1]
+    return leaf.args[1][k] if k < len(leaf.args[1]) else leaf.args[0]
 
 
 def _freeu_output(n) -> bool:
@@ -56,6 +72,8 @@ def _producers(v: fx.Node) -> Optional[List[fx.Node]]:
     v = _root(v)
     if _freeu_output(v):
         return [v]
+    if _controlnet_output(v):
+        return [v] if _can_emit(v) else None
     if _is_fn(v, operator.getitem) and v.args[1] == 0 and _can_emit(v.args[0]) and v.args[0].kwargs.get("emit_colstats"):
         return [v.args[0]]
     if _can_emit(v):
@@ -79,6 +97,19 @@ def _stats_of(gm: fx.GraphModule, prod: fx.Node) -> fx.Node:
                 return u
         with gm.graph.inserting_after(prod):
             return gm.graph.call_function(operator.getitem, (site, want))
+    if _controlnet_output(prod):
+        # the inner producer's partials go INTO the leaf (which rewrites them in place where the site's scale is not 0) and come
+        # out of it at index n + k
+        leaf, k, n = prod.args[0], prod.args[1], len(prod.args[0].args[1]) + 1
+        for u in leaf.users:
+            if _is_fn(u, operator.getitem) and u.args[1] == n + k:
+                return u
+        inner = _stats_of(gm, _producers(_controlnet_input(prod))[0])
+        src = list(leaf.kwargs.get("src_stats") or [None] * n)
+        src[k] = inner
+        leaf.kwargs = {**leaf.kwargs, "src_stats": src}
+        with gm.graph.inserting_after(prod):
+            return gm.graph.call_function(operator.getitem, (leaf, n + k))
     if _is_fn(prod, t2i_site) and not prod.kwargs.get("emit_colstats"):
         # the inner producer's partials go INTO the site (which rewrites them in place when its scale is not 0) and come out of it
         inner = _stats_of(gm, _producers(prod.args[0])[0])

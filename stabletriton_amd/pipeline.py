@@ -68,6 +68,16 @@ under a per-step scale table (`scale` for the first int(n_steps * factor) steps,
 `step_ids[i:i+1]` (modes loop / eager) or at the step counter (mode step); a step at scale 0 - every step until `set_t2i_adapter` -
 writes nothing: the bits of a UNet compiled without sites.
 
+ControlNet (`controlnet=`, `set_controlnet`, `set_controlnet_scale`; controlnet.py) on a UNet compiled with `controlnet=True`:
+`controlnet=` is the compiled branch (`optimize_model(ControlNetXL(...), cuda_graph=False)`).  Every step calls the branch on the
+UNet's own `x_in`, timestep and conditioning rows plus the control image's embedding (a static buffer of `rows` rows), then the UNet
+with the branch's outputs lent to its sites (`state.using(step, table, residuals=...)`: no copies, the capture records their
+addresses) under a per-step scale table that is 0 outside [int(n * start), int(n * end)).  Nothing of this is captured by value:
+`set_controlnet` / `set_controlnet_scale` are in-place writes before or after `capture()`.  The captured graph is static, so a
+step at scale 0 still runs the branch; only the sites' launch leaves early, and the UNet gives the bits of one compiled without
+sites.  Not built: several branches in one loop, guess mode's cond-only rows, the branch's own context / time split (its plain
+forward runs).
+
 Tiled denoising (`tile_hw`, `tile_stride`, `tile_wrap_w`, `tile_weights`, `set_tile_weights`; tiles.py) makes `latent_hw` a canvas
 larger than the UNet denoises in one piece (MultiDiffusion; with Gaussian weights Mixture of Diffusers): the UNet runs on the T
 overlapping windows of the canvas as batch rows - `x_in`, the conditioning buffers, the hoisted context and the time tables have
@@ -78,7 +88,7 @@ into windows): two more launches per step, every sampler and guidance form as be
 over the canvas, not per window.  The weight map is a device buffer the blend reads by address: `set_tile_weights` is an in-place write,
 before or after `capture()`.  `set_conditioning` takes B rows (one prompt for all of a sample's windows) or B * T rows (one prompt per
 window, sample-major).  PAG and SEG work (their row block is outermost; the perturbed scope and SEG's blur see the window size).  UNets
-compiled with `regions`, `ip_adapter` or `t2i_adapter` are refused: their states bind per latent size and row count, and cropping them
+compiled with `regions`, `ip_adapter`, `t2i_adapter` or `controlnet` are refused: their states bind per latent size and row count, and cropping them
 per window is not built.  The fp8 plan is allowed with tiles and not covered by tests.  `tile_hw=None` is the untiled loop exactly:
 `x_step is x_in`, no further buffers or launches.
 """
@@ -104,13 +114,15 @@ class DenoiseLoop:
                  guidance_rescale: Optional[Union[float, Sequence[float]]] = None,
                  pag_scale: Optional[Union[float, Sequence[float]]] = None,
                  seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf"),
-                 tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform"):
+                 tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform", controlnet: Optional[Callable] = None):
         assert mode in ("loop", "step", "eager")
         if seg_scale is not None and pag_scale is not None:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
         if guidance_rescale is not None and guidance_scale is None:
             raise ValueError("guidance_rescale needs guidance_scale")
-        from . import ip_adapter as _ip, pag, regions as _regions, t2i_adapter as _t2i
+        from . import controlnet as _cn, ip_adapter as _ip, pag, regions as _regions, t2i_adapter as _t2i
+        if controlnet is not None:                         # the branch's residuals need the UNet's sites
+            _cn.state_of(unet, "DenoiseLoop(controlnet=...)")
         # perturbed-attention guidance: the UNet's sites must exist (compiled in), and the loop names the perturbed row block
         # around its own UNet calls only (chunks 3 = [neg | pos | pert], 2 = [pos | pert])
         self._perturbed = None
@@ -144,7 +156,8 @@ class DenoiseLoop:
         th, tw, T = lh, lw, 1
         if tile_hw is not None:
             from . import tiles as _tiles
-            for name, cls in (("regions", _regions.Regions), ("ip_adapter", _ip.IPAdapter), ("t2i_adapter", _t2i.T2IAdapterState)):
+            for name, cls in (("regions", _regions.Regions), ("ip_adapter", _ip.IPAdapter), ("t2i_adapter", _t2i.T2IAdapterState),
+                              ("controlnet", _cn.ControlNetState)):
                 if compiled_state(unet, name, cls) is not None:
                     raise ValueError(f"DenoiseLoop: tile_hw cannot be combined with a UNet compiled with {name}: its state binds per latent "
                                      "size and row count, and cropping it per window is not built")
@@ -169,6 +182,16 @@ class DenoiseLoop:
         if self._t2i_state is not None:
             self._t2i_state.bind(rows, (lh, lw), dev, dtype=dtype, feature_rows=batch)
             self.t2i_table = torch.zeros(n, dtype=torch.float32, device=dev)
+        # ControlNet: the sites' state of this row count, this loop's own per-step scale table (0 = off) and - with a branch - the
+        # static buffer of the control image's embedding, `rows` rows: allocated once, outside capture
+        self._cn_state = compiled_state(unet, "controlnet", _cn.ControlNetState)
+        self.controlnet, self.controlnet_table, self.controlnet_cond = controlnet, None, None
+        if self._cn_state is not None:
+            self._cn_state.bind(rows, (lh, lw), dev, dtype=dtype)
+            self.controlnet_table = torch.zeros(n, dtype=torch.float32, device=dev)
+            if controlnet is not None:
+                self.controlnet_cond = torch.zeros((rows, self._cn_state.channels[0], lh, lw), dtype=dtype, device=dev).contiguous(
+                    memory_format=cl)
         self._latent_hw = (th, tw)                         # what the UNet sees: the window when tiled
         if isinstance(self._perturbed, seg.SEG):           # the blur's parameter rows of this latent size: allocated once, outside capture
             self._perturbed.bind((th, tw), dev)
@@ -498,6 +521,52 @@ class DenoiseLoop:
         t2i_adapter.state_of(self.unet, "set_t2i_adapter_scale")
         self.t2i_table.copy_(self._step_table(scale, "scale", "set_t2i_adapter_scale"))
 
+    # ---- ControlNet (controlnet.py): in-place writes of buffers the branch and the sites read by address, no new capture --------
+    def set_controlnet(self, image_or_cond_embed, scale: float = 1.0, start: float = 0.0, end: float = 1.0) -> None:
+        """The control image (1, B or rows, 3, 8 lh, 8 lw) - embedded here by the branch's eager `embed_condition`, once - or its
+        ready embedding (1, B or rows, widths[0], lh, lw), and the per-step scale table: `scale` for the steps
+        int(n_steps * start) <= i < int(n_steps * end), 0 for the rest (diffusers' `controlnet_conditioning_scale`,
+        `control_guidance_start` / `_end`).  Every row block of the UNet batch sees the same control.  `set_controlnet(None)` is
+        "off": the bits of a loop on a UNet compiled without sites (the branch still runs: the captured graph is static).  In-place
+        writes, legal before or after `capture()`.  The UNet must have been compiled with `controlnet=True`.  (An image is embedded by
+        eager torch convolutions, which do not promise the same bits from one call to the next: two loops that are to agree bit for
+        bit are handed one embedding.)"""
+        from . import controlnet as _cn
+        _cn.state_of(self.unet, "set_controlnet")
+        if image_or_cond_embed is None:
+            self.controlnet_table.zero_()
+            return
+        if self.controlnet is None:
+            raise ValueError("set_controlnet: this loop was built without controlnet= (the compiled branch)")
+        table = _cn.scale_table(self.n_steps, scale, start, end)
+        c = image_or_cond_embed
+        buf = self.controlnet_cond
+        lh, lw = buf.shape[-2:]
+        if torch.is_tensor(c) and c.dim() == 4 and c.shape[1] != buf.shape[1] and tuple(c.shape[-2:]) == (8 * lh, 8 * lw):
+            embed = getattr(self.controlnet, "embed_condition", None)
+            if embed is None:
+                raise ValueError("set_controlnet: this branch has no embed_condition (the eager embedding of a control image); pass "
+                                 "the embedding itself")
+            p = next(self.controlnet.parameters())
+            c = embed(c.to(p.device, p.dtype))
+        if not torch.is_tensor(c) or c.dim() != 4 or tuple(c.shape[1:]) != tuple(buf.shape[1:]) or c.shape[0] < 1 or buf.shape[0] % c.shape[0]:
+            shape = tuple(c.shape) if torch.is_tensor(c) else type(c).__name__
+            raise ValueError(f"set_controlnet: takes a control image (rows, 3, {8 * lh}, {8 * lw}) or its embedding (rows, {buf.shape[1]}, "
+                             f"{lh}, {lw}) with rows 1, the batch {self.batch} or all {buf.shape[0]}, got {shape}")
+        buf.copy_(c.detach().to(buf.device, buf.dtype).repeat(buf.shape[0] // c.shape[0], 1, 1, 1))
+        self.controlnet_table.copy_(table)
+
+    def set_controlnet_scale(self, scale: Union[float, Sequence[float]], site_weights: Optional[Sequence[float]] = None) -> None:
+        """The sites' scale per step: a float, or n_steps floats; `site_weights`: one factor per site on top of it (the skips in
+        encoder order, the middle block's last; they belong to the UNet's state: loops that share one compiled UNet share them).
+        Written into the device tables in place: no new capture."""
+        from . import controlnet as _cn
+        state = _cn.state_of(self.unet, "set_controlnet_scale")
+        table = self._step_table(scale, "scale", "set_controlnet_scale")
+        if site_weights is not None:
+            state.set_site_weights(site_weights)
+        self.controlnet_table.copy_(table)
+
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
         s + B - 1 (mod 2^64).  Written into the device table in place: a captured graph reads it by address."""
@@ -604,6 +673,13 @@ class DenoiseLoop:
         with contextlib.ExitStack() as scopes:      # both for this loop's own calls only
             if self._t2i_state is not None:      # the residual sites read this loop's scale table at `step`
                 scopes.enter_context(self._t2i_state.using(self.step_ids[0:1] if step is None else step, self.t2i_table))
+            if self._cn_state is not None:       # the branch on the UNet's own rows, then its outputs lent to the sites (no copies)
+                residuals = None
+                if self.controlnet is not None:
+                    down, mid = self.controlnet(self.x_in, t, self.ehs, self._cond(), cond_embed=self.controlnet_cond)
+                    residuals = list(down) + [mid]
+                scopes.enter_context(self._cn_state.using(self.step_ids[0:1] if step is None else step, self.controlnet_table,
+                                                          residuals=residuals))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
                 scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
             return self._unet_call(t, time_row)
