@@ -26,140 +26,34 @@ spelling, restated from memory (diffusers is not a dependency) - parity with a p
 from __future__ import annotations
 
 import contextlib
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 from torch import nn
 
-from .state import RowBound, latent_size, require_state
+from .state import ResidualSites, comfy_control, finite_scale, require_state
 from .unet import SDXL_BASE, MidStage, SinusoidalProj, Stage, TimestepMLP, UNetSpec
 
 
 def scale_table(n_steps: int, scale: float = 1.0, start: float = 0.0, end: float = 1.0) -> torch.Tensor:
     """diffusers' `controlnet_conditioning_scale` / `control_guidance_start` / `control_guidance_end` as a table: `scale` for the
     steps int(n_steps * start) <= i < int(n_steps * end), 0 for the rest (n_steps fp32 values, on the host)."""
-    scale, start, end = float(scale), float(start), float(end)
-    if not (scale == scale and abs(scale) != float("inf")):
-        raise ValueError(f"controlnet: scale must be finite, got {scale!r}")
+    scale, start, end = finite_scale("controlnet", scale), float(start), float(end)
     if not 0.0 <= start <= end <= 1.0:
         raise ValueError(f"controlnet: 0 <= start <= end <= 1 (the share of the steps the control acts on), got start={start!r} end={end!r}")
     lo, hi = int(n_steps * start), int(n_steps * end)
     return torch.tensor([scale if lo <= i < hi else 0.0 for i in range(n_steps)], dtype=torch.float32)
 
 
-class ControlNetState(RowBound, nn.Module):
+class ControlNetState(ResidualSites):
     """State of one compiled module: the sites (name, channels, latent halvings) - the skip tensors in encoder order, the middle
     block's output last - and their buffers."""
     label = "controlnet"
 
     def __init__(self, sites: Sequence[Tuple[str, int, int]], dtype: Optional[torch.dtype] = None):
-        super().__init__()
-        self.sites = tuple(s[0] for s in sites)
-        self.channels = tuple(int(s[1]) for s in sites)
-        self.levels = tuple(int(s[2]) for s in sites)
-        self.dtype = dtype
-        # plain dicts under names torch does not know (as in t2i_adapter.T2IAdapterState): .to(dtype) / state_dict() leave them alone
-        self._residuals: Dict[Tuple[int, int, int, int], torch.Tensor] = {}         # (rows, site, h, w) -> (rows, C, h, w) channels_last
-        self._tables: Dict[torch.device, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = {}      # device -> (scale, step 0, site weights)
-        self._use = None                                   # (step, table, residuals or None) of the caller inside `using`
-        self.host_scale = 0.0                              # the state's own scale and weights as Python floats (the CPU route)
+        super().__init__(sites, dtype)
         self.host_weights = [1.0] * len(self.sites)
-        self.grouped = True                                # A/B switch (tools/controlnet_time.py): False = one st_residual_add per site
-
-    # ---- geometry --------------------------------------------------------------------------------
-    def site_shapes(self, latent_hw):
-        """(C, h, w) of every site at this latent size: each halving is the UNet's stride-2 convolution, ceil(n / 2)."""
-        lh, lw = latent_size(latent_hw)
-        out = []
-        for c, l in zip(self.channels, self.levels):
-            h, w = lh, lw
-            for _ in range(l):
-                h, w = (h + 1) // 2, (w + 1) // 2
-            out.append((c, h, w))
-        return out
-
-    # ---- buffers ---------------------------------------------------------------------------------
-    def bind(self, rows: int, latent_hw, device, dtype: Optional[torch.dtype] = None) -> None:
-        """Allocate, outside any capture, the zeroed residual buffers of a UNet batch of `rows` rows at this latent size, the site
-        weights (ones), the one-entry scale table (0 = off) and the step counter.  A buffer that exists is kept (its address is what
-        captured graphs read), so binding twice is free."""
-        rows, lh, lw, device = self._parse_bind(rows, latent_hw, device)
-        dtype = dtype or self.dtype or torch.float32
-        if device not in self._tables:
-            self._refuse_capture(device)
-            self._tables[device] = (torch.full((1,), self.host_scale, dtype=torch.float32, device=device),
-                                    torch.zeros(1, dtype=torch.int32, device=device),
-                                    torch.tensor(self.host_weights, dtype=torch.float32, device=device))
-        for k, (c, h, w) in enumerate(self.site_shapes((lh, lw))):
-            buf = self._residuals.get((rows, k, h, w))
-            if buf is None:
-                self._refuse_capture(device)
-                self._residuals[(rows, k, h, w)] = torch.zeros((rows, c, h, w), dtype=dtype, device=device).contiguous(
-                    memory_format=torch.channels_last)
-            elif buf.device != device or buf.dtype != dtype:
-                raise ValueError(f"controlnet.bind: the buffers of {rows} rows at site {self.sites[k]} are {buf.dtype} on {buf.device}; "
-                                 f"asked for {dtype} on {device}")
-
-    def bound_rows(self):
-        return sorted({key[0] for key in self._residuals})
-
-    def _own(self, device=None):
-        if not self._tables:
-            raise ValueError("controlnet: nothing is bound; call bind(rows, latent_hw, device) first")
-        if device is None:
-            if len(self._tables) != 1:
-                raise ValueError(f"controlnet: bound on {sorted(str(d) for d in self._tables)}: one state serves one device")
-            return next(iter(self._tables.values()))
-        if torch.device(device) not in self._tables:
-            raise ValueError(f"controlnet: nothing is bound on {device}; call bind(rows, latent_hw, device) first")
-        return self._tables[torch.device(device)]
-
-    # ---- values ----------------------------------------------------------------------------------
-    def check_residuals(self, residuals, what: str, rows: Optional[int] = None, like: Optional[Sequence[torch.Tensor]] = None):
-        """`residuals` validated against the sites: one (rows or a divisor of rows, C_k, h_k, w_k) tensor per site, the middle one
-        last.  With `like` (the activations of a call) the sizes are theirs; else those of the buffers bound for `rows`."""
-        n = len(self.sites)
-        if not isinstance(residuals, (list, tuple)) or len(residuals) != n:
-            got = len(residuals) if isinstance(residuals, (list, tuple)) else type(residuals).__name__
-            raise ValueError(f"{what}: takes {n} residuals, one per skip tensor in encoder order and the middle block's last, got {got}")
-        pairs = []
-        for k, r in enumerate(residuals):
-            if not torch.is_tensor(r) or r.dim() != 4 or r.shape[1] != self.channels[k]:
-                shape = tuple(r.shape) if torch.is_tensor(r) else type(r).__name__
-                raise ValueError(f"{what}: residual {k} (site {self.sites[k]}) must be (rows, {self.channels[k]}, h, w), got {shape}")
-            if like is not None:
-                want = like[k]
-                if tuple(r.shape[1:]) != tuple(want.shape[1:]) or r.shape[0] < 1 or want.shape[0] % r.shape[0]:
-                    raise ValueError(f"{what}: residual {k} (site {self.sites[k]}) is {tuple(r.shape)}; the activation there is "
-                                     f"{tuple(want.shape)}")
-                pairs.append((want, r))
-                continue
-            buf = self._residuals.get((rows, k, int(r.shape[2]), int(r.shape[3])))
-            if buf is None:
-                sizes = sorted(key[2:] for key in self._residuals if key[0] == rows and key[1] == k)
-                raise ValueError(f"{what}: residual {k} (site {self.sites[k]}) is {tuple(r.shape[2:])}; the buffers bound for {rows} rows "
-                                 f"have the sizes {sizes} there")
-            if r.shape[0] not in (1, buf.shape[0]):
-                raise ValueError(f"{what}: residual {k} (site {self.sites[k]}) has {r.shape[0]} rows; the buffers hold {buf.shape[0]} "
-                                 "(or 1 for every row)")
-            pairs.append((buf, r))
-        return pairs
-
-    def set(self, residuals, scale: Optional[float] = 1.0, rows: Optional[int] = None) -> None:
-        """Copy one residual per site into the buffers of `rows` in place, and (scale not None) set the state's own scale."""
-        rows = self._rows(rows, "controlnet.set")
-        pairs = self.check_residuals(residuals, "controlnet.set", rows)
-        for buf, r in pairs:          # (nothing is written unless every site validated)
-            buf.copy_(r.detach().to(buf.dtype).expand(buf.shape))
-        if scale is not None:
-            self.set_scale(scale)
-
-    def set_scale(self, scale: float) -> None:
-        """The state's own scale (what the sites read outside `using`): an in-place write on every bound device."""
-        scale_table(1, scale)            # (validates)
-        for table, _, _ in self._tables.values():
-            table.fill_(float(scale))
-        self.host_scale = float(scale)
+        self._lent = None                                  # the residuals of the caller inside `using(..., residuals=)`
 
     def set_site_weights(self, weights: Optional[Sequence[float]] = None) -> None:
         """One factor per site on top of the scale (the skip tensors in encoder order, the middle block's last); None: all 1.  A site
@@ -168,54 +62,34 @@ class ControlNetState(RowBound, nn.Module):
         vals = [1.0] * n if weights is None else [float(v) for v in weights]
         if len(vals) != n or any(not (v == v and abs(v) != float("inf")) for v in vals):
             raise ValueError(f"controlnet.set_site_weights: takes {n} finite values, one per site, got {vals!r}")
-        for _, _, w in self._tables.values():
-            w.copy_(torch.tensor(vals, dtype=torch.float32))
+        for own in self._tables.values():
+            own.weights.copy_(torch.tensor(vals, dtype=torch.float32))
         self.host_weights = vals
-
-    def clear(self) -> None:
-        """Back to "off": scale 0 (the buffers and the weights keep their contents; at scale 0 nobody reads the buffers)."""
-        for table, _, _ in self._tables.values():
-            table.zero_()
-        self.host_scale = 0.0
 
     @contextlib.contextmanager
     def using(self, step: torch.Tensor, table: torch.Tensor, residuals=None):
-        """Around the caller's own UNet calls: the sites read `table[*step]` (an fp32 device table, an int32 device counter, both by
-        address) instead of the state's own scale, and - with `residuals`, one tensor per site - those tensors INSTEAD of the state's
+        """`ResidualSites.using`, and - with `residuals`, one tensor per site - the sites read those tensors INSTEAD of the state's
         buffers: no copies, a capture records their addresses."""
-        if step.dtype != torch.int32 or step.numel() != 1 or table.dtype != torch.float32 or table.dim() != 1:
-            raise ValueError("controlnet.using: step is an int32 tensor of one entry, table a 1-D fp32 tensor")
-        if residuals is not None and (not isinstance(residuals, (list, tuple)) or len(residuals) != len(self.sites)):
-            raise ValueError(f"controlnet.using: residuals are {len(self.sites)} tensors, one per site (the middle block's last)")
-        prev, self._use = self._use, (step, table, None if residuals is None else list(residuals))
-        try:
-            yield self
-        finally:
-            self._use = prev
-
-    def current(self, device):
-        """(step, table, site weights) the sites of a call on `device` read."""
-        scale, step, weights = self._own(device)
-        if self._use is not None:
-            return self._use[0], self._use[1], weights
-        return step, scale, weights
+        with super().using(step, table):
+            if residuals is not None and (not isinstance(residuals, (list, tuple)) or len(residuals) != len(self.sites)):
+                raise ValueError(f"controlnet.using: residuals are {len(self.sites)} tensors, one per site (the middle block's last)")
+            prev, self._lent = self._lent, None if residuals is None else list(residuals)
+            try:
+                yield self
+            finally:
+                self._lent = prev
 
     def residuals_for(self, xs: Sequence[torch.Tensor]) -> List[torch.Tensor]:
-        """The residuals the sites of a call with the activations `xs` read: the lent ones, or the buffers bound for that size."""
-        if self._use is not None and self._use[2] is not None:
-            return [r for _, r in self.check_residuals(self._use[2], "controlnet.using", like=xs)]
-        out = []
-        for k, x in enumerate(xs):
-            rows, _, h, w = x.shape
-            buf = self._residuals.get((int(rows), k, int(h), int(w)))
-            if buf is None:
-                raise ValueError(f"controlnet: no residual buffer for site {self.sites[k]} at {rows} rows x {h} x {w} (bound: "
-                                 f"{sorted(self._residuals)}); call gm.controlnet.bind(rows, latent_hw, device) before the first evaluation")
-            out.append(buf)
-        return out
-
-    def extra_repr(self) -> str:
-        return f"sites={self.sites}, channels={self.channels}, levels={self.levels}, bound={sorted(self._residuals)}"
+        """The residuals the sites of a call with the activations `xs` read: the lent ones - each (rows or a divisor of rows, C_k,
+        h_k, w_k) of its activation, validated here -, or the buffers bound for that size."""
+        if self._lent is None:
+            return [self.buffer_for(x.shape[0], k, x.shape[2], x.shape[3]) for k, x in enumerate(xs)]
+        self._check_list(self._lent, "controlnet.using")
+        for k, (r, x) in enumerate(zip(self._lent, xs)):
+            if tuple(r.shape[1:]) != tuple(x.shape[1:]) or r.shape[0] < 1 or x.shape[0] % r.shape[0]:
+                raise ValueError(f"controlnet.using: residual {k} (site {self.sites[k]}) is {tuple(r.shape)}; the activation there is "
+                                 f"{tuple(x.shape)}")
+        return self._lent
 
 
 def controlnet_sites(mid: torch.Tensor, skips, state: ControlNetState, src_stats=None):
@@ -229,8 +103,7 @@ def controlnet_sites(mid: torch.Tensor, skips, state: ControlNetState, src_stats
     rs = state.residuals_for(xs)
     step, table, weights = state.current(mid.device)
     if mid.device.type == "cpu":
-        i = min(max(int(step.reshape(-1)[0]), 0), table.numel() - 1)      # the kernel's clamp
-        s = state.host_scale if state._use is None else float(table[i])
+        s = state.cpu_scale(step, table)
         out = []
         for x, r, w in zip(xs, rs, state.host_weights):
             sk = s * w
@@ -241,13 +114,7 @@ def controlnet_sites(mid: torch.Tensor, skips, state: ControlNetState, src_stats
             raise ValueError(f"controlnet: the residual of site {state.sites[k]} is {r.dtype} on {r.device}, the activation is "
                              f"{x.dtype} on {x.device}: bind(rows, latent_hw, device, dtype) with the UNet's own")
     from . import ops
-    if state.grouped:
-        stats = ops.residual_add_grouped(xs, rs, table, step, src_stats, weights)
-    else:                                                  # the A/B form: the same sites as n launches of st_residual_add
-        if any(w != 1.0 for w in state.host_weights):
-            raise ValueError("controlnet: the one-launch-per-site form (grouped = False) has no site weights")
-        stats = [ops.residual_add(x, r, table, step, st) for x, r, st in zip(xs, rs, src_stats)]
-    return tuple(xs) + tuple(stats)
+    return tuple(xs) + tuple(ops.residual_add_grouped(xs, rs, table, step, src_stats, weights))
 
 
 torch.fx.wrap("controlnet_sites")
@@ -271,23 +138,15 @@ def comfy_residuals(state: ControlNetState, control: dict):
     """ComfyUI's `control` dict -> one entry per site (a tensor or None), or None when it carries nothing.  `control["output"]`
     holds the skip residuals: ComfyUI pops from the END while the decoder consumes its skips last-first, so entry i is skip i in
     encoder order; `control["middle"]` takes its last entry.  A non-empty `control["input"]` (T2I-Adapter residuals) raises."""
-    if not isinstance(control, dict):
-        raise NotImplementedError(f"control must be a dict of lists (output / middle), got {type(control).__name__}")
-    extra = sorted(k for k in control if k not in ("input", "middle", "output"))
-    if extra:
-        raise NotImplementedError(f"control entries {extra} are not supported by the compiled UNet (output / middle of a ControlNet are)")
-    if any(e is not None for e in (control.get("input") or [])):
+    inputs, output, middle = comfy_control(control, "output / middle", "a ControlNet")
+    if any(e is not None for e in inputs):
         raise NotImplementedError('control["input"] (T2I-Adapter residuals inside the encoder) is not supported by a UNet compiled with '
                                   "controlnet=True: only ControlNet residuals (output / middle) are")
     n = len(state.sites)
-    output = list(control.get("output") or [])
     if output and len(output) != n - 1:      # (ComfyUI pops from the end: a shorter list would belong to the LAST skips; none is guessed)
         raise NotImplementedError(f'control["output"] carries {len(output)} residuals; this UNet has {n - 1} skip tensors and takes one '
                                   "entry (or None) for each")
-    middle = list(control.get("middle") or [])
-    if any(e is not None for e in middle[:-1]):
-        raise NotImplementedError('control["middle"] carries more than one residual; the middle block takes the last entry')
-    out = output + [None] * (n - 1 - len(output)) + [middle[-1] if middle else None]
+    out = output + [None] * (n - 1 - len(output)) + [middle]
     return None if all(e is None for e in out) else out
 
 

@@ -60,8 +60,7 @@ class _HoistedUNet(nn.Module):
         self._ip_images = {}                      # set_ip_adapter_image: slot -> (tokens, negative_tokens, chunks)
         self._ip_masks = {}                       # set_ip_adapter_masks: slot -> masks
         self._ip_applied = {}                     # ... rows -> the latent size the buffers of that row count were last written for
-        self._t2i_last = None                     # T2I-Adapter: (rows, the residual tensors last copied - HELD, not their addresses -, their versions)
-        self._cn_last = None                      # ControlNet: likewise
+        self._residuals_last = None               # T2I-Adapter / ControlNet: (state, rows, the residual tensors last copied - HELD, not their addresses -, their versions)
 
     def refresh_weights(self) -> int:
         """Re-derive fused / folded weight buffers after an in-place weight update (also done at every new prompt).
@@ -277,76 +276,45 @@ class _HoistedUNet(nn.Module):
             state.set_masks(masks, slot, rows)
         self._ip_applied[rows] = hw
 
-    # ---- T2I-Adapter residuals (t2i_adapter.py): static buffers the residual sites read by address; the captured graphs stay ----
+    # ---- T2I-Adapter / ControlNet residuals (t2i_adapter.py, controlnet.py): static buffers the residual sites read by address;
+    # the captured graphs stay.  A compiled module carries at most one of the two states -------------------------------------------
     def _t2i_state(self):
         from . import t2i_adapter
         return compiled_state(self.compiled, "t2i_adapter", t2i_adapter.T2IAdapterState)
 
-    def _apply_t2i(self, sample: torch.Tensor, features) -> None:
-        """Bind the buffers of this call's batch and latent size (outside any capture) and write this call's residuals: one tensor
-        per site (None: zeros there), already scaled by the caller, so the scale is 1; `features` None: scale 0, nothing else is
-        touched.  The very tensors of the previous call at their versions are not copied again: the wrapper HOLDS those tensors until
-        the next call with others (identity is only safe while the objects live; at 1024 x 1024, bf16, two rows that is about 26 MB
-        kept alive), and the rule looks at the caller's tensors alone - somebody who writes the shared buffers through
-        `gm.t2i_adapter.set` in between, and then calls with the same tensor objects, is not noticed."""
-        state = self._t2i_state()
-        if state is None:
-            return
-        rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
-        if not torch.cuda.is_current_stream_capturing():
-            state.bind(rows, hw, sample.device, dtype=self.compute_dtype)
-        if features is None:
-            if state.host_scale != 0.0:
-                state.clear()
-            return
-        if len(features) != len(state.sites):
-            raise ValueError(f"T2I-Adapter residuals: {len(state.sites)} tensors expected, one per site {state.sites}, got {len(features)}")
-        versions = tuple(None if f is None else f._version for f in features)
-        last = self._t2i_last
-        same = (last is not None and last[0] == rows and last[2] == versions and len(last[1]) == len(features)
-                and all(a is b for a, b in zip(last[1], features)))
-        if not same:
-            shapes = state.site_shapes(hw)
-            full = [torch.zeros((1,) + shapes[k], dtype=self.compute_dtype, device=sample.device) if f is None else f
-                    for k, f in enumerate(features)]
-            state.set(full, None, rows)
-            self._t2i_last = (rows, list(features), versions)
-        if state.host_scale != 1.0:
-            state.set_scale(1.0)
-
-    # ---- ControlNet residuals (controlnet.py): static buffers the sites' one launch reads by address; the captured graphs stay ----
     def _cn_state(self):
         from . import controlnet
         return compiled_state(self.compiled, "controlnet", controlnet.ControlNetState)
 
-    def _apply_controlnet(self, sample: torch.Tensor, residuals) -> None:
-        """As `_apply_t2i`, for the ControlNet sites: one tensor per site, the skips' in encoder order and the middle block's last
-        (None: zeros there), already scaled by the pipeline and summed over a MultiControlNet, so the scale is 1; `residuals` None:
-        scale 0, nothing else is touched.  The very tensors of the previous call at their versions are not copied again (the wrapper
-        HOLDS them until the next call with others)."""
-        state = self._cn_state()
+    def _apply_residuals(self, sample: torch.Tensor, state, values, what: str) -> None:
+        """Bind `state`'s buffers of this call's batch and latent size (outside any capture) and write this call's residuals: one
+        tensor per site (None: zeros there), already scaled by the caller (and summed over several adapters / a MultiControlNet), so
+        the scale is 1; `values` None: scale 0, nothing else is touched.  The very tensors of the previous call at their versions are
+        not copied again: the wrapper HOLDS those tensors until the next call with others (identity is only safe while the objects
+        live; at 1024 x 1024, bf16, two rows that is about 26 MB kept alive for a T2I adapter), and the rule looks at the caller's
+        tensors alone - somebody who writes the shared buffers through `gm.t2i_adapter.set` / `gm.controlnet.set` in between, and
+        then calls with the same tensor objects, is not noticed."""
         if state is None:
             return
         rows, hw = int(sample.shape[0]), (int(sample.shape[-2]), int(sample.shape[-1]))
         if not torch.cuda.is_current_stream_capturing():
             state.bind(rows, hw, sample.device, dtype=self.compute_dtype)
-        if residuals is None:
+        if values is None:
             if state.host_scale != 0.0:
                 state.clear()
             return
-        if len(residuals) != len(state.sites):
-            raise ValueError(f"ControlNet residuals: {len(state.sites)} tensors expected, {len(state.sites) - 1} skip residuals and the middle "
-                             f"block's, got {len(residuals)}")
-        versions = tuple(None if r is None else r._version for r in residuals)
-        last = self._cn_last
-        same = (last is not None and last[0] == rows and last[2] == versions and len(last[1]) == len(residuals)
-                and all(a is b for a, b in zip(last[1], residuals)))
+        if len(values) != len(state.sites):
+            raise ValueError(f"{what}: {len(state.sites)} tensors expected, one per site {state.sites}, got {len(values)}")
+        versions = tuple(None if v is None else v._version for v in values)
+        last = self._residuals_last
+        same = (last is not None and last[0] is state and last[1] == rows and last[3] == versions and len(last[2]) == len(values)
+                and all(a is b for a, b in zip(last[2], values)))
         if not same:
             shapes = state.site_shapes(hw)
-            full = [torch.zeros((1,) + shapes[k], dtype=self.compute_dtype, device=sample.device) if r is None else r
-                    for k, r in enumerate(residuals)]
+            full = [torch.zeros((1,) + shapes[k], dtype=self.compute_dtype, device=sample.device) if v is None else v
+                    for k, v in enumerate(values)]
             state.set(full, None, rows)
-            self._cn_last = (rows, list(residuals), versions)
+            self._residuals_last = (state, rows, list(values), versions)
         if state.host_scale != 1.0:
             state.set_scale(1.0)
 
@@ -422,8 +390,8 @@ class _HoistedUNet(nn.Module):
         self._apply_regions(sample)
         self._apply_ip_adapter(sample)
         self._apply_seg(sample)
-        self._apply_t2i(sample, t2i)
-        self._apply_controlnet(sample, controlnet)
+        self._apply_residuals(sample, self._t2i_state(), t2i, "T2I-Adapter residuals")
+        self._apply_residuals(sample, self._cn_state(), controlnet, "ControlNet residuals")
         self._context_for(ehs)
         if not torch.is_tensor(timesteps):
             timesteps = torch.tensor(float(timesteps), dtype=torch.float32)

@@ -1918,6 +1918,37 @@ def _forget_split(x: torch.Tensor) -> None:
         lst[:] = [ent for ent in lst if ent[1] != at]
 
 
+def _residual_table(what: str, scale_table: torch.Tensor, step: torch.Tensor) -> None:
+    if scale_table.dtype != torch.float32 or scale_table.dim() != 1 or not scale_table.is_contiguous() or scale_table.numel() < 1:
+        raise BackendError(f"{what}: scale_table must be a contiguous 1-D fp32 tensor")
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise BackendError(f"{what}: step must be an int32 tensor of one entry")
+
+
+def _residual_site(x: torch.Tensor, r: torch.Tensor, stats: Optional["ColStats"]):
+    """One site as the kernel takes it - (r dense NHWC: a copy lives until the launch is queued, the statistics' buffer or None,
+    their rows per tile, their tiles; no statistics where they do not fit the shape) - or None: not dense NHWC, or a channel count
+    that is not a whole number of 16-byte vectors."""
+    rows, Cc, H, W = x.shape
+    cl = torch.channels_last
+    vec = 4 if x.dtype == torch.float32 else 8
+    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or Cc % vec or not x.is_contiguous(memory_format=cl):
+        return None
+    if not r.is_contiguous(memory_format=cl):
+        r = r.contiguous(memory_format=cl)
+    HW = H * W
+    ok = stats is not None and stats.channels == Cc and stats.rows > 0 and HW % stats.rows == 0 \
+        and stats.buf.numel() >= (rows * HW // stats.rows) * Cc * 2
+    return (r, stats.buf, stats.rows, rows * HW // stats.rows) if ok else (r, None, 0, 0)
+
+
+def _residual_add_torch(x: torch.Tensor, r: torch.Tensor, scale_table: torch.Tensor, step: torch.Tensor, weight=None) -> None:
+    s = scale_table.index_select(0, step.reshape(1).long().clamp(0, scale_table.numel() - 1))
+    if weight is not None:
+        s = s * weight
+    x.add_((r.float() * s).to(x.dtype).repeat(x.shape[0] // r.shape[0], 1, 1, 1))
+
+
 def residual_add(x: torch.Tensor, f: torch.Tensor, scale_table: torch.Tensor, step: torch.Tensor, stats: Optional["ColStats"] = None):
     """x[n] += s * f[n % f_rows] IN PLACE, s = scale_table[*step] read on the device (csrc/t2i_adapter.hip): x (rows, C, H, W)
     channels_last, f (f_rows, C, H, W) channels_last of the same dtype with f_rows a divisor of rows, scale_table fp32 and step an
@@ -1934,28 +1965,17 @@ def residual_add(x: torch.Tensor, f: torch.Tensor, scale_table: torch.Tensor, st
             or x.shape[0] % f.shape[0]:
         raise BackendError(f"residual_add: x {tuple(x.shape)} {x.dtype} and f {tuple(f.shape)} {f.dtype} must be (rows, C, H, W) and "
                            "(f_rows, C, H, W) of one dtype with f_rows a divisor of rows")
-    if scale_table.dtype != torch.float32 or scale_table.dim() != 1 or not scale_table.is_contiguous() or scale_table.numel() < 1:
-        raise BackendError("residual_add: scale_table must be a contiguous 1-D fp32 tensor")
-    if step.dtype != torch.int32 or step.numel() != 1:
-        raise BackendError("residual_add: step must be an int32 tensor of one entry")
-    rows, Cc, H, W = x.shape
-    cl = torch.channels_last
-    vec = 4 if x.dtype == torch.float32 else 8
+    _residual_table("residual_add", scale_table, step)
     _forget_split(x)
-    if x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or Cc % vec or not x.is_contiguous(memory_format=cl):
-        s = scale_table.index_select(0, step.reshape(1).long().clamp(0, scale_table.numel() - 1))
-        x.add_((f.float() * s).to(x.dtype).repeat(rows // f.shape[0], 1, 1, 1))
+    site = _residual_site(x, f, stats)
+    if site is None:
+        _residual_add_torch(x, f, scale_table, step)
         return None
-    if not f.is_contiguous(memory_format=cl):
-        f = f.contiguous(memory_format=cl)
-    HW = H * W
-    ok = stats is not None and stats.channels == Cc and stats.rows > 0 and HW % stats.rows == 0 \
-        and stats.buf.numel() >= (rows * HW // stats.rows) * Cc * 2
-    tiles = rows * HW // stats.rows if ok else 0
-    _C.check(_C.load().st_residual_add(x.data_ptr(), f.data_ptr(), rows, f.shape[0], HW, Cc, scale_table.data_ptr(), scale_table.numel(),
-                                       step.data_ptr(), _C.dtype_code(x.dtype), stats.buf.data_ptr() if ok else None,
-                                       stats.rows if ok else 0, tiles, _C.stream_ptr()), "residual_add")
-    return stats if ok else None
+    f, buf, srows, tiles = site
+    rows, Cc, H, W = x.shape
+    _C.check(_C.load().st_residual_add(x.data_ptr(), f.data_ptr(), rows, f.shape[0], H * W, Cc, scale_table.data_ptr(), scale_table.numel(),
+                                       step.data_ptr(), _C.dtype_code(x.dtype), _ptr(buf), srows, tiles, _C.stream_ptr()), "residual_add")
+    return stats if tiles else None
 
 
 def residual_add_grouped(xs, rs, scale_table: torch.Tensor, step: torch.Tensor, stats_list=None, weights: Optional[torch.Tensor] = None):
@@ -1971,35 +1991,27 @@ def residual_add_grouped(xs, rs, scale_table: torch.Tensor, step: torch.Tensor, 
                            f"statistics entries; one launch takes 1..{_C.RESIDUAL_MAX_SITES} sites with one entry each")
     stats_list = [None] * n if stats_list is None else list(stats_list)
     _C.require_device(scale_table, step, weights, *xs, *rs)
-    if scale_table.dtype != torch.float32 or scale_table.dim() != 1 or not scale_table.is_contiguous() or scale_table.numel() < 1:
-        raise BackendError("residual_add_grouped: scale_table must be a contiguous 1-D fp32 tensor")
-    if step.dtype != torch.int32 or step.numel() != 1:
-        raise BackendError("residual_add_grouped: step must be an int32 tensor of one entry")
+    _residual_table("residual_add_grouped", scale_table, step)
     if weights is not None and (weights.dtype != torch.float32 or weights.dim() != 1 or weights.numel() != n or not weights.is_contiguous()):
         raise BackendError(f"residual_add_grouped: weights must be a contiguous fp32 tensor of {n} values, one per site")
     dtype = xs[0].dtype
-    cl = torch.channels_last
-    vec = 4 if dtype == torch.float32 else 8
-    out, taken, routed, sites, keep = [None] * n, [], [], [], []
     for k, (x, r) in enumerate(zip(xs, rs)):
         if x.dim() != 4 or r.dim() != 4 or r.dtype != x.dtype or x.dtype != dtype or tuple(r.shape[1:]) != tuple(x.shape[1:]) \
                 or r.shape[0] < 1 or x.shape[0] % r.shape[0]:
             raise BackendError(f"residual_add_grouped: site {k}: x {tuple(x.shape)} {x.dtype} and r {tuple(r.shape)} {r.dtype} must be "
                                f"(rows, C, H, W) and (r_rows, C, H, W) of one dtype ({dtype}, the call's) with r_rows a divisor of rows")
+    out, taken, routed, sites, keep = [None] * n, [], [], [], []
     for k, (x, r) in enumerate(zip(xs, rs)):                 # nothing is written, and no note dropped, before the entry point has validated the launch
-        rows, Cc, H, W = x.shape
-        if dtype not in (torch.float32, torch.bfloat16, torch.float16) or Cc % vec or not x.is_contiguous(memory_format=cl):
+        site = _residual_site(x, r, stats_list[k])
+        if site is None:
             routed.append(k)
             continue
-        if not r.is_contiguous(memory_format=cl):
-            r = r.contiguous(memory_format=cl)
-        HW, st = H * W, stats_list[k]
-        ok = st is not None and st.channels == Cc and st.rows > 0 and HW % st.rows == 0 and st.buf.numel() >= (rows * HW // st.rows) * Cc * 2
-        sites.append(_C.ResidualSite(x.data_ptr(), r.data_ptr(), st.buf.data_ptr() if ok else None, rows, r.shape[0], HW, Cc,
-                                     st.rows if ok else 0, rows * HW // st.rows if ok else 0))
+        r, buf, srows, tiles = site
+        rows, Cc, H, W = x.shape
+        sites.append(_C.ResidualSite(x.data_ptr(), r.data_ptr(), _ptr(buf), rows, r.shape[0], H * W, Cc, srows, tiles))
         keep.append(r)                                     # (a channels_last copy lives until the launch is queued)
         taken.append(k)
-        out[k] = st if ok else None
+        out[k] = stats_list[k] if tiles else None
     if sites:
         w = weights
         if w is not None and len(taken) != n:              # the launch's sites are a subset: their weights, side by side
@@ -2010,11 +2022,7 @@ def residual_add_grouped(xs, rs, scale_table: torch.Tensor, step: torch.Tensor, 
     for x in xs:
         _forget_split(x)
     for k in routed:                                       # torch's route, one site at a time
-        x, r = xs[k], rs[k]
-        s = scale_table.index_select(0, step.reshape(1).long().clamp(0, scale_table.numel() - 1))
-        if weights is not None:
-            s = s * weights[k:k + 1]
-        x.add_((r.float() * s).to(x.dtype).repeat(x.shape[0] // r.shape[0], 1, 1, 1))
+        _residual_add_torch(xs[k], rs[k], scale_table, step, None if weights is None else weights[k:k + 1])
     return out
 
 

@@ -31,7 +31,7 @@ _DOWN_CONV = re.compile(r"(?:^|\.)down_blocks\.(\d+)\.downsamplers\.0\.conv$")
 _UP_RES = re.compile(r"(?:^|\.)up_blocks\.\d+\.resnets\.\d+\.")
 
 
-def _decoder_cats(gm: fx.GraphModule):
+def decoder_cats(gm: fx.GraphModule):
     """The decoder's skip concatenations in graph order: two tensors along the channels, read by an up block's resnet only."""
     cats = []
     for n in gm.graph.nodes:
@@ -71,7 +71,7 @@ def find_sites(gm: fx.GraphModule):
             sites.append((f"down_blocks.{i}.{what}.{j}", res[(i, j)], i))
         if i in down:
             sites.append((f"down_blocks.{i}.downsamplers.0", down[i], i + 1))
-    cats = _decoder_cats(gm)
+    cats = decoder_cats(gm)
     if len(cats) != len(sites):
         raise ValueError(f"controlnet: the encoder emits {len(sites)} skip tensors but the decoder has {len(cats)} skip concatenations; "
                          "the sites cannot be placed")

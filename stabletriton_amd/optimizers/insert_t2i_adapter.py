@@ -19,28 +19,14 @@ from __future__ import annotations
 
 import re
 
-import torch
 from torch import fx
 
 from ..t2i_adapter import T2IAdapterState, t2i_site
+from .insert_controlnet import decoder_cats
 
 _DOWN_CONV = re.compile(r"(?:^|\.)down_blocks\.(\d+)\.downsamplers\.0\.conv$")
 _DOWN_RES = re.compile(r"(?:^|\.)down_blocks\.(\d+)\.resnets\.(\d+)\.")
 _MID_IN = re.compile(r"(?:^|\.)mid_block\.resnets\.0\.norm1$")
-_UP_FIRST = re.compile(r"(?:^|\.)up_blocks\.0\.resnets\.0\.")
-
-
-def _first_decoder_cat(gm: fx.GraphModule):
-    for n in gm.graph.nodes:
-        if not (n.op == "call_function" and n.target in (torch.cat, torch.concat)):
-            continue
-        parts = n.args[0] if n.args else n.kwargs.get("tensors")
-        dim = n.kwargs.get("dim", n.args[1] if len(n.args) > 1 else 0)
-        if dim != 1 or not isinstance(parts, (list, tuple)) or len(parts) != 2 or not isinstance(parts[0], fx.Node):
-            continue
-        if n.users and all(u.op == "call_module" and _UP_FIRST.search(str(u.target)) for u in n.users):
-            return n
-    return None
 
 
 def find_sites(gm: fx.GraphModule):
@@ -78,7 +64,7 @@ def find_sites(gm: fx.GraphModule):
         mod = mods[reader.target]
         ch = mod.in_channels if hasattr(mod, "in_channels") else mod.num_channels
         sites.append((f"down_blocks.{i}", reader.args[0], int(ch), i, base[i] + n_res[i] - 1))
-    cat = _first_decoder_cat(gm)
+    cat = next(iter(decoder_cats(gm)), None)             # the decoder's skip concatenations in graph order: the first reads the middle block
     if cat is None:
         raise ValueError("t2i_adapter: no decoder concatenation behind the middle block; the middle site cannot be placed")
     mid = cat.args[0][0] if cat.args else cat.kwargs["tensors"][0]

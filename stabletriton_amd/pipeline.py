@@ -175,23 +175,21 @@ class DenoiseLoop:
         self._ip_state = compiled_state(unet, "ip_adapter", _ip.IPAdapter)
         if self._ip_state is not None:                     # scale table, mask weights, image K/V of this row count: allocated once, "off"
             self._ip_state.bind(rows, (lh, lw), dev)
-        # T2I-Adapter residual sites: feature buffers of `batch` rows shared by every row block, and this loop's own per-step scale
-        # table (0 = off), both read by address: allocated once, outside capture
-        self._t2i_state = compiled_state(unet, "t2i_adapter", _t2i.T2IAdapterState)
-        self.t2i_table = None
-        if self._t2i_state is not None:
-            self._t2i_state.bind(rows, (lh, lw), dev, dtype=dtype, feature_rows=batch)
-            self.t2i_table = torch.zeros(n, dtype=torch.float32, device=dev)
-        # ControlNet: the sites' state of this row count, this loop's own per-step scale table (0 = off) and - with a branch - the
-        # static buffer of the control image's embedding, `rows` rows: allocated once, outside capture
-        self._cn_state = compiled_state(unet, "controlnet", _cn.ControlNetState)
-        self.controlnet, self.controlnet_table, self.controlnet_cond = controlnet, None, None
-        if self._cn_state is not None:
-            self._cn_state.bind(rows, (lh, lw), dev, dtype=dtype)
-            self.controlnet_table = torch.zeros(n, dtype=torch.float32, device=dev)
+        # residual sites, T2I-Adapter's or ControlNet's (a UNet carries at most one of the two states): the state's buffers of this
+        # row count - T2I features of `batch` rows shared by every row block, ControlNet residuals of `rows` rows -, this loop's own
+        # per-step scale table (0 = off) under the feature's name and - with a ControlNet branch - the static buffer of the control
+        # image's embedding, `rows` rows: all read by address, allocated once, outside capture
+        t2i = compiled_state(unet, "t2i_adapter", _t2i.T2IAdapterState)
+        self._sites = t2i if t2i is not None else compiled_state(unet, "controlnet", _cn.ControlNetState)
+        self.controlnet, self.controlnet_cond, self._sites_table = controlnet, None, None
+        if self._sites is not None:
+            self._sites.bind(rows, (lh, lw), dev, dtype, batch if t2i is not None else rows)
+            self._sites_table = torch.zeros(n, dtype=torch.float32, device=dev)
             if controlnet is not None:
-                self.controlnet_cond = torch.zeros((rows, self._cn_state.channels[0], lh, lw), dtype=dtype, device=dev).contiguous(
+                self.controlnet_cond = torch.zeros((rows, self._sites.channels[0], lh, lw), dtype=dtype, device=dev).contiguous(
                     memory_format=cl)
+        self.t2i_table = self._sites_table if t2i is not None else None
+        self.controlnet_table = self._sites_table if t2i is None else None
         self._latent_hw = (th, tw)                         # what the UNet sees: the window when tiled
         if isinstance(self._perturbed, seg.SEG):           # the blur's parameter rows of this latent size: allocated once, outside capture
             self._perturbed.bind((th, tw), dev)
@@ -518,8 +516,14 @@ class DenoiseLoop:
     def set_t2i_adapter_scale(self, scale: Union[float, Sequence[float]]) -> None:
         """The sites' scale per step: a float, or n_steps floats.  Written into the device table in place: no new capture."""
         from . import t2i_adapter
-        t2i_adapter.state_of(self.unet, "set_t2i_adapter_scale")
-        self.t2i_table.copy_(self._step_table(scale, "scale", "set_t2i_adapter_scale"))
+        self._set_sites_scale(t2i_adapter, "set_t2i_adapter_scale", scale)
+
+    def _set_sites_scale(self, feature, what: str, scale, site_weights=None) -> None:
+        state = feature.state_of(self.unet, what)
+        table = self._step_table(scale, "scale", what)      # (validated before anything is written)
+        if site_weights is not None:
+            state.set_site_weights(site_weights)
+        self._sites_table.copy_(table)
 
     # ---- ControlNet (controlnet.py): in-place writes of buffers the branch and the sites read by address, no new capture --------
     def set_controlnet(self, image_or_cond_embed, scale: float = 1.0, start: float = 0.0, end: float = 1.0) -> None:
@@ -561,11 +565,7 @@ class DenoiseLoop:
         encoder order, the middle block's last; they belong to the UNet's state: loops that share one compiled UNet share them).
         Written into the device tables in place: no new capture."""
         from . import controlnet as _cn
-        state = _cn.state_of(self.unet, "set_controlnet_scale")
-        table = self._step_table(scale, "scale", "set_controlnet_scale")
-        if site_weights is not None:
-            state.set_site_weights(site_weights)
-        self.controlnet_table.copy_(table)
+        self._set_sites_scale(_cn, "set_controlnet_scale", scale, site_weights)
 
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
@@ -671,15 +671,12 @@ class DenoiseLoop:
 
     def _unet(self, t, time_row=None, step=None):
         with contextlib.ExitStack() as scopes:      # both for this loop's own calls only
-            if self._t2i_state is not None:      # the residual sites read this loop's scale table at `step`
-                scopes.enter_context(self._t2i_state.using(self.step_ids[0:1] if step is None else step, self.t2i_table))
-            if self._cn_state is not None:       # the branch on the UNet's own rows, then its outputs lent to the sites (no copies)
-                residuals = None
-                if self.controlnet is not None:
+            if self._sites is not None:          # the residual sites read this loop's scale table at `step`
+                lent = ()
+                if self.controlnet is not None:  # the branch on the UNet's own rows, then its outputs lent to the sites (no copies)
                     down, mid = self.controlnet(self.x_in, t, self.ehs, self._cond(), cond_embed=self.controlnet_cond)
-                    residuals = list(down) + [mid]
-                scopes.enter_context(self._cn_state.using(self.step_ids[0:1] if step is None else step, self.controlnet_table,
-                                                          residuals=residuals))
+                    lent = (list(down) + [mid],)
+                scopes.enter_context(self._sites.using(self.step_ids[0:1] if step is None else step, self._sites_table, *lent))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
                 scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
             return self._unet_call(t, time_row)

@@ -260,7 +260,7 @@ def test_validation_messages():
     st.set(res, 0.5)
     assert st.host_scale == 0.5 and float(st._own()[0]) == 0.5 and st._own()[2].tolist() == [1.0] * 10
     st.set([r[:1] for r in res], None)                         # one row for every batch row
-    assert st.host_scale == 0.5 and torch.equal(st._residuals[(2, 0, 16, 16)][1], res[0][0])
+    assert st.host_scale == 0.5 and torch.equal(st.buffer_for(2, 0, 16, 16)[1], res[0][0])
     with pytest.raises(ValueError, match="takes 10 residuals"):
         st.set(res[:9])
     with pytest.raises(ValueError, match=r"residual 4 .*must be \(rows, 128, h, w\)"):
@@ -279,13 +279,83 @@ def test_validation_messages():
     with pytest.raises(ValueError, match="residuals are 10 tensors"):
         with st.using(torch.zeros(1, dtype=torch.int32), torch.zeros(3), residuals=res[:3]):
             pass
-    addr = st._residuals[(2, 0, 16, 16)].data_ptr()
+    addr = st.buffer_for(2, 0, 16, 16).data_ptr()
     st.bind(2, 16, "cpu", dtype=torch.float32)
-    assert st._residuals[(2, 0, 16, 16)].data_ptr() == addr, "binding twice keeps the buffers"
+    assert st.buffer_for(2, 0, 16, 16).data_ptr() == addr, "binding twice keeps the buffers"
     plain = fx.symbolic_trace(_meta(TINY))
     with pytest.raises(ValueError, match="compiled without ControlNet sites; compile it with controlnet=True"):
         CN.state_of(plain, "set_controlnet")
     assert CN.state_of(gm, "x") is st
+
+
+def _bound_states(which):
+    """(state, values for `set`) of a traced TINY module carrying that pass, nothing bound yet."""
+    from stabletriton_amd import t2i_adapter as T
+    from stabletriton_amd.optimizers import insert_t2i_adapter
+    from tests import t2i_util as TU
+    gm = fx.symbolic_trace(_meta(TINY))
+    if which == "t2i_adapter":
+        insert_t2i_adapter(gm)
+        return T.state_of(gm, "x"), TU.features(TINY, 16, rows=2)
+    insert_controlnet(gm)
+    return CN.state_of(gm, "x"), CU.residuals(TINY, 16, rows=2)
+
+
+@pytest.mark.parametrize("which", ["t2i_adapter", "controlnet"])
+def test_both_states_share_one_base(which):
+    from stabletriton_amd.state import ResidualSites
+    st, values = _bound_states(which)
+    assert isinstance(st, ResidualSites) and st.label == which
+    st.bind(2, 16, "cpu", dtype=torch.float32)
+    keys = [(2, k, h, w) for k, (_, h, w) in enumerate(st.site_shapes(16))]
+    addrs = [st.buffer_for(*key).data_ptr() for key in keys]
+    assert len(set(addrs)) == len(st.sites) and st.bound_rows() == [2]
+    st.bind(2, 16, "cpu", dtype=torch.float32)
+    assert [st.buffer_for(*key).data_ptr() for key in keys] == addrs, "binding twice keeps every buffer at its address"
+    with pytest.raises(ValueError, match="asked for 2 .* rows of torch.float64"):
+        st.bind(2, 16, "cpu", dtype=torch.float64)
+    with pytest.raises(ValueError, match=r"nothing is bound on meta; call bind\(rows, latent_hw, device\) first"):
+        st._own("meta")
+    # one order for both: (step, table, site weights or None), the state's own outside `using`, the caller's inside
+    own = st._own()
+    assert own[0] is own.scale and own[1] is own.step and own[2] is own.weights
+    assert own.scale.dtype == torch.float32 and own.step.dtype == torch.int32 and int(own.step) == 0
+    assert (own.weights is None) == (which == "t2i_adapter")
+    cur = st.current("cpu")
+    assert len(cur) == 3 and cur[0] is own.step and cur[1] is own.scale and cur[2] is own.weights
+    step, table = torch.tensor([1], dtype=torch.int32), torch.tensor([0.0, 0.25])
+    with st.using(step, table):
+        cur = st.current("cpu")
+        assert len(cur) == 3 and cur[0] is step and cur[1] is table and cur[2] is own.weights
+    assert st._use is None and st.current("cpu")[1] is own.scale
+    st.set(values, 0.5)
+    assert st.host_scale == 0.5 and float(st._own().scale) == 0.5
+    assert all(torch.equal(st.buffer_for(*key), v) for key, v in zip(keys, values))
+    st.clear()
+    assert st.host_scale == 0.0 and float(st._own().scale) == 0.0
+    assert all(torch.equal(st.buffer_for(*key), v) for key, v in zip(keys, values)), "clear leaves the buffers alone"
+    assert [st.buffer_for(*key).data_ptr() for key in keys] == addrs
+
+
+def test_the_leaf_has_one_form_and_keeps_the_site_weights():
+    st = CN.ControlNetState([("a", 4, 0), ("b", 8, 1), ("m", 8, 1)])
+    assert not hasattr(st, "grouped")
+    st.bind(2, (6, 4), "cpu", dtype=torch.float64)
+    xs = [synth.normal(f"cn.leaf.x{k}", (2, c, h, w), 11 + k).double() for k, (c, h, w) in enumerate(st.site_shapes((6, 4)))]
+    rs = [synth.normal(f"cn.leaf.r{k}", (2, c, h, w), 21 + k).double() for k, (c, h, w) in enumerate(st.site_shapes((6, 4)))]
+    st.set(rs, 0.75)
+    w = [0.5, 0.0, 1.5]
+    st.set_site_weights(w)
+    assert st._own().weights.tolist() == w
+    out = CN.controlnet_sites(xs[2], xs[:2], st)
+    assert len(out) == 6 and out[3:] == (None, None, None)
+    for k in range(3):
+        assert torch.equal(out[k], xs[k] + (0.75 * w[k]) * rs[k]) if w[k] else out[k] is xs[k]
+    table, step = torch.tensor([0.0, 0.25]), torch.tensor([1], dtype=torch.int32)
+    lent = [2.0 * r for r in rs]
+    with st.using(step, table, residuals=lent):                # the caller's table and tensors, the state's weights
+        out = CN.controlnet_sites(xs[2], xs[:2], st)
+    assert torch.equal(out[0], xs[0] + (0.25 * 0.5) * lent[0]) and out[1] is xs[1] and torch.equal(out[2], xs[2] + (0.25 * 1.5) * lent[2])
 
 
 def test_comfy_control_lists_land_on_the_sites():

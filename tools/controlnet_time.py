@@ -1,4 +1,4 @@
-"""What ControlNet costs per step on SDXL-base bf16 at 1024 x 1024 (latent 128), bs = 1, guided (2 UNet rows), mode loop: four
+"""What ControlNet costs per step on SDXL-base bf16 at 1024 x 1024 (latent 128), bs = 1, guided (2 UNet rows), mode loop: three
 variants of the captured loop, same weights, alternated in one process.
 
     python tools/controlnet_time.py [--spec sdxl|tiny] [--steps 20] [--runs 5] [--out profiles/controlnet_time.json]
@@ -7,7 +7,6 @@ One JSON object:
   a_ms_per_step   (a) a UNet compiled WITHOUT sites: the default graph
   b_ms_per_step   (b) sites compiled in, no branch, scale 0: one launch per step that reads its scale and leaves;   b_minus_a_ms
   c_ms_per_step   (c) the compiled branch + the sites at scale 0.8 in ONE grouped launch;                           c_minus_a_ms
-  d_ms_per_step   (d) as (c) with the sites as one st_residual_add launch each (state.grouped = False);             d_minus_c_ms
   *_min_max       min and max over the runs: the spread the deltas are to be read against
   floor_us        the sites' own traffic - x read and written, the residuals read: 3 x tensor bytes - at 6.3 TB/s
   kernel          the launch alone on the sites' shapes (statistics rewritten where 256 rows per tile divide the image): microseconds
@@ -15,7 +14,7 @@ One JSON object:
                   launches (buffers resident in the caches; the boundary between two launches is inside the figure), and the ratio
                   of the grouped launch to the floor
 Each run is one replay of the loop graph (host clock around a device synchronise) after one warm-up replay of each; medians
-over --runs.  (c) and (d) share one loop and one captured graph each; the branch runs in both.
+over --runs.
 """
 import argparse
 import json
@@ -122,37 +121,32 @@ def main():
     state = sites.controlnet
     shapes = state.site_shapes(latent)
     cond = synth.normal("controlnet.time.cond", (1, spec.widths[0], latent, latent), 5).to(dev, dt)
-    times = {k: [] for k in "abcd"}
+    times = {k: [] for k in "abc"}
     finite = True
     with torch.no_grad():
         loops = {"a": make_loop(without, spec, latent, dt, dev, args.steps, x), "b": make_loop(sites, spec, latent, dt, dev, args.steps, x),
-                 "c": make_loop(sites, spec, latent, dt, dev, args.steps, x, branch), "d": make_loop(sites, spec, latent, dt, dev, args.steps, x, branch)}
+                 "c": make_loop(sites, spec, latent, dt, dev, args.steps, x, branch)}
         loops["c"].set_controlnet(cond, 0.8)
-        loops["d"].set_controlnet(cond, 0.8)
-        for name in "abcd":                                        # the form of the sites is fixed when a loop's graph is captured
-            state.grouped = name != "d"
+        for name in "abc":
             loops[name].capture()
-        state.grouped = True
         for i in range(args.runs + 1):                             # (round 0 warms the graphs up)
-            for name in "abcd":
+            for name in "abc":
                 loop = loops[name]
                 loop.set_noise(noise)
                 t = timed(lambda: loop.run_steps(args.steps), dev)
                 finite = finite and bool(torch.isfinite(loop.latent).all())
                 if i:
                     times[name].append(t / args.steps)
-        same = bool(torch.equal(loops["c"].latent, loops["d"].latent))
         kernel = kernel_alone(shapes, 2, dt, dev, args.kernel_iters)
     med = {k: statistics.median(v) for k, v in times.items()}
     res = {"tool": "controlnet_time", "spec": args.spec, "dtype": "bf16", "latent": latent, "unet_rows": 2, "steps": args.steps,
-           "runs": args.runs, "sites": [list(s) for s in shapes], "finite": finite, "c_equals_d_bits": same,
+           "runs": args.runs, "sites": [list(s) for s in shapes], "finite": finite,
            "floor_us": kernel["floor_us"], "kernel": kernel}
-    for k in "abcd":
+    for k in "abc":
         res[f"{k}_ms_per_step"] = round(med[k], 4)
         res[f"{k}_min_max"] = [round(min(times[k]), 4), round(max(times[k]), 4)]
     res["b_minus_a_ms"] = round(med["b"] - med["a"], 4)
     res["c_minus_a_ms"] = round(med["c"] - med["a"], 4)
-    res["d_minus_c_ms"] = round(med["d"] - med["c"], 4)
     line = json.dumps(res)
     print(line)
     if args.out:
