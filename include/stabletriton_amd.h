@@ -589,6 +589,32 @@ int st_tile_gather(const void* canvas, void* windows, int rows, int H, int W, in
 int st_tile_blend(const void* windows, void* canvas, const float* weights, int rows, int H, int W, int h, int w, int C,
                   const int* ys, int ny, const int* xs, int nx, int wrap_w, int dtype, void* stream);
 
+/* ---- Masked inpainting (no reference counterpart: the post-step blend of diffusers' StableDiffusionXLInpaintPipeline; with a
+ * threshold table, Differential Diffusion).  Added after ABI 18 without a bump: a new entry point, no existing signature or contract
+ * changed.
+ *
+ * st_inpaint_blend runs BEHIND a sampler step, on what the step wrote: latent (batch, HW, C) fp32 and next_in, `blocks` row blocks of
+ * (batch, HW, C) in `dtype` (ST_BF16, ST_F16, ST_F32), row r * batch + b for sample b - the denoise loop's layout, every row block the
+ * same latent.  init and noise: (batch, HW, C) fp32, the latent to keep and the trajectory's unit start noise.  All dense NHWC, C a
+ * multiple of 4.  mask: (mask_rows, HW) fp32 with mask_rows 1 (one mask for every sample) or batch; 1 = repaint, 0 = keep.  thr (may be
+ * NULL), sigma_next and in_scale are DEVICE tables of n_steps floats, step a DEVICE int; all are read when the kernel runs (a captured
+ * graph sees new values).  With i = *step clamped to [0, n_steps), s = sigma_next[i], sc = in_scale[min(i + 1, n_steps - 1)], per
+ * pixel with mask value m:
+ *   w = m                      when thr == NULL, or when thr[i] is NaN (the table's own "no threshold at this step": one captured
+ *                              launch serves both forms),
+ *   w = (m > thr[i]) ? 1 : 0   otherwise;
+ *   w = !(w < 1) ? 1 : max(w, 0): NaN and values of 1 or more repaint, negative values keep;
+ *   w == 1: nothing of the pixel is written, neither latent nor any next_in row (mask all ones: the buffers keep the step's bits);
+ *   else    per element known = fma(s, noise, init), v = (w == 0) ? known : fma(w, latent - known, known); latent = v, and every one
+ *           of the `blocks` rows of next_in = (dtype)(v * sc).
+ * One thread per pixel, no atomics: two launches give the same bits.  Rejected before any launch: null pointers (thr excepted), an
+ * unsupported dtype, non-positive sizes, C % 4 != 0, mask_rows other than 1 or batch, blocks < 1, latent / init / noise / next_in not
+ * 16-byte aligned, mask / tables / step not 4-byte aligned, latent overlapping init, noise, mask or next_in, sizes past the index
+ * range.  64-bit index arithmetic throughout (csrc/inpaint.hip). */
+int st_inpaint_blend(float* latent, void* next_in, const float* init, const float* noise, const float* mask,
+                     const float* thr, const float* sigma_next, const float* in_scale, const int* step,
+                     int batch, int blocks, long HW, int C, int mask_rows, int n_steps, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -73,6 +73,7 @@ SIGNATURES = {
     "st_residual_add_grouped": (_i, [_p, _i, _p, _p, _i, _p, _i, _p]),
     "st_tile_gather": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
     "st_tile_blend": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
+    "st_inpaint_blend": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _i, _i, _p]),
 }
 
 

@@ -2066,3 +2066,39 @@ def tile_blend(windows: torch.Tensor, canvas: torch.Tensor, weights: torch.Tenso
                            f"{tuple(weights.shape)}")
     _C.check(_C.load().st_tile_blend(windows.data_ptr(), canvas.data_ptr(), weights.data_ptr(), *g, int(bool(wrap_w)),
                                      _C.dtype_code(canvas.dtype), _C.stream_ptr()), "tile_blend")
+
+
+# ----------------------------------------------------------------------------- masked inpainting: the blend behind the sampler step
+def inpaint_blend(latent: torch.Tensor, next_in: torch.Tensor, init: torch.Tensor, noise: torch.Tensor, mask: torch.Tensor,
+                  sigma_next: torch.Tensor, in_scale: torch.Tensor, step: torch.Tensor, thr: Optional[torch.Tensor] = None) -> None:
+    """In place, behind a sampler step (csrc/inpaint.hip, st_inpaint_blend): latent, init, noise (B, C, H, W) fp32 channels_last; next_in
+    (blocks * B, C, H, W) channels_last, every row block the same latent; mask fp32 (1 | B, H, W), 1 = repaint, 0 = keep; sigma_next,
+    in_scale and thr fp32 tables of n_steps values, step an int32 device tensor of one entry.  i = *step: w = mask, or with a threshold
+    (thr given and thr[i] not NaN) w = mask > thr[i]; a pixel at w == 1 is not written at all; the others take
+    known + w (latent - known) with known = init + sigma_next[i] noise, and next_in that value times in_scale[i + 1]."""
+    _C.require_device(latent, next_in, init, noise, mask, sigma_next, in_scale, step, thr)
+    cl = torch.channels_last
+    if latent.dim() != 4 or latent.dtype != torch.float32 or not latent.is_contiguous(memory_format=cl):
+        raise BackendError("inpaint_blend: latent must be a dense channels_last (NHWC) fp32 tensor (B, C, H, W)")
+    B, Cc, H, W = latent.shape
+    for name, t in (("init", init), ("noise", noise)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, Cc, H, W) or not t.is_contiguous(memory_format=cl):
+            raise BackendError(f"inpaint_blend: {name} must be fp32 channels_last of the latent's shape {(B, Cc, H, W)}, got {t.dtype} "
+                               f"{tuple(t.shape)}")
+    if next_in.dim() != 4 or next_in.shape[0] < B or next_in.shape[0] % B or tuple(next_in.shape[1:]) != (Cc, H, W) \
+            or not next_in.is_contiguous(memory_format=cl):
+        raise BackendError(f"inpaint_blend: next_in must be channels_last (blocks * {B}, {Cc}, {H}, {W}), got {tuple(next_in.shape)}")
+    if Cc % 4:
+        raise BackendError(f"inpaint_blend: channel count {Cc} must be a multiple of 4")
+    if mask.dtype != torch.float32 or mask.dim() != 3 or mask.shape[0] not in (1, B) or tuple(mask.shape[1:]) != (H, W) \
+            or not mask.is_contiguous():
+        raise BackendError(f"inpaint_blend: mask must be a contiguous fp32 (1 | {B}, {H}, {W}) tensor, got {mask.dtype} {tuple(mask.shape)}")
+    n = sigma_next.numel()
+    for name, t in (("sigma_next", sigma_next), ("in_scale", in_scale), ("thr", thr)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or n < 1 or not t.is_contiguous()):
+            raise BackendError(f"inpaint_blend: {name} must be a contiguous fp32 table of n_steps = {n} values")
+    if step.dtype != torch.int32 or step.numel() != 1:
+        raise BackendError("inpaint_blend: step must be an int32 tensor of one entry")
+    _C.check(_C.load().st_inpaint_blend(latent.data_ptr(), next_in.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr(), _ptr(thr),
+                                        sigma_next.data_ptr(), in_scale.data_ptr(), step.data_ptr(), B, next_in.shape[0] // B, H * W, Cc,
+                                        mask.shape[0], n, _C.dtype_code(next_in.dtype), _C.stream_ptr()), "inpaint_blend")

@@ -91,6 +91,16 @@ window, sample-major).  PAG and SEG work (their row block is outermost; the pert
 compiled with `regions`, `ip_adapter`, `t2i_adapter` or `controlnet` are refused: their states bind per latent size and row count, and cropping them
 per window is not built.  The fp8 plan is allowed with tiles and not covered by tests.  `tile_hw=None` is the untiled loop exactly:
 `x_step is x_in`, no further buffers or launches.
+
+Masked inpainting (`inpaint=True`, `set_inpaint`; inpaint.py) keeps part of an image fixed: behind every sampler update one more launch,
+`st_inpaint_blend`, puts the pixels to keep back to init + sigma[i + 1] * noise (the trajectory's own start noise, which `set_noise` and
+`set_image` also copy into a static buffer) on the fp32 latent and rewrites the next input of every row block; a pixel to repaint is
+not written.  The blend is behind the step, so every sampler, CFG, rescale, PAG and SEG, LoRA and FreeU are as before, the DPM history
+is left alone, and a tiled loop blends on the canvas, ahead of `st_tile_gather`.  Init latent, mask and the differential mode's threshold
+table are device buffers read by address: `set_inpaint` is an in-place write, before or after `capture()`; binary / soft and threshold
+mode share the captured launch (a NaN threshold entry = no threshold).  Mask all ones - the state until `set_inpaint`, and after
+`set_inpaint(None)` - writes nothing: the bits of a loop built without the flag, at one early-exit launch per step.  `inpaint=False` is
+the present loop exactly: no buffers, no launch.  Not built: nine-channel inpainting checkpoints, mask resampling.
 """
 from __future__ import annotations
 
@@ -114,7 +124,8 @@ class DenoiseLoop:
                  guidance_rescale: Optional[Union[float, Sequence[float]]] = None,
                  pag_scale: Optional[Union[float, Sequence[float]]] = None,
                  seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf"),
-                 tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform", controlnet: Optional[Callable] = None):
+                 tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform", controlnet: Optional[Callable] = None,
+                 inpaint: bool = False):
         assert mode in ("loop", "step", "eager")
         if seg_scale is not None and pag_scale is not None:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
@@ -237,6 +248,16 @@ class DenoiseLoop:
         if pag_scale is not None:
             self.pag = torch.zeros(n, dtype=torch.float32, device=dev)
             self.pag.copy_(self._step_table(pag_scale, "scale", "set_seg" if isinstance(self._perturbed, seg.SEG) else "set_pag"))
+        # masked inpainting (inpaint.py): the latent to keep, the trajectory's unit start noise, the mask (all ones = "off": the blend
+        # writes nothing), the threshold table of the differential mode (a NaN entry = no threshold at that step: the mask is the
+        # blend weight itself) and sigma[i + 1] per step; canvas-sized when tiled, read by address, allocated once, outside capture
+        self.inpaint_init = self.inpaint_noise = self.inpaint_mask = self.inpaint_thr = self.sigma_next = None
+        if inpaint:
+            self.inpaint_init = torch.zeros_like(self.latent)
+            self.inpaint_noise = torch.zeros_like(self.latent)
+            self.inpaint_mask = torch.ones((batch, lh, lw), dtype=torch.float32, device=dev)
+            self.inpaint_thr = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+            self.sigma_next = torch.tensor(self.tables.sigmas[1:], dtype=torch.float32, device=dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -352,6 +373,48 @@ class DenoiseLoop:
             raise ValueError("set_tile_weights: this loop was built without tile_hw")
         from . import tiles
         self.tile_weights.copy_(tiles.weight_map(weights, self.tile_grid.tile_hw))
+
+    def set_inpaint(self, init_latent: Optional[torch.Tensor], mask=None, differential: bool = False, thresholds=None) -> None:
+        """Masked inpainting (inpaint.py): keep `init_latent` (B or 1, 4, lh, lw) where `mask` is 0 and repaint where it is 1; the
+        mask is (lh, lw), (1 | B, lh, lw) or (1 | B, 1, lh, lw) AT LATENT RESOLUTION (the canvas when tiled; inpaint.prepare_mask: finite,
+        in [0, 1], never resampled).  Behind every sampler step the pixels to keep are put back to init + sigma[i + 1] * noise with the
+        trajectory's own start noise (what set_noise / set_image / a seed started it from), a fractional mask value blends, and after
+        the last step (sigma = 0) a pixel at mask 0 is `init_latent` bit for bit.  `differential=True` reads the mask as a change
+        map (Differential Diffusion): a pixel of value m is frozen after step i while m <= thr[i], thr = `thresholds` (n_steps
+        floats in [0, 1]) or inpaint.differential_thresholds(n_steps).  `set_inpaint(None)` is "off": the mask is all ones, the
+        blend writes nothing, and the loop gives the bits of one built without `inpaint`.
+
+        In-place writes of device buffers the captured graph reads by address, legal before or after `capture()`, never a new
+        capture.  The two modes share one captured launch: the threshold table is always passed, and a table of NaN - the state
+        without `differential` - tells the kernel to take the mask itself as the weight.  All arguments are validated before
+        anything is written.  Strength 1: mode "loop", `set_inpaint`, `denoise`.  Partial strength: `set_image(init, noise, strength)`
+        in mode "step" / "eager", `set_inpaint(init, mask)`, `run_steps`."""
+        if self.inpaint_mask is None:
+            raise ValueError("set_inpaint: this loop was built without inpaint=True")
+        from . import inpaint
+        if init_latent is None:
+            if mask is not None or differential or thresholds is not None:
+                raise ValueError("set_inpaint: takes (init_latent, mask[, differential, thresholds]) or None")
+            self.inpaint_mask.fill_(1.0)
+            self.inpaint_thr.fill_(float("nan"))
+            return
+        if mask is None:
+            raise ValueError("set_inpaint: a mask is needed with init_latent (1 = repaint, 0 = keep)")
+        init = torch.as_tensor(init_latent)
+        if init.dim() != 4 or init.shape[0] not in (1, self.batch) or tuple(init.shape[1:]) != tuple(self.latent.shape[1:]):
+            raise ValueError(f"set_inpaint: init_latent must be (1 | {self.batch}, {', '.join(str(v) for v in self.latent.shape[1:])}), got "
+                             f"{tuple(init.shape)}")
+        m = inpaint.prepare_mask(mask, self.batch, tuple(self.latent.shape[-2:]))
+        if thresholds is not None and not differential:
+            raise ValueError("set_inpaint: thresholds need differential=True")
+        thr = torch.full((self.n_steps,), float("nan"), dtype=torch.float32)
+        if differential:
+            thr = inpaint.differential_thresholds(self.n_steps) if thresholds is None else self._step_table(thresholds, "thresholds", "set_inpaint")
+            if thr.numel() != self.n_steps or not bool(torch.isfinite(thr).all()) or bool((thr < 0).any()) or bool((thr > 1).any()):
+                raise ValueError(f"set_inpaint: thresholds are {self.n_steps} finite values in [0, 1]")
+        self.inpaint_init.copy_(init.detach().to(self.device, torch.float32).expand_as(self.inpaint_init))
+        self.inpaint_mask.copy_(m.expand_as(self.inpaint_mask))
+        self.inpaint_thr.copy_(thr)
 
     def _rederive_conditioning(self) -> None:
         """Everything the loop computes once per prompt from the weights and its own static `ehs`, `text_embeds` and
@@ -607,6 +670,8 @@ class DenoiseLoop:
             if seed is None:
                 raise ValueError("set_noise: pass latent_unit, seed, or both")
             latent_unit = self._seeded_unit(0)
+        if self.inpaint_noise is not None:                 # the noise the blend re-noises the kept pixels with
+            self.inpaint_noise.copy_(latent_unit)
         self.latent.copy_(latent_unit.to(self.device, torch.float32) * self.tables.init_noise_sigma)
         self._write_input(float(self.tables.in_scale()[0]))
         self.step.zero_()
@@ -632,6 +697,8 @@ class DenoiseLoop:
             if seed is None:
                 raise ValueError("set_image: pass noise_unit, seed, or both")
             noise_unit = self._seeded_unit(0)
+        if self.inpaint_noise is not None:
+            self.inpaint_noise.copy_(noise_unit)
         sigma = float(self.tables.sigmas[t_start])
         lat = init_latent.to(self.device, torch.float32) + noise_unit.to(self.device, torch.float32) * sigma
         self.latent.copy_(lat)
@@ -709,6 +776,9 @@ class DenoiseLoop:
             ops.tile_blend(eps, self.eps_canvas, self.tile_weights, g.ys, g.xs, g.wrap_w)
             eps = self.eps_canvas
         self._sampler_update(eps, step)
+        if self.inpaint_mask is not None:                  # behind the update, on what it wrote: pixels to repaint are not touched
+            ops.inpaint_blend(self.latent, self.x_step, self.inpaint_init, self.inpaint_noise, self.inpaint_mask, self.sigma_next,
+                              self.in_scale, step, self.inpaint_thr)
         self._gather_windows()
 
     def _sampler_update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
