@@ -58,7 +58,7 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               st_sde_step and st_philox_normal, and then st_lora_merge, and then
                                               st_freeu, st_freeu_workspace_bytes and st_freeu_stat_rows, and then st_attention_pag,
                                               st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then a DoRA and a LoHa / LoKr entry point beside
-                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed (st_attention_regions and st_attention_segments, after 18, likewise);
+                                              st_lora_merge, added without a bump: new entry points, no existing signature or contract changed (st_attention_regions, st_attention_segments and st_attention_joint, after 18, likewise);
                                               18: st_lora_merge takes one ST_LORA_FORM_WORDS segment row, the norm pass's tables and `forms`, and is
                                               the only LoRA entry point again: the two beside it are removed) */
 const char* st_last_error(void);           /* host string, thread-local     */
@@ -508,6 +508,34 @@ int st_attention_regions(const void* q, const void* k, const void* v, const floa
 typedef struct { const void* k; const void* v; long ldk, ldv; long bsk, bsv; int len; } st_kv_segment;
 int st_attention_segments(const void* q, const st_kv_segment* segs, int S, const float* weights, const float* seg_scale,
                           void* out, int B, int T, int H, int D, long ldq, long ldo, float scale, int dtype, void* stream);
+
+/* ---- two-source self-attention (no reference counterpart: reference-only control - A1111's ControlNet `reference_only`,
+ * ComfyUI's ReferenceOnlySimple, diffusers' community stable_diffusion_xl_reference pipeline): every query row attends to its own
+ * keys AND to the keys of a reference row, under ONE softmax.  ABI 18, added without a bump: a new entry point, no existing
+ * signature or contract changed.
+ *
+ * st_attention_joint: q (B, T, H*D), k / v (B, S1, H*D) as st_attention takes them (batch strides T*ldq, S1*ldk, S1*ldv);
+ * k2 / v2: B2 entries of S2 keys, token strides ldk2 / ldv2 and batch strides bsk2 / bsv2 in elements (as st_kv_segment);
+ *   out[b,t,h,:] = softmax_s( scale * q[b,t,h] . Kcat[b,s,h] ) Vcat[b,s,h]
+ *   Kcat[b] = [ k[b, 0:S1] ; k2[b % B2, 0:S2_eff(b)] ]      (V likewise)
+ *   S2_eff(b) = S2 if b < lead and the gate is on, else 0.
+ * The gate: on iff gate_table == NULL (then gate_step must be NULL too), or gate_table[clamp(*gate_step, 0, gate_n - 1)] != 0;
+ * DEVICE memory read at every launch (one scalar load of a value no launch writes: uniform over the grid), so a captured launch
+ * follows in-place writes of the table and of the step counter.
+ * Bit contracts (tile partition and arithmetic are st_attention's; only the address a key row is read from differs):
+ *   (a) gate on and b < lead: the bits of st_attention on the contiguous concatenation of the two sources;
+ *   (b) gate off, or b >= lead: the bits of st_attention with S = S1; k2 and v2 are NEVER READ and need not be finite.
+ * The kernel form (3, 4 or 7 compute waves with a loader wave, or 8 self-loading waves) is st_attention's choice for (T, H, B).
+ * dtype ST_BF16 or ST_F16, D = 64, S1 >= 256 (so that both contracts compare with one kernel family), S2 >= 1, B2 >= 1,
+ * 0 <= lead <= B; anything else is rejected (the Python host has a slow path).  All pointers 16-byte aligned; every stride a
+ * multiple of 8, token strides under 2^31, ldk2 / ldv2 >= H*D, bsk2 / bsv2 >= 0 (0: one second source for every entry), ldo a
+ * multiple of 4.  One launch, no atomics, nothing written but the B*T*H*64 values of out; never emits a split image
+ * (csrc/attention_joint.hip).  Parity with A1111, ComfyUI and diffusers is unpinned; their `style_fidelity`, a continuous
+ * strength and the AdaIN variant are out of scope. */
+int st_attention_joint(const void* q, const void* k, const void* v, const void* k2, const void* v2, void* out,
+                       int B, int T, int S1, int S2, int B2, int lead, int H, int D,
+                       long ldq, long ldk, long ldv, long ldk2, long ldv2, long bsk2, long bsv2, long ldo, float scale,
+                       const float* gate_table, const int* gate_step, int gate_n, int dtype, void* stream);
 
 /* The three updates with a third noise prediction: st_cfg_euler_step, st_dpmpp2m_step and st_sde_step with one more device table
  * `pag` of n_steps floats (never NULL) and one more row block of eps / next_in, the prediction under perturbed self-attention.

@@ -63,6 +63,7 @@ SIGNATURES = {
     "st_attention_pag": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _p]),
     "st_attention_regions": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _p]),
     "st_attention_segments": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _l, _l, _f, _i, _p]),
+    "st_attention_joint": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _l, _f, _p, _p, _i, _i, _p]),
     "st_pag_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),

@@ -390,6 +390,7 @@ static int attention16_launch(const void* q, const void* k, const void* v, void*
     // batch 4 43.8 -> 39.2 us.
     // Three compute waves (96 rows) when four would still leave a third of the CUs without a block: the 32x32 level at batch 1
     // is 220 blocks instead of 160 (15.3 -> 13.9 us).
+    // (attention_joint.hip's attention_joint_launch restates this rule, and tests/edge_util.py's attention_kernel too: change all three together)
     int nw = (long)cdiv(T, 256) * H * B <= 128 ? 4 : 7;
     if (nw == 4 && (long)cdiv(T, 128) * H * B <= 176 && (long)cdiv(T, 96) * H * B <= 256) nw = 3;
     // Eight self-loading waves (256 rows per block) where that saves a whole round of blocks over seven + loader (224 rows): a round

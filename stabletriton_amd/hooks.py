@@ -120,10 +120,38 @@ class _HoistedUNet(nn.Module):
         self._perturbed_chunks = 0
 
     def _perturbed_scope(self, chunks: int, latent_hw):
-        """The PAG or SEG state's `using` (a module has at most one of them) around this wrapper's own calls."""
-        from . import pag, seg
+        """The PAG, SEG or reference state's `using` (a module has at most one of them) around this wrapper's own calls."""
+        from . import pag, reference, seg
+        ref = compiled_state(self.compiled, "reference", reference.ReferenceRows)
+        if ref is not None:
+            return ref.using(chunks)
         state = compiled_state(self.compiled, "pag", pag.PAG) or compiled_state(self.compiled, "seg", seg.SEG)
         return state.using(chunks, latent_hw) if state is not None else contextlib.nullcontext()
+
+    # ---- reference-only control (reference.py): which rows of a call are the reference rows; one captured graph per setting ----
+    def enable_reference(self, chunks: int) -> None:
+        """The last B // chunks batch rows of every following call are reference rows: at the sites compiled in with
+        `reference_layers` every other row attends to its own tokens and to the tokens of its reference row (row lead + b % (B //
+        chunks), lead = B - B // chunks) under one softmax; 3 for [uncond | cond | reference], 2 for [generated | reference].  The
+        caller orders its batch with the reference rows last, noises them itself and drops their prediction.  Raises on a wrapper
+        compiled without `reference_layers`."""
+        from . import reference
+        reference.state_of(self.compiled, "enable_reference")
+        if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 2:
+            raise ValueError(f"enable_reference: chunks must be an integer of 2 or more (3 or 2), got {chunks!r}")
+        self._perturbed_chunks = chunks
+
+    def disable_reference(self) -> None:
+        from . import reference
+        reference.state_of(self.compiled, "disable_reference")
+        self._perturbed_chunks = 0
+
+    def _apply_reference(self, sample: torch.Tensor) -> None:
+        """The state's own always-on gate on this call's device: allocated outside any capture (the sites only look it up)."""
+        from . import reference
+        state = compiled_state(self.compiled, "reference", reference.ReferenceRows)
+        if state is not None and self._perturbed_chunks and not torch.cuda.is_current_stream_capturing():
+            state.own_gate(sample.device)
 
     # ---- smoothed energy guidance (seg.py): which rows of a call take blurred queries; sigma is a device row, written in place ----
     def enable_seg(self, chunks: int, sigma: float = float("inf")) -> None:
@@ -390,6 +418,7 @@ class _HoistedUNet(nn.Module):
         self._apply_regions(sample)
         self._apply_ip_adapter(sample)
         self._apply_seg(sample)
+        self._apply_reference(sample)
         self._apply_residuals(sample, self._t2i_state(), t2i, "T2I-Adapter residuals")
         self._apply_residuals(sample, self._cn_state(), controlnet, "ControlNet residuals")
         self._context_for(ehs)
@@ -477,7 +506,7 @@ class DiffusersUNet(_HoistedUNet):
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                                  region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                                 controlnet: bool = False) -> DiffusersUNet:
+                                 controlnet: bool = False, reference_layers=None) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
@@ -493,7 +522,9 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     `t2i_adapter=True` compiles the T2I-Adapter residual sites in (t2i_adapter.py): `down_intrablock_additional_residuals` of a call
     are then added at the sites (None: off, at no cost), ControlNet's residual arguments raise.
     `controlnet=True` compiles the ControlNet sites in (controlnet.py; not with `t2i_adapter`): `down_block_additional_residuals` and
-    `mid_block_additional_residual` of a call are then added for the decoder (None: off), the T2I-Adapter's argument raises."""
+    `mid_block_additional_residual` of a call are then added for the decoder (None: off), the T2I-Adapter's argument raises.
+    `reference_layers=(".*",)` compiles the reference-only sites in (reference.py; not with `pag_layers` / `seg_layers`):
+    `enable_reference(chunks)` / `disable_reference()` then say which rows of a call are the reference rows."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
@@ -501,19 +532,20 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model = model.to_empty(device=device).to(dtype)
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
-                              ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet)
+                              ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
+                              reference_layers=reference_layers)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                         regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                        controlnet: bool = False):
+                        controlnet: bool = False, reference_layers=None):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
                                              regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers,
-                                             t2i_adapter=t2i_adapter, controlnet=controlnet)
+                                             t2i_adapter=t2i_adapter, controlnet=controlnet, reference_layers=reference_layers)
     return pipe
 
 
@@ -543,7 +575,7 @@ class ComfyUNet(_HoistedUNet):
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                        region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                       controlnet: bool = False) -> ComfyUNet:
+                       controlnet: bool = False, reference_layers=None) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
@@ -555,19 +587,21 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
     is consumed the way ComfyUI's apply_control does (from the end of each list, None entries skipped) and must land on the sites.
     `controlnet=True`: with ControlNet sites (not with `t2i_adapter`): `control={"output": [...], "middle": [...]}` of a call, entry i of
     `output` being skip i in encoder order (ComfyUI pops from the end while the decoder consumes its skips last-first); a non-empty
-    `"input"` raises."""
+    `"input"` raises.  `reference_layers=(".*",)`: with reference-only sites (the ReferenceOnlySimple node's batch of
+    [generated | reference] latents is `enable_reference(2)`)."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
                               region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
-                              controlnet=controlnet)
+                              controlnet=controlnet, reference_layers=reference_layers)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                       regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                      controlnet: bool = False) -> ComfyUNet:
+                      controlnet: bool = False, reference_layers=None) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
     adapter = compile_comfy_unet(unet, cuda_graph, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
-                                 ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet)
+                                 ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
+                                 reference_layers=reference_layers)
     model_patcher.model.diffusion_model = adapter
     return adapter

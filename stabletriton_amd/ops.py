@@ -1287,6 +1287,92 @@ def attention_segments(q: torch.Tensor, segments, weights: torch.Tensor, seg_sca
     return out
 
 
+JOINT_MIN_S1 = 256            # st_attention_joint: the first source's fewest keys (below it st_attention is on another kernel family)
+
+
+def _gate_on(gate, what: str) -> Optional[torch.Tensor]:
+    """`gate` = (step, table) -> a bool tensor of one entry, table[clamp(*step)] != 0, made on the device; None -> None (always on)."""
+    if gate is None:
+        return None
+    step, table = gate
+    _residual_table(what, table, step)
+    return table.index_select(0, step.reshape(1).long().clamp(0, table.numel() - 1)) != 0
+
+
+def attention_joint(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor, num_heads: int, scale: float,
+                    lead: Optional[int] = None, gate=None, fused: Optional[bool] = None) -> torch.Tensor:
+    """Self-attention over two key/value sources under ONE softmax - reference-only control (reference.py,
+    csrc/attention_joint.hip): q (B, T, H*D) and k / v (B, S1, H*D) as `attention` takes them; k2 / v2 (B2, S2, H*D) with unit stride
+    along the last axis (column and batch slices of the fused q|k|v buffer are taken as they are).  Batch entry b < `lead` (None: B)
+    attends to [k[b] ; k2[b % B2]], every other entry to k[b] alone.  `gate` = (step, table): an int32 device tensor of one entry and
+    a contiguous fp32 device table, read at every launch; with table[clamp(*step)] == 0 every entry attends to k[b] alone and k2 / v2
+    are never read by the kernel (they need not be finite).  None: always on.
+    bf16 / fp16 at head size 64 with S1 >= 256 is ONE launch: the bits of `attention` on the concatenated sources for the lead
+    entries with the gate on, the bits of `attention(q, k, v)` otherwise.  Everything else (fp32 strict mode, other head sizes,
+    short S1) takes the slow path: `torch.cat` of the sources and `attention` on the lead entries, `attention` on the rest, and with
+    a device gate a `torch.where` between the joint and the plain result of the lead entries (both are computed; the discarded one
+    may be NaN when k2 / v2 are not finite) - all legal inside a capture.  fused=False forces the slow path, fused=True raises where
+    the kernel does not apply.  CPU tensors take the plain torch statement of reference.joint_attention_reference."""
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3 or k2.dim() != 3 or v2.dim() != 3:
+        raise BackendError("attention_joint expects (B, T, H*D) tensors")
+    B, T, Cc = q.shape
+    S1, B2, S2 = k.shape[1], k2.shape[0], k2.shape[1]
+    D = Cc // num_heads
+    lead = B if lead is None else int(lead)
+    if not 0 <= lead <= B:
+        raise BackendError(f"attention_joint: lead {lead} outside [0, B = {B}]")
+    if k.shape != v.shape or k.shape[0] != B or k.shape[2] != Cc or k2.shape != v2.shape or k2.shape[2] != Cc or B2 < 1 or S2 < 1:
+        raise BackendError(f"attention_joint: k / v must be (B, S1, H*D) and k2 / v2 (B2, S2, H*D) for q {tuple(q.shape)}, got k {tuple(k.shape)}, "
+                           f"v {tuple(v.shape)}, k2 {tuple(k2.shape)}, v2 {tuple(v2.shape)}")
+    if len({t.dtype for t in (q, k, v, k2, v2)}) != 1:
+        raise BackendError("attention_joint: q, k, v, k2 and v2 must share a dtype")
+    if q.device.type == "cpu":
+        from .reference import joint_attention_reference
+        on = _gate_on(gate, "attention_joint")
+        joint = joint_attention_reference(q, k, v, k2, v2, num_heads, scale, lead)
+        return joint if on is None else torch.where(on, joint, joint_attention_reference(q, k, v, k2, v2, num_heads, scale, 0))
+    _C.require_device(q, k, v, k2, v2)
+    if gate is not None:
+        _C.require_device(*gate)
+        _residual_table("attention_joint", gate[1], gate[0])
+    applies = q.dtype in (torch.bfloat16, torch.float16) and D == 64 and S1 >= JOINT_MIN_S1
+    if fused and not applies:
+        raise BackendError(f"attention_joint: the kernel takes bf16 / fp16 at head size 64 with S1 >= {JOINT_MIN_S1}; got {q.dtype}, head size {D}, "
+                           f"S1 = {S1}")
+    if fused is False or not applies:
+        plain = attention(q, k, v, num_heads, scale)
+        if lead == 0:
+            return plain
+        rows = torch.arange(lead, device=q.device) % B2
+        joint = attention(q[:lead], torch.cat([k[:lead], k2.index_select(0, rows)], dim=1), torch.cat([v[:lead], v2.index_select(0, rows)], dim=1),
+                          num_heads, scale)
+        on = _gate_on(gate, "attention_joint")
+        if on is not None:
+            joint = torch.where(on, joint, plain[:lead])
+        return joint if lead == B else torch.cat([joint, plain[lead:]], dim=0)
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    def seg(t):      # unit stride along the channels; token and batch strides as they are
+        return t if t.stride(2) == 1 and t.stride(1) >= Cc and t.stride(0) >= 0 else t.contiguous()
+
+    q_, ldq = tok(q)
+    k_, ldk = tok(k)
+    v_, ldv = tok(v)
+    k2_, v2_ = seg(k2), seg(v2)
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    step, table = gate if gate is not None else (None, None)
+    _C.check(_C.load().st_attention_joint(q_.data_ptr(), k_.data_ptr(), v_.data_ptr(), k2_.data_ptr(), v2_.data_ptr(), out.data_ptr(), B, T, S1, S2, B2,
+                                          lead, num_heads, D, ldq, ldk, ldv, k2_.stride(1), v2_.stride(1), k2_.stride(0) if B2 > 1 else 0,
+                                          v2_.stride(0) if B2 > 1 else 0, Cc, float(scale), _ptr(table), _ptr(step),
+                                          0 if table is None else table.numel(), _C.dtype_code(q.dtype), _C.stream_ptr()), "attention_joint")
+    return out
+
+
 # ----------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int, *,
            upsample2x: bool = False, rowbias: Optional[torch.Tensor] = None,

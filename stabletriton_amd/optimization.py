@@ -21,14 +21,15 @@ from . import t2i_adapter as _t2i
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_reference, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
 
 def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
-                    ip_adapter=None, seg_layers=None, t2i_adapter: bool = False, controlnet: bool = False) -> fx.GraphModule:
+                    ip_adapter=None, seg_layers=None, t2i_adapter: bool = False, controlnet: bool = False,
+                    reference_layers=None) -> fx.GraphModule:
     """Pass pipeline over a traced module; an untraced nn.Module is traced here, after the flags were checked against each other
     (optimize_model relies on it: a bad combination raises before the trace).  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
@@ -50,8 +51,12 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     state, `gm.t2i_adapter`, starts at scale 0 = the bits of the module without sites; not with `fp8`.  `controlnet=True` (addition,
     off by default, likewise): one leaf behind the middle block that adds a ControlNet's residuals to the skip tensors and the middle
     block's output, for the decoder's readers only (optimizers/insert_controlnet.py, controlnet.py); the state, `gm.controlnet`,
-    starts at scale 0 = the bits of the module without sites; not with `t2i_adapter` or `fp8`."""
-    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet)
+    starts at scale 0 = the bits of the module without sites; not with `t2i_adapter` or `fp8`.  `reference_layers` (addition, off by
+    default, likewise): regular expressions selecting the self-attention sites whose leading batch entries also attend to the keys
+    of the call's last B // chunks entries, the reference rows (reference-only control; optimizers/insert_reference.py,
+    reference.py); the state, `gm.reference`, starts with chunks 0 = ordinary attention; not with `pag_layers` or `seg_layers` (a
+    site carries one leaf)."""
+    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet, reference_layers)
     if not isinstance(gm, fx.GraphModule):
         gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
@@ -69,6 +74,8 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
         stats["pag_sites"] = insert_pag(gm, pag_layers)
     if seg_layers is not None:      # likewise (never both: check_feature_combination)
         stats["seg_sites"] = insert_seg(gm, seg_layers)
+    if reference_layers is not None:      # likewise (never with either: check_feature_combination)
+        stats["reference_sites"] = insert_reference(gm, reference_layers)
     if regions is not None:         # likewise
         stats["region_sites"] = insert_regions(gm, regions, region_tokens)
     if ip_adapter is not None:      # likewise
@@ -101,8 +108,10 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     return gm
 
 
-def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet=False) -> None:
+def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet=False, reference_layers=None) -> None:
     """The compile flags that exclude each other."""
+    if reference_layers is not None and (pag_layers is not None or seg_layers is not None):
+        raise ValueError("reference_layers cannot be combined with pag_layers or seg_layers: a self-attention site carries one leaf")
     if seg_layers is not None and pag_layers is not None:
         raise ValueError("seg_layers cannot be combined with pag_layers: smoothed energy guidance and perturbed-attention guidance both "
                          "claim the perturbed row block of a call, and a self-attention site carries one leaf")
@@ -119,8 +128,13 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
                    pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None,
-                   t2i_adapter: bool = False, controlnet: bool = False) -> fx.GraphModule:
-    """`controlnet=True` (addition): ControlNet structural control (controlnet.py).  One launch behind the middle block adds the
+                   t2i_adapter: bool = False, controlnet: bool = False, reference_layers=None) -> fx.GraphModule:
+    """`reference_layers=(".*",)` (addition): reference-only control (reference.py).  The selected self-attention sites can treat the
+    last B // chunks batch entries of a call as reference rows: every other entry attends to its own tokens and to its reference
+    row's tokens under one softmax (one launch, csrc/attention_joint.hip).  `gm.reference.using(chunks, step=..., table=...)` around the
+    caller's own calls, `step` / `table` an optional device gate read at every launch; chunks 0, the initial state, is ordinary
+    attention.  Not with `pag_layers` or `seg_layers`.
+    `controlnet=True` (addition): ControlNet structural control (controlnet.py).  One launch behind the middle block adds the
     residuals of a ControlNet branch to the UNet's skip tensors and to the middle block's output, in place, for the decoder's readers
     only, and rewrites the producers' GroupNorm partials.  `gm.controlnet` - `bind(rows, latent_hw, device)` once, then
     `set(residuals, scale)`, `set_scale(scale)`, `set_site_weights(weights)`, `clear()` in place, no new capture;
@@ -174,7 +188,7 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
         raise RuntimeError("fp8 projections need a bfloat16 model")
     gm = replace_backend(model, fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
                          region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
-                         controlnet=controlnet)
+                         controlnet=controlnet, reference_layers=reference_layers)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()
@@ -216,6 +230,27 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
             return graphed(*args, _chunks=state.chunks, _latent=latent, **kwargs)
 
         gm.forward = perturbed_forward
+    elif cuda_graph and reference_layers is not None:
+        # likewise: the reference range is host state of the captured launches; the gate is the state's own pair (the caller's
+        # `using(chunks, step=, table=)` tensors would be captured by address: pass none with cuda_graph=True)
+        ref_state, ref_inner = gm.reference, gm.forward
+
+        def run_reference(*args, _chunks: int = 0, **kwargs):
+            with ref_state.using(_chunks):
+                return ref_inner(*args, **kwargs)
+
+        ref_graphed = make_dynamic_graphed_callable(run_reference, before_replay=gm.exec_context.refresh_derived)
+
+        def reference_forward(*args, **kwargs):
+            if ref_state.gate is not None:
+                raise ValueError("reference: a module compiled with cuda_graph=True runs under the state's own gate; compile with "
+                                 "cuda_graph=False to pass step= / table= to using()")
+            if ref_state.chunks:      # allocated outside the capture the cache may start
+                sample = args[0] if args else kwargs["sample"]
+                ref_state.own_gate(sample.device)
+            return ref_graphed(*args, _chunks=ref_state.chunks, **kwargs)
+
+        gm.forward = reference_forward
     elif cuda_graph:
         gm.forward = make_dynamic_graphed_callable(gm.forward, before_replay=gm.exec_context.refresh_derived)
     return gm

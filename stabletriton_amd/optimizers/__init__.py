@@ -17,6 +17,7 @@ from .insert_t2i_adapter import insert_t2i_adapter
 from .insert_controlnet import insert_controlnet
 from .insert_pag import insert_pag
 from .insert_seg import insert_seg
+from .insert_reference import insert_reference
 from .insert_regions import insert_regions
 from .insert_ip_adapter import insert_ip_adapter
 from .cleanup import dedupe_pure_calls, fuse_token_residual

@@ -101,6 +101,18 @@ table are device buffers read by address: `set_inpaint` is an in-place write, be
 mode share the captured launch (a NaN threshold entry = no threshold).  Mask all ones - the state until `set_inpaint`, and after
 `set_inpaint(None)` - writes nothing: the bits of a loop built without the flag, at one early-exit launch per step.  `inpaint=False` is
 the present loop exactly: no buffers, no launch.  Not built: nine-channel inpainting checkpoints, mask resampling.
+
+Reference-only control (`reference=True`, `set_reference`; reference.py) on a UNet compiled with `reference_layers`: the UNet evaluates
+one more block of batch rows, [negative | positive | reference] or [positive | reference], the noised reference latent under the
+positive conditioning, and in the selected self-attention sites every other row attends to its own tokens and to its reference
+row's tokens under one softmax (one launch per site, csrc/attention_joint.hip).  The sampler update sees the leading row blocks of
+the prediction and of the next input as views and is unchanged; behind it (and behind the inpaint blend) one launch of the existing
+`st_inpaint_blend` with an all-zero mask writes the reference block's next input, (init + sigma[i + 1] * noise) * in_scale[i + 1].
+The sites read a per-step device table (1 inside [start * n, end * n), 0 = ordinary attention, the reference rows' keys are never
+read) at the step counter: `set_reference` / `set_reference(None)` are in-place writes, before or after `capture()`.  The captured graph
+is static, so a loop gated off still evaluates the reference rows.  Not with `pag_scale`, `seg_scale`, `tile_hw`, or UNets compiled with
+`regions`, `ip_adapter`, `t2i_adapter`, `controlnet`.  Parity with A1111, ComfyUI and diffusers is unpinned; `style_fidelity`, a continuous
+strength and the AdaIN variant are out of scope.
 """
 from __future__ import annotations
 
@@ -116,6 +128,9 @@ from .scheduler import DPMSolverTables, EulerTables, SDETables, euler_discrete_t
 from .state import compiled_state
 
 
+REFERENCE_COUNTER_WORD = (1 << 32) - 1      # rng.py's counter word of set_reference(seed=): behind every start (0) and step (i + 1) word
+
+
 class DenoiseLoop:
     def __init__(self, unet: Callable, batch: int, latent_hw, dtype: torch.dtype, device,
                  tables: Optional[Union[EulerTables, DPMSolverTables, SDETables]] = None, cross_dim: int = 2048, pooled_dim: int = 1280,
@@ -125,7 +140,7 @@ class DenoiseLoop:
                  pag_scale: Optional[Union[float, Sequence[float]]] = None,
                  seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf"),
                  tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform", controlnet: Optional[Callable] = None,
-                 inpaint: bool = False):
+                 inpaint: bool = False, reference: bool = False):
         assert mode in ("loop", "step", "eager")
         if seg_scale is not None and pag_scale is not None:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
@@ -146,6 +161,19 @@ class DenoiseLoop:
             seg.check_sigma(seg_sigma)
             pag_scale = seg_scale
         self._perturbed_chunks = 0 if pag_scale is None else (3 if guidance_scale is not None else 2)
+        # reference-only control: the UNet's sites must exist, and the reference rows are one more row block behind the others
+        self._reference = None
+        if reference:
+            from . import reference as _reference
+            self._reference = _reference.state_of(unet, "DenoiseLoop(reference=True)")
+            if pag_scale is not None or tile_hw is not None:
+                raise ValueError("DenoiseLoop: reference=True cannot be combined with pag_scale, seg_scale or tile_hw")
+            for name, cls in (("regions", _regions.Regions), ("ip_adapter", _ip.IPAdapter), ("t2i_adapter", _t2i.T2IAdapterState),
+                              ("controlnet", _cn.ControlNetState)):
+                if compiled_state(unet, name, cls) is not None:
+                    raise ValueError(f"DenoiseLoop: reference=True cannot be combined with a UNet compiled with {name}: its row-bound "
+                                     "state is not verified with a reference row block")
+        self._reference_chunks = 0 if not reference else (3 if guidance_scale is not None else 2)
         # regional prompts: the sites are part of the compiled UNet, the text context carries its R prompts side by side
         self._regions_state = compiled_state(unet, "regions", _regions.Regions)
         if self._regions_state is not None and tokens != self._regions_state.R * self._regions_state.seg_len:
@@ -179,7 +207,8 @@ class DenoiseLoop:
             raise ValueError("DenoiseLoop: tile_stride, tile_wrap_w and tile_weights need tile_hw")
         self._T = T
         # guidance: the UNet sees [negative | positive]; with pag_scale one more block, [.. | perturbed]
-        canvas_rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0))
+        canvas_rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0) + (1 if reference else 0))
+        self._lead_rows = canvas_rows - (batch if reference else 0)      # the row blocks the sampler update reads and writes
         rows = canvas_rows * T
         if self._regions_state is not None:                # the weight buffers of this row count: allocated once, "off"
             self._regions_state.bind(rows, (lh, lw), dev)
@@ -258,6 +287,18 @@ class DenoiseLoop:
             self.inpaint_mask = torch.ones((batch, lh, lw), dtype=torch.float32, device=dev)
             self.inpaint_thr = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
             self.sigma_next = torch.tensor(self.tables.sigmas[1:], dtype=torch.float32, device=dev)
+        # reference-only control: the reference latent and its unit noise, the scratch latent and the all-zero mask ("keep every
+        # pixel") of the launch that re-noises the block for the next step, and the sites' per-step gate (all 0 = off); read by
+        # address, allocated once, outside capture
+        self.reference_init = self.reference_noise = self._reference_latent = self._reference_mask = self.reference_table = None
+        if reference:
+            self.reference_init = torch.zeros_like(self.latent)
+            self.reference_noise = torch.zeros_like(self.latent)
+            self._reference_latent = torch.zeros_like(self.latent)
+            self._reference_mask = torch.zeros((1, lh, lw), dtype=torch.float32, device=dev)
+            self.reference_table = torch.zeros(n, dtype=torch.float32, device=dev)
+            if self.sigma_next is None:
+                self.sigma_next = torch.tensor(self.tables.sigmas[1:], dtype=torch.float32, device=dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -337,14 +378,14 @@ class DenoiseLoop:
                 raise ValueError("set_conditioning: negative conditioning needs a loop built with guidance_scale")
             for buf, pos in ((self.ehs, encoder_hidden_states), (self.text_embeds, text_embeds), (self.time_ids, time_ids)):
                 buf[:b].copy_(pos)
-                if self.pag is not None:                   # the perturbed rows carry the positive conditioning
+                if self.pag is not None or self._reference is not None:      # the perturbed / reference rows carry the positive conditioning
                     buf[b:].copy_(pos)
         else:
             for buf, pos, neg in ((self.ehs, encoder_hidden_states, negative_encoder_hidden_states),
                                   (self.text_embeds, text_embeds, negative_text_embeds),
                                   (self.time_ids, time_ids, time_ids if negative_time_ids is None else negative_time_ids)):
                 buf[b:2 * b].copy_(pos)
-                if self.pag is not None:                   # the perturbed rows carry the positive conditioning
+                if self.pag is not None or self._reference is not None:      # the perturbed / reference rows carry the positive conditioning
                     buf[2 * b:].copy_(pos)
                 if neg is None:
                     buf[:b].zero_()
@@ -415,6 +456,48 @@ class DenoiseLoop:
         self.inpaint_init.copy_(init.detach().to(self.device, torch.float32).expand_as(self.inpaint_init))
         self.inpaint_mask.copy_(m.expand_as(self.inpaint_mask))
         self.inpaint_thr.copy_(thr)
+
+    def set_reference(self, latent: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
+                      start: float = 0.0, end: float = 1.0) -> None:
+        """Reference-only control: `latent` (1 | B, 4, lh, lw) is the reference image's latent; at step i the reference rows see
+        (latent + sigma[i] * noise) * in_scale[i].  `noise`: unit noise of the same shape, or `seed`: an int (or B ints) in [0, 2^64)
+        for rng.py's stream at counter word REFERENCE_COUNTER_WORD = 2^32 - 1 (the start noise is word 0 and step i's noise word i + 1,
+        i < n_steps: no collision); the seeds are the call's own and leave `set_seed`'s table alone.  The sites are on for the steps
+        in [int(start * n), int(end * n)).  `set_reference(None)` switches them off: the table is zeroed, the reference rows' keys are
+        no longer read, and the result does not depend on the reference.
+        In-place writes of device buffers the captured graph reads by address, legal before or after `capture()`, never a new capture.
+        Call it before `set_noise` / `set_image` (they write the reference block's first input), or again after them: the call itself
+        writes that input for the step the counter stands at, which it reads with `step.item()` - one host synchronisation."""
+        if self._reference is None:
+            raise ValueError("set_reference: this loop was built without reference=True")
+        if latent is None:
+            if noise is not None or seed is not None:
+                raise ValueError("set_reference: takes (latent, noise | seed[, start, end]) or None")
+            self.reference_table.zero_()
+            return
+        n = self.n_steps
+        if not (0.0 <= float(start) <= float(end) <= 1.0):
+            raise ValueError(f"set_reference: 0 <= start <= end <= 1 expected, got start={start}, end={end}")
+        lat = torch.as_tensor(latent)
+        if lat.dim() != 4 or lat.shape[0] not in (1, self.batch) or tuple(lat.shape[1:]) != tuple(self.latent.shape[1:]):
+            raise ValueError(f"set_reference: latent must be (1 | {self.batch}, {', '.join(str(v) for v in self.latent.shape[1:])}), got "
+                             f"{tuple(lat.shape)}")
+        if (noise is None) == (seed is None):
+            raise ValueError("set_reference: pass noise or seed (one of them)")
+        if noise is not None:
+            z = torch.as_tensor(noise)
+            if z.dim() != 4 or z.shape[0] not in (1, self.batch) or tuple(z.shape[1:]) != tuple(self.latent.shape[1:]):
+                raise ValueError(f"set_reference: noise must have the latent's shape, got {tuple(z.shape)}")
+            z = z.detach().to(self.device, torch.float32).expand_as(self.reference_noise)
+        else:
+            z = torch.empty_like(self.latent)
+            ops.philox_normal(z, self._seed_bits(seed, "set_reference").to(self.device), REFERENCE_COUNTER_WORD)
+        table = torch.zeros(n, dtype=torch.float32)
+        table[int(float(start) * n):int(float(end) * n)] = 1.0
+        self.reference_init.copy_(lat.detach().to(self.device, torch.float32).expand_as(self.reference_init))
+        self.reference_noise.copy_(z)
+        self.reference_table.copy_(table)
+        self._write_reference_input(int(self.step.item()) % n)
 
     def _rederive_conditioning(self) -> None:
         """Everything the loop computes once per prompt from the weights and its own static `ehs`, `text_embeds` and
@@ -633,6 +716,13 @@ class DenoiseLoop:
     def set_seed(self, seed: Union[int, Sequence[int]]) -> None:
         """The generator's seeds (rng.py): B ints in [0, 2^64), one per latent sample, or one int s for seeds s, s + 1, ...,
         s + B - 1 (mod 2^64).  Written into the device table in place: a captured graph reads it by address."""
+        bits = self._seed_bits(seed, "set_seed")
+        if self.seeds is None:                             # Euler / DPM++: only the initial noise reads the seeds
+            self.seeds = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
+        self.seeds.copy_(bits)
+
+    def _seed_bits(self, seed: Union[int, Sequence[int]], who: str) -> torch.Tensor:
+        """`seed` as set_seed takes it -> a host int64 tensor of B entries holding the seeds' 64 bits."""
         def integer(v) -> bool:
             return isinstance(v, numbers.Integral) and not isinstance(v, bool)
 
@@ -643,18 +733,15 @@ class DenoiseLoop:
             try:
                 vals = list(seed)
             except TypeError:
-                raise ValueError(f"set_seed: takes one int or B = {self.batch} ints, got {seed!r}") from None
+                raise ValueError(f"{who}: takes one int or B = {self.batch} ints, got {seed!r}") from None
             if not all(integer(v) for v in vals):
-                raise ValueError(f"set_seed: seeds are integers, got {vals!r}")
+                raise ValueError(f"{who}: seeds are integers, got {vals!r}")
             vals = [int(v) for v in vals]
         if len(vals) != self.batch:
-            raise ValueError(f"set_seed: takes one int or B = {self.batch} ints, got {len(vals)}")
+            raise ValueError(f"{who}: takes one int or B = {self.batch} ints, got {len(vals)}")
         if any(v < 0 or v >= 1 << 64 for v in vals):
-            raise ValueError("set_seed: seeds are 64-bit unsigned integers, in [0, 2^64)")
-        bits = torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
-        if self.seeds is None:                             # Euler / DPM++: only the initial noise reads the seeds
-            self.seeds = torch.zeros(self.batch, dtype=torch.int64, device=self.device)
-        self.seeds.copy_(bits)
+            raise ValueError(f"{who}: seeds are 64-bit unsigned integers, in [0, 2^64)")
+        return torch.tensor([v - (1 << 64) if v >= 1 << 63 else v for v in vals], dtype=torch.int64)
 
     def _seeded_unit(self, counter: int) -> torch.Tensor:
         z = torch.empty_like(self.latent)
@@ -674,6 +761,7 @@ class DenoiseLoop:
             self.inpaint_noise.copy_(latent_unit)
         self.latent.copy_(latent_unit.to(self.device, torch.float32) * self.tables.init_noise_sigma)
         self._write_input(float(self.tables.in_scale()[0]))
+        self._write_reference_input(0)
         self.step.zero_()
         if self.start is not None:
             self.start.zero_()
@@ -703,6 +791,7 @@ class DenoiseLoop:
         lat = init_latent.to(self.device, torch.float32) + noise_unit.to(self.device, torch.float32) * sigma
         self.latent.copy_(lat)
         self._write_input(float(self.tables.in_scale()[t_start]))
+        self._write_reference_input(t_start)
         self.step.fill_(t_start)
         if self.start is not None:
             self.start.fill_(t_start)
@@ -710,13 +799,19 @@ class DenoiseLoop:
         return n - t_start
 
     def _write_input(self, scale: float) -> None:
-        if self.guidance is None and self.pag is None:
+        if self.guidance is None and self.pag is None and self._reference is None:
             self.x_step.copy_(self.latent * scale)
         else:
             v = self.latent * scale
-            for r in range(self.x_step.shape[0] // self.batch):      # every row block sees the same latent
+            for r in range(self._lead_rows // self.batch):      # every row block sees the same latent
                 self.x_step[r * self.batch:(r + 1) * self.batch].copy_(v)
         self._gather_windows()
+
+    def _write_reference_input(self, i: int) -> None:
+        """The reference block's input of schedule entry i, the trajectory's start: (init + sigma[i] * noise) * in_scale[i]."""
+        if self._reference is not None:
+            v = (self.reference_init + self.reference_noise * float(self.tables.sigmas[i])) * float(self.tables.in_scale()[i])
+            self.x_step[self._lead_rows:].copy_(v)
 
     def _gather_windows(self) -> None:
         if self.tile_grid is not None:                     # the UNet's input: the windows of the canvas the update wrote
@@ -744,6 +839,9 @@ class DenoiseLoop:
                     down, mid = self.controlnet(self.x_in, t, self.ehs, self._cond(), cond_embed=self.controlnet_cond)
                     lent = (list(down) + [mid],)
                 scopes.enter_context(self._sites.using(self.step_ids[0:1] if step is None else step, self._sites_table, *lent))
+            if self._reference is not None:      # the last B rows are the reference block; the sites read this loop's gate at `step`
+                scopes.enter_context(self._reference.using(self._reference_chunks, step=self.step_ids[0:1] if step is None else step,
+                                                           table=self.reference_table))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
                 scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
             return self._unet_call(t, time_row)
@@ -775,33 +873,43 @@ class DenoiseLoop:
             g = self.tile_grid
             ops.tile_blend(eps, self.eps_canvas, self.tile_weights, g.ys, g.xs, g.wrap_w)
             eps = self.eps_canvas
+        if self._reference is not None:                    # the sampler sees the leading row blocks (views): its kernels are unchanged
+            eps = eps[:self._lead_rows]
         self._sampler_update(eps, step)
         if self.inpaint_mask is not None:                  # behind the update, on what it wrote: pixels to repaint are not touched
-            ops.inpaint_blend(self.latent, self.x_step, self.inpaint_init, self.inpaint_noise, self.inpaint_mask, self.sigma_next,
+            ops.inpaint_blend(self.latent, self._x_lead, self.inpaint_init, self.inpaint_noise, self.inpaint_mask, self.sigma_next,
                               self.in_scale, step, self.inpaint_thr)
+        if self._reference is not None:                    # the reference block's next input: every pixel "kept" = init + sigma[i + 1] * noise
+            ops.inpaint_blend(self._reference_latent, self.x_step[self._lead_rows:], self.reference_init, self.reference_noise,
+                              self._reference_mask, self.sigma_next, self.in_scale, step, None)
         self._gather_windows()
+
+    @property
+    def _x_lead(self) -> torch.Tensor:
+        """What the update kernels write: `x_step`, without the reference block when there is one."""
+        return self.x_step if self._reference is None else self.x_step[:self._lead_rows]
 
     def _sampler_update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
         if self.pag is not None:
             if isinstance(self.tables, SDETables):
-                ops.pag_sde_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+                ops.pag_sde_step(self.latent, eps, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
                                  self.pag, self.guidance, self.rescale, self.cfg_workspace)
             elif self.coef is not None:
-                ops.pag_dpmpp2m_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.pag,
+                ops.pag_dpmpp2m_step(self.latent, eps, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.pag,
                                      self.guidance, self.rescale, self.cfg_workspace)
             else:
-                ops.pag_euler_step(self.latent, eps, self.x_step, self.dsigma, self.in_scale, self.guidance, self.pag, step, self.rescale,
+                ops.pag_euler_step(self.latent, eps, self._x_lead, self.dsigma, self.in_scale, self.guidance, self.pag, step, self.rescale,
                                    self.cfg_workspace)
         elif isinstance(self.tables, SDETables):
-            ops.sde_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+            ops.sde_step(self.latent, eps, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
                          self.guidance, self.rescale, self.cfg_workspace)
         elif self.coef is not None:
-            ops.dpmpp2m_step(self.latent, eps, self.x_step, self.history, self.coef, self.in_scale, step, self.start, self.guidance,
+            ops.dpmpp2m_step(self.latent, eps, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.guidance,
                              self.rescale, self.cfg_workspace)
         elif self.guidance is None:
-            ops.euler_step(self.latent, eps, self.x_step, self.dsigma, self.in_scale, step)
+            ops.euler_step(self.latent, eps, self._x_lead, self.dsigma, self.in_scale, step)
         else:
-            ops.cfg_euler_step(self.latent, eps, self.x_step, self.dsigma, self.in_scale, self.guidance, step, self.rescale,
+            ops.cfg_euler_step(self.latent, eps, self._x_lead, self.dsigma, self.in_scale, self.guidance, step, self.rescale,
                                self.cfg_workspace)
 
     # ---- capture / run -------------------------------------------------------------------
