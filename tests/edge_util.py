@@ -744,7 +744,8 @@ def assert_spotlight_condition(ref: AttentionRef, pairs, S, H):
     return min(best[c] for c in need)
 
 
-# ---- which kernel a shape takes (attention.hip: attention16_launch, st_attention; attention_f32.hip; attention_anyd.hip) ----------
+# ---- which kernel a shape takes (attention.hip: attention16_launch, st_attention; attention_core.h: att32_form, the one place
+#      that holds the 32-row rule; attention_f32.hip; attention_anyd.hip) -------------------------------------------------------------
 def _cdiv(a, b):
     return -(-a // b)
 
