@@ -643,6 +643,26 @@ int st_inpaint_blend(float* latent, void* next_in, const float* init, const floa
                      const float* thr, const float* sigma_next, const float* in_scale, const int* step,
                      int batch, int blocks, long HW, int C, int mask_rows, int n_steps, int dtype, void* stream);
 
+/* ---- Stem convolution of nine-channel (inpainting) UNets (no reference counterpart: conv_in of the SDXL inpainting checkpoints, whose
+ * input per step is [scaled latent (4) | mask (1) | masked-image latent (4)]).  Added after ABI 18 without a bump: a new entry point, no
+ * existing signature or contract changed.
+ *
+ * st_conv_stem: y[n, oy, ox, co] = bias[co] + sum over r, s in 0..2 and c < C0 + C1 of w[co, r, s, c] * in[n, oy + r - 1, ox + s - 1, c],
+ * a 3x3 convolution, stride 1, zero padding 1; out is dense NHWC (N, H, W, Cout) of `dtype` (ST_BF16, ST_F16, ST_F32).  in[.., c] is
+ * source a for c < C0, else source b at channel c - C0.  A source is a pointer, its pixel stride and image stride in ELEMENTS (rows are
+ * dense: W pixel strides) and its image count: image n reads a[n % Na] and b[n % Nb] (the row blocks [negative | positive | perturbed]
+ * of a guided call share one conditioning image per sample).  C1 == 0: one source, b is not read.  1 <= C0, 0 <= C1, C0 + C1 <= 16,
+ * Cout a multiple of 16.  w is (Cout, 3, 3, C0 + C1) dense - torch's channels-last conv weight - and is read when the kernel runs:
+ * nothing derived from it is cached, an in-place update is seen by the next launch.  epi: 0 or ST_EPI_BIAS (bias: Cout values of `dtype`).
+ * Products on the matrix pipe (16-bit types: v_mfma_f32_16x16x32; fp32: v_mfma_f32_16x16x4_f32, exact fp32 products), fp32 accumulation
+ * in a fixed order, bias added in fp32, one rounding; every element is written by one lane: two launches give the same bits, and the
+ * same values given as one or as two sources give the same bits.  No GroupNorm partials are produced.  Rejected before any launch: null
+ * pointers (bias without ST_EPI_BIAS excepted; b when C1 == 0), an unsupported dtype, non-positive sizes, C0 + C1 > 16, Cout % 16 != 0,
+ * image counts that do not divide N, pixel strides below the channel count, an output not 16-byte aligned, an output overlapping either
+ * source, epilogue flags other than ST_EPI_BIAS, sizes past the index range.  64-bit index arithmetic throughout (csrc/conv_stem.hip). */
+int st_conv_stem(const void* a, long a_px, long a_img, int Na, int C0, const void* b, long b_px, long b_img, int Nb, int C1,
+                 const void* w, const void* bias, void* out, int N, int H, int W, int Cout, int epi, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,7 @@ SIGNATURES = {
     "st_tile_gather": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
     "st_tile_blend": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
     "st_inpaint_blend": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _i, _i, _p]),
+    "st_conv_stem": (_i, [_p, _l, _l, _i, _i, _p, _l, _l, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 

@@ -23,6 +23,9 @@ ARCH = "gfx950"
 # softmax / epilogue VALU code reads them without v_accvgpr_read/write copies.
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-gpu-rdc", "-Wno-unused-result",
          "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# per source, on top of FLAGS.  conv_stem.hip: the compiler forms no packed fp32 VALU instructions (v_pk_add / mul / fma_f32) from
+# its epilogue's bias adds.
+SOURCE_FLAGS = {"conv_stem.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def lib_path() -> str:
@@ -46,7 +49,7 @@ def _digest(path: str) -> str:
     for dep in [path] + headers + [os.path.join(PKG, "..", "include", "stabletriton_amd.h")]:
         with open(dep, "rb") as f:
             h.update(f.read())
-    h.update(" ".join(FLAGS).encode())
+    h.update(" ".join(FLAGS + SOURCE_FLAGS.get(os.path.basename(path), [])).encode())
     return h.hexdigest()
 
 
@@ -68,7 +71,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
         sp, obj, stamp, dg, fresh = job
         if fresh:
             return obj
-        cmd = [hipcc, *FLAGS, "-c", sp, "-o", obj]
+        cmd = [hipcc, *FLAGS, *SOURCE_FLAGS.get(os.path.basename(sp), []), "-c", sp, "-o", obj]
         if verbose:
             print(" ".join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

@@ -24,6 +24,11 @@ stochastic samplers' noise are what they are without a mask.  The DPM-Solver++ h
 latent) is left alone, as diffusers leaves its `model_outputs`.  Parity with either published pipeline is unpinned - no reference
 output has been compared.
 
+Nine-channel inpainting checkpoints (stable-diffusion-xl-1.0-inpainting-0.1 and its fine-tunes) are a second, independent piece:
+their UNet's conv_in reads [scaled latent (4) | mask (1) | masked-image latent (4)].  `InpaintCond` below is the state of the five
+constant channels; the stem kernel (ops.conv_stem, csrc/conv_stem.hip) reads them where they lie, next to the loop's 4-channel input.
+ComfyUI and A1111 run the post-step blend on these checkpoints too, diffusers does not: the two compose and neither needs the other.
+
 `DenoiseLoop(inpaint=True)` / `set_inpaint` (pipeline.py) run the blend inside the captured loop; `blend` is here for callers with
 their own loop (a UI's inpainting around the hooked UNet).  Device tensors go to the HIP kernel (ops.inpaint_blend,
 csrc/inpaint.hip); CPU tensors take a torch restatement of the same arithmetic (fp32 fused multiply-adds, one rounding to the input's
@@ -34,6 +39,9 @@ from __future__ import annotations
 from typing import Optional
 
 import torch
+from torch import nn
+
+from .state import RowBound
 
 
 def prepare_mask(mask, batch: int, latent_hw) -> torch.Tensor:
@@ -105,3 +113,73 @@ def blend(latent: torch.Tensor, x_step: torch.Tensor, init: torch.Tensor, noise:
     for r in range(x_step.shape[0] // B):
         rows = x_step[r * B:(r + 1) * B]
         rows.copy_(torch.where(keep, rows, out))
+
+
+class InpaintCond(RowBound, nn.Module):
+    """State of a compiled nine-channel UNet (`gm.inpaint_cond`, installed by optimizers/replace_conv.py when conv_in has 9 input
+    channels): per bound row count one zeroed channels_last buffer of `batch` images x 5 channels in diffusers' order - the mask
+    (1 = repaint), then the four channels of the masked image's latent - shared by every row block of a guided call (UNet row n reads
+    image n % batch).  Read by ADDRESS by the stem's launch: `write` is an in-place copy a captured graph picks up.  Neither part is
+    multiplied by the sampler's input scale (only the latent is, and the sampler kernels do that)."""
+    label = "inpaint_cond"
+    channels = 5
+
+    def __init__(self):
+        super().__init__()
+        # rows -> (batch, 5, lh, lw) channels_last; a plain dict, not registered buffers: .to(dtype) / state_dict() leave the
+        # buffers alone at their addresses (state.ResidualSites does the same)
+        self._cond = {}
+
+    def bind(self, rows: int, latent_hw, device, dtype: torch.dtype, batch: int = None) -> None:
+        """Allocate, outside any capture, the zeroed buffer of a UNet batch of `rows` rows at this latent size: `batch` images (a
+        divisor of rows; default rows).  A buffer that exists is kept, so binding twice is free."""
+        rows, lh, lw, device = self._parse_bind(rows, latent_hw, device)
+        batch = rows if batch is None else int(batch)
+        if batch < 1 or rows % batch:
+            raise ValueError(f"{self.label}.bind: batch {batch} must divide the {rows} rows")
+        buf = self._cond.get(rows)
+        if buf is None:
+            self._refuse_capture(device)
+            self._cond[rows] = torch.zeros((batch, self.channels, lh, lw), dtype=dtype, device=device).contiguous(
+                memory_format=torch.channels_last)
+        elif tuple(buf.shape) != (batch, self.channels, lh, lw) or buf.dtype != dtype or buf.device != device:
+            raise ValueError(f"{self.label}.bind: the buffer of {rows} rows is {tuple(buf.shape)} {buf.dtype} on {buf.device}; asked for "
+                             f"{(batch, self.channels, lh, lw)} {dtype} on {device}")
+
+    def bound_rows(self):
+        return sorted(self._cond)
+
+    def cond_for(self, rows: int) -> torch.Tensor:
+        """The buffer the stem of a call with `rows` rows reads."""
+        buf = self._cond.get(int(rows))
+        if buf is None:
+            raise ValueError(f"{self.label}: no condition buffer for a UNet batch of {rows} rows (bound: {self.bound_rows()}); call "
+                             f"gm.{self.label}.bind(rows, latent_hw, device, dtype) first, or pass the sample with all nine channels")
+        return buf
+
+    def write(self, mask, masked_latent: torch.Tensor, rows: Optional[int] = None) -> None:
+        """Copy the condition in place: `mask` as `prepare_mask` takes it (latent resolution, never resampled, 1 = repaint),
+        `masked_latent` (1 | batch, 4, lh, lw), finite - the VAE encoding of the image with the repainted region blanked, the
+        caller's to compute.  Everything is validated on the host before anything is written."""
+        rows = self._rows(rows, f"{self.label}.write")
+        buf = self._cond[rows]
+        batch, _, lh, lw = buf.shape
+        m = prepare_mask(mask, batch, (lh, lw))
+        if not torch.is_tensor(masked_latent) or masked_latent.dim() != 4 or masked_latent.shape[0] not in (1, batch) \
+                or tuple(masked_latent.shape[1:]) != (self.channels - 1, lh, lw):
+            got = tuple(masked_latent.shape) if torch.is_tensor(masked_latent) else type(masked_latent).__name__
+            raise ValueError(f"{self.label}.write: masked_latent must be (1 | {batch}, {self.channels - 1}, {lh}, {lw}), got {got}")
+        lat = masked_latent.detach().to("cpu", torch.float32)
+        if not bool(torch.isfinite(lat).all()):
+            raise ValueError(f"{self.label}.write: masked_latent values must be finite")
+        cond = torch.cat([m[:, None].expand(batch, 1, lh, lw), lat.expand(batch, -1, -1, -1)], dim=1)
+        buf.copy_(cond.to(buf.dtype))
+
+    def clear(self, rows: Optional[int] = None) -> None:
+        """Zero the buffer in place (a valid input, and never what a caller meant: the loop asks for a `write` before it runs)."""
+        rows = self._rows(rows, f"{self.label}.clear")
+        self._cond[rows].zero_()
+
+    def extra_repr(self) -> str:
+        return f"channels={self.channels}, bound={self.bound_rows()}"
+

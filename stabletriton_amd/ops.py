@@ -1484,6 +1484,56 @@ def conv2d_cat(x0: torch.Tensor, x1: torch.Tensor, weight: torch.Tensor, bias: O
     return out
 
 
+def _stem_source(t: torch.Tensor):
+    """(tensor, pixel stride, image stride) of one source of `conv_stem`, strides in elements: a channels_last tensor or a channel
+    slice of one passes as it is; anything else (NCHW, a one-pixel-wide image whose strides say nothing) is copied to channels_last."""
+    N, C, H, W = t.shape
+    px = t.stride(3)
+    if (C == 1 or t.stride(1) == 1) and W > 1 and px >= C and (H == 1 or t.stride(2) == W * px) and (N == 1 or t.stride(0) >= H * W * px):
+        return t, px, (t.stride(0) if N > 1 else H * W * px)
+    return t.contiguous(memory_format=torch.channels_last), C, H * W * C
+
+
+def conv_stem(a: torch.Tensor, b: Optional[torch.Tensor], weight: torch.Tensor, bias: Optional[torch.Tensor],
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """3x3 / stride 1 / padding 1 convolution of torch.cat([a, b], 1) for thin inputs (5..16 channels: the nine-channel conv_in of
+    the inpainting checkpoints) without the concatenated tensor.  a: (N | Na, C0, H, W) and b: (Nb, C1, H, W) or None, each a
+    channels_last tensor or a channel slice of one (strides are passed through, nothing is copied); Na and Nb divide N = the larger
+    of the two counts, output image n reads a[n % Na] and b[n % Nb].  weight: (Cout, C0 + C1, 3, 3), read live (no repack is cached).
+    Returns a channels_last (N, Cout, H, W): `out` when the caller brings one of that shape, layout and dtype."""
+    _C.require_device(a, b, weight, bias, out)
+    lib = _C.load()
+    if a.dim() != 4 or weight.dim() != 4 or (b is not None and b.dim() != 4):
+        raise BackendError("conv_stem expects 4-D inputs and weight")
+    if weight.dtype != a.dtype or (b is not None and b.dtype != a.dtype):
+        raise BackendError(f"conv_stem: weight dtype {weight.dtype} / second source dtype {None if b is None else b.dtype} != input dtype {a.dtype}")
+    if b is not None and (b.device != a.device or tuple(b.shape[2:]) != tuple(a.shape[2:])):
+        raise BackendError(f"conv_stem: the sources must share device and image size, got {tuple(a.shape)} and {tuple(b.shape)}")
+    Na, C0, H, W = a.shape
+    Nb, C1 = (b.shape[0], b.shape[1]) if b is not None else (1, 0)
+    N = max(Na, Nb)
+    Cout = weight.shape[0]
+    if tuple(weight.shape[1:]) != (C0 + C1, 3, 3):
+        raise BackendError(f"conv_stem: weight must be (Cout, {C0 + C1}, 3, 3) for sources of {C0} + {C1} channels, got {tuple(weight.shape)}")
+    a, a_px, a_img = _stem_source(a)
+    b_px = b_img = 0
+    if b is not None:
+        b, b_px, b_img = _stem_source(b)
+    w = weight if weight.is_contiguous(memory_format=torch.channels_last) else weight.contiguous(memory_format=torch.channels_last)
+    epi = 0
+    if bias is not None:
+        epi |= _C.EPI_BIAS
+        if bias.dtype != a.dtype:
+            bias = bias.to(a.dtype)
+    if out is None:
+        out = torch.empty((N, Cout, H, W), dtype=a.dtype, device=a.device, memory_format=torch.channels_last)
+    elif tuple(out.shape) != (N, Cout, H, W) or out.dtype != a.dtype or not out.is_contiguous(memory_format=torch.channels_last):
+        raise BackendError(f"conv_stem: out must be a channels_last ({N}, {Cout}, {H}, {W}) tensor of {a.dtype}")
+    _C.check(lib.st_conv_stem(a.data_ptr(), a_px, a_img, Na, C0, _ptr(b), b_px, b_img, Nb, C1, w.data_ptr(), _ptr(bias), out.data_ptr(),
+                              N, H, W, Cout, epi, _C.dtype_code(a.dtype), _C.stream_ptr()), "conv_stem")
+    return out
+
+
 # ----------------------------------------------------------------------------- loop pieces
 TIMESTEP_TABLE_ROWS = 4097      # integer timesteps / sizes 0 .. 4096 (SDXL: 1000 train steps; time_ids = sizes and crops in pixels)
 _timestep_tables = {}

@@ -81,6 +81,21 @@ def conv2d_wrapper(v: torch.Tensor, conv: nn.Conv2d, upsample2x: bool = False,
                       emit_colstats=emit_colstats)
 
 
+def conv_stem_wrapper(sample: torch.Tensor, conv: nn.Conv2d, state=None) -> torch.Tensor:
+    """The 3x3 stem of a UNet with 5..16 input channels (conv_in of the nine-channel inpainting checkpoints; ops.conv_stem).  A
+    sample with all `conv.in_channels` channels - what the hooks pass: diffusers and ComfyUI concatenate themselves - runs as two
+    channel-slice views of itself; a sample that lacks the `state.channels` condition channels (inpaint.InpaintCond: the denoise
+    loop's 4-channel x_in) takes them from `state.cond_for(rows)`, one image per sample shared by every row block."""
+    cin, have = conv.in_channels, sample.shape[1]
+    if have == cin:
+        split = cin - state.channels if state is not None else min(cin, 8)
+        return ops.conv_stem(sample[:, :split], sample[:, split:] if split < cin else None, conv.weight, conv.bias)
+    if state is not None and have == cin - state.channels:
+        return ops.conv_stem(sample, state.cond_for(sample.shape[0]), conv.weight, conv.bias)
+    accepted = f"{cin}" if state is None else f"{cin} (latent | mask | masked-image latent) or {cin - state.channels} (the latent; the condition is the state's)"
+    raise ops.BackendError(f"conv_stem_wrapper: the sample has {have} channels; this stem takes {accepted}")
+
+
 def group_norm_stats_wrapper(v, stats, groupnorm: nn.GroupNorm, activation: bool) -> torch.Tensor:
     """group_norm_wrapper whose statistics come from the launch(es) that produced `v` (`stats`: one ColStats, or two
     for a channel concatenation): finalize + apply, no statistics pass over v.  `v` may be the pair of tensors of a
@@ -109,7 +124,7 @@ def linear_residual_wrapper(v: torch.Tensor, linear: nn.Linear, residual: torch.
 
 for _name in ("attention_wrapper", "geglu_triton", "group_norm_wrapper", "layer_norm_wrapper", "linear_wrapper",
               "linear_wrapper_functional", "timestep_wrapper", "timestep_embedding_wrapper", "conv2d_wrapper", "linear_geglu_wrapper",
-              "linear_residual_wrapper", "group_norm_stats_wrapper", "conv2d_cat_wrapper"):
+              "linear_residual_wrapper", "group_norm_stats_wrapper", "conv2d_cat_wrapper", "conv_stem_wrapper"):
     torch.fx.wrap(_name)
 
 

@@ -100,7 +100,13 @@ is left alone, and a tiled loop blends on the canvas, ahead of `st_tile_gather`.
 table are device buffers read by address: `set_inpaint` is an in-place write, before or after `capture()`; binary / soft and threshold
 mode share the captured launch (a NaN threshold entry = no threshold).  Mask all ones - the state until `set_inpaint`, and after
 `set_inpaint(None)` - writes nothing: the bits of a loop built without the flag, at one early-exit launch per step.  `inpaint=False` is
-the present loop exactly: no buffers, no launch.  Not built: nine-channel inpainting checkpoints, mask resampling.
+the present loop exactly: no buffers, no launch.  Not built: mask resampling.
+
+Nine-channel inpainting checkpoints (`set_inpaint_condition`; inpaint.InpaintCond) need no flag: a UNet compiled from one
+carries `inpaint_cond`, and the loop binds it for its row count.  `x_in` stays the 4-channel latent; conv_in (ops.conv_stem) reads the
+mask and the masked-image latent from the state's buffer of `batch` images, shared by every row block, by address -
+`set_inpaint_condition` is an in-place write, before or after `capture()`.  Running before the first call raises.  Composes with
+`inpaint=True` (the two are independent); not with `tile_hw` or `reference=True`.
 
 Reference-only control (`reference=True`, `set_reference`; reference.py) on a UNet compiled with `reference_layers`: the UNet evaluates
 one more block of batch rows, [negative | positive | reference] or [positive | reference], the noised reference latent under the
@@ -206,6 +212,18 @@ class DenoiseLoop:
         elif tile_stride is not None or tile_wrap_w or not (isinstance(tile_weights, str) and tile_weights == "uniform"):
             raise ValueError("DenoiseLoop: tile_stride, tile_wrap_w and tile_weights need tile_hw")
         self._T = T
+        # a nine-channel inpainting checkpoint (inpaint.InpaintCond): its stem reads the mask and the masked-image latent from the
+        # state's buffer, one image per sample for every row block; x_in stays the 4-channel latent
+        from .inpaint import InpaintCond
+        self._inpaint_cond = compiled_state(unet, "inpaint_cond", InpaintCond)
+        self._inpaint_condition_set = False
+        if self._inpaint_cond is not None:
+            if tile_hw is not None:
+                raise ValueError("DenoiseLoop: tile_hw cannot be combined with a nine-channel inpainting UNet: its condition (mask and "
+                                 "masked-image latent) binds per latent size, and cropping it per window is not built")
+            if reference:
+                raise ValueError("DenoiseLoop: reference=True cannot be combined with a nine-channel inpainting UNet: a reference row "
+                                 "has no mask and no masked image")
         # guidance: the UNet sees [negative | positive]; with pag_scale one more block, [.. | perturbed]
         canvas_rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0) + (1 if reference else 0))
         self._lead_rows = canvas_rows - (batch if reference else 0)      # the row blocks the sampler update reads and writes
@@ -229,6 +247,8 @@ class DenoiseLoop:
                 self.controlnet_cond = torch.zeros((rows, self._sites.channels[0], lh, lw), dtype=dtype, device=dev).contiguous(
                     memory_format=cl)
         self.t2i_table = self._sites_table if t2i is not None else None
+        if self._inpaint_cond is not None:                 # `batch` condition images, zeroed: allocated once, outside capture
+            self._inpaint_cond.bind(rows, (lh, lw), dev, dtype, batch)
         self.controlnet_table = self._sites_table if t2i is None else None
         self._latent_hw = (th, tw)                         # what the UNet sees: the window when tiled
         if isinstance(self._perturbed, seg.SEG):           # the blur's parameter rows of this latent size: allocated once, outside capture
@@ -456,6 +476,29 @@ class DenoiseLoop:
         self.inpaint_init.copy_(init.detach().to(self.device, torch.float32).expand_as(self.inpaint_init))
         self.inpaint_mask.copy_(m.expand_as(self.inpaint_mask))
         self.inpaint_thr.copy_(thr)
+
+    def set_inpaint_condition(self, mask, masked_image_latent: Optional[torch.Tensor] = None) -> None:
+        """The condition of a nine-channel inpainting checkpoint (inpaint.InpaintCond): `mask` (lh, lw), (1 | B, lh, lw) or
+        (1 | B, 1, lh, lw) AT LATENT RESOLUTION (never resampled; 1 = repaint) and `masked_image_latent` (1 | B, 4, lh, lw), the VAE
+        encoding of the image with the region to repaint blanked - the caller's to compute.  Neither is multiplied by the sampler's
+        input scale.  An in-place write of the buffer conv_in reads by address: valid before or after `capture()`, no new capture;
+        validated on the host before anything is written.  `set_inpaint_condition(None)` zeroes the buffer.  Independent of
+        `inpaint=True` / `set_inpaint` (the post-step blend): ComfyUI and A1111 run both on these checkpoints, diffusers only this."""
+        if self._inpaint_cond is None:
+            cin = getattr(getattr(self.unet, "conv_in", None), "in_channels", None)
+            raise ValueError(f"set_inpaint_condition: this UNet's conv_in takes {4 if cin is None else cin} "
+                             "input channels - a text-to-image checkpoint, which has no mask or masked-image input; nine-channel "
+                             "inpainting checkpoints do (for this UNet: inpaint=True and set_inpaint, the post-step blend)")
+        rows = self.x_in.shape[0]
+        if mask is None:
+            if masked_image_latent is not None:
+                raise ValueError("set_inpaint_condition: takes (mask, masked_image_latent) or None")
+            self._inpaint_cond.clear(rows)
+        else:
+            if masked_image_latent is None:
+                raise ValueError("set_inpaint_condition: a masked_image_latent is needed with the mask")
+            self._inpaint_cond.write(mask, masked_image_latent, rows)
+        self._inpaint_condition_set = True
 
     def set_reference(self, latent: Optional[torch.Tensor], noise: Optional[torch.Tensor] = None, seed: Optional[int] = None,
                       start: float = 0.0, end: float = 1.0) -> None:
@@ -951,6 +994,9 @@ class DenoiseLoop:
 
     def run_steps(self, k: int) -> None:
         """Advance exactly k denoise steps from the current state (asynchronous)."""
+        if self._inpaint_cond is not None and not self._inpaint_condition_set:      # (capture() alone may precede it: a write needs no recapture)
+            raise RuntimeError("set_inpaint_condition() must be called before running the loop (a nine-channel inpainting UNet; "
+                               "set_inpaint_condition(None) asks for the zero condition explicitly)")
         if self.mode == "eager":
             s = int(self.step.item())
             for i in range(k):
