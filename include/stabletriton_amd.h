@@ -537,6 +537,33 @@ int st_attention_joint(const void* q, const void* k, const void* v, const void* 
                        long ldq, long ldk, long ldv, long ldk2, long ldv2, long bsk2, long bsv2, long ldo, float scale,
                        const float* gate_table, const int* gate_step, int gate_n, int dtype, void* stream);
 
+/* ---- windowed self-attention (no reference counterpart: HyperTile, the A1111 / ComfyUI switch): the T = gh * gw tokens of a site
+ * are a row-major gh x gw grid, a tiling (nh, nw) cuts it into nh * nw windows of th x tw tokens (th = gh / nh, tw = gw / nw) and
+ * every window attends to itself alone.  ABI 18, added without a bump: a new entry point, no existing signature or contract changed.
+ *
+ * st_attention_windows: q, k, v (B, T, H*D) as st_attention takes them for self-attention (batch strides T*ldq, T*ldk, T*ldv;
+ * column slices of a fused q|k|v buffer are taken where they lie); row i of window (wy, wx) is token
+ *   (wy*th + i / tw) * gw + wx*tw + i % tw,
+ *   out[b,t,h,:] = softmax_s( scale * q[b,t,h] . k[b,s,h] ) v[b,s,h]        s over the tokens of t's window.
+ * out has q's layout; every token is written exactly once, nothing else is.
+ * The tiling: the host pair (nh, nw) when tilings == NULL (then step must be NULL too), else row clamp(*step, 0, n - 1) of
+ * `tilings`, n pairs (nh, nw) of int32 in DEVICE memory read at every launch (one scalar load per block of values no launch
+ * writes), so a captured launch follows in-place writes of the table and of the step counter.
+ * row_forms: bit 0 / 1 / 2 set = 256 / 128 / 96 query rows per block divide th*tw of EVERY tiling the launch may read; the entry
+ * point picks one of the set forms from (T, H, B) (csrc/attention_windows.hip, att_win_rows), and the grid, T / rows blocks per
+ * (batch entry, head), is the same for every tiling.  A host pair is checked here (nh | gh, nw | gw, tw % 8 == 0, rows | th*tw);
+ * the rows of a device table cannot be: the caller guarantees the same three conditions for every pair it writes.
+ * Bit contract: the rows of a window carry the bits of st_attention (at T = S >= 256) on the gathered window; tiling (1, 1) the
+ * bits of st_attention.
+ * dtype ST_BF16 or ST_F16, D = 64; all pointers 16-byte aligned; ldq, ldk, ldv multiples of 8, ldo of 4, all >= H*D and under
+ * 2^31.  One launch, no atomics; never emits a split image.  Not built: tw not a multiple of 8 (the Python host has a slow path).
+ * Parity with either UI's node is unpinned. */
+int st_attention_windows(const void* q, const void* k, const void* v, void* out, int B, int gh, int gw, int H, int D,
+                         long ldq, long ldk, long ldv, long ldo, float scale, int nh, int nw,
+                         const int* tilings, const int* step, int n, int row_forms, int dtype, void* stream);
+/* the query rows per block (256, 128 or 96) st_attention_windows runs for (T = gh*gw, H, B) under `row_forms`; 0: none.  Host arithmetic. */
+int st_attention_windows_rows(int T, int H, int B, int row_forms);
+
 /* The three updates with a third noise prediction: st_cfg_euler_step, st_dpmpp2m_step and st_sde_step with one more device table
  * `pag` of n_steps floats (never NULL) and one more row block of eps / next_in, the prediction under perturbed self-attention.
  * With i = *step, s = pag[i]:

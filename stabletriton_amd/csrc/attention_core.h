@@ -356,7 +356,11 @@ __device__ __forceinline__ void att_xcd_decode(int T, int rows, int H, int& b, i
 //   keys.load_tile(kt, slot)     LD: the sixteen pieces of tile kt (< the tile count) to LDS byte offset slot;
 //   keys.load_piece(kt, i, p, slot, dump, live)   !LD: piece p = first + i of tile kt to slot, or, when !live (kt is past
 //                                the last tile), any 16 readable bytes to dump.
-// Tiles are asked for in order kt = 0, 1, 2, ... and every piece of a tile exactly once, keys >= S as a zero line.  THE
+// ROWS is the second rule, where a token comes from: rows(r) = the token (in units of ldq / ldo from Qb / Ob) of query / output row r
+// of this (batch entry, head).  The identity for attn32i_kernel and attnj32i_kernel; attnw32i_kernel (attention_windows.hip) maps
+// a window row to its place in the token grid.  Evaluated twice per lane, both outside the key loop.
+// Tiles are asked for in order kt = 0, 1, 2, ... and every piece of a tile exactly once, a wave's pieces in order i = 0, 1, ... N - 1
+// (a rule may keep running state that it steps at a tile's last piece: AttKeysWin does), keys >= S as a zero line.  THE
 // INVARIANT THE WAITS REST ON: load_tile issues exactly sixteen att_dma16 on every path and load_piece exactly one, and
 // neither issues any other vector-memory instruction; piece p lands at slot + att32_piece_off(p).
 static constexpr int ATT32_SLOTS = 6;                                        // ring slots of one (K, V) tile pair
@@ -364,9 +368,13 @@ static constexpr int ATT32_TILE_B = ATT_KV * 128, ATT32_BUF_B = 2 * ATT32_TILE_B
 static constexpr size_t ATT32_RING = ATT32_SLOTS * ATT32_BUF_B + 1024;       // + the dump line of the dummy DMAs
 __device__ __forceinline__ unsigned att32_piece_off(int p) { return (p >> 3) * ATT32_TILE_B + (p & 7) * 1024; }
 
-template <typename E, int NW, bool LD, typename KEYS>
+struct AttRowsId {                                     // the row rule of the two kernels whose queries are a contiguous token run
+    __device__ __forceinline__ int operator()(int r) const { return r; }
+};
+
+template <typename E, int NW, bool LD, typename KEYS, typename ROWS = AttRowsId>
 __device__ __forceinline__ void attn32i_core(const E* Qb, long ldq, int T, int xblk, E* Ob, long ldo, float scale_log2e,
-                                             char* lds, KEYS& keys) {
+                                             char* lds, KEYS& keys, const ROWS rows = ROWS()) {
     typedef typename V16<E>::x8 E8;
     typedef typename V16<E>::x4 E4;
     constexpr int TILE_B = ATT32_TILE_B, BUF_B = ATT32_BUF_B, RB = ATT32_SLOTS;
@@ -421,7 +429,7 @@ __device__ __forceinline__ void attn32i_core(const E* Qb, long ldq, int T, int x
     q_raw_t qraw[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(qraw[ks]) : "v"(Qb + (size_t)qrow * ldq + 16 * ks + 8 * h) : "memory");
+        asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(qraw[ks]) : "v"(Qb + (size_t)rows(qrow) * ldq + 16 * ks + 8 * h) : "memory");
     E8 qf[4];
     E8 ones;
 #pragma unroll
@@ -611,7 +619,7 @@ __device__ __forceinline__ void attn32i_core(const E* Qb, long ldq, int T, int x
     const float l = __shfl(o2[0], r32, 64);
     const float inv = 1.0f / l;
     if (q0 + r32 < T) {
-        E* orow = Ob + (size_t)(q0 + r32) * ldo;
+        E* orow = Ob + (size_t)rows(q0 + r32) * ldo;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             E4 a_, c_;

@@ -60,6 +60,9 @@ class _HoistedUNet(nn.Module):
         self._ip_images = {}                      # set_ip_adapter_image: slot -> (tokens, negative_tokens, chunks)
         self._ip_masks = {}                       # set_ip_adapter_masks: slot -> masks
         self._ip_applied = {}                     # ... rows -> the latent size the buffers of that row count were last written for
+        self._hypertile_steps = {}                # enable_hypertile: device -> this wrapper's int32 call counter (a device row the sites read)
+        self._hypertile_step = None               # ... the current call's
+        self._hypertile_calls = 0                 # ... calls since enable_hypertile / disable_hypertile
         self._residuals_last = None               # T2I-Adapter / ControlNet: (state, rows, the residual tensors last copied - HELD, not their addresses -, their versions)
 
     def refresh_weights(self) -> int:
@@ -120,8 +123,13 @@ class _HoistedUNet(nn.Module):
         self._perturbed_chunks = 0
 
     def _perturbed_scope(self, chunks: int, latent_hw):
-        """The PAG, SEG or reference state's `using` (a module has at most one of them) around this wrapper's own calls."""
-        from . import pag, reference, seg
+        """The PAG, SEG, reference or HyperTile state's `using` (a module has at most one of them) around this wrapper's own calls."""
+        from . import hypertile, pag, reference, seg
+        tiles = compiled_state(self.compiled, "hypertile", hypertile.HyperTile)
+        if tiles is not None:
+            if self._hypertile_step is None:
+                raise RuntimeError("hypertile: run one call outside the capture first (the wrapper's call counter is allocated there)")
+            return tiles.using(latent_hw, self._hypertile_step)
         ref = compiled_state(self.compiled, "reference", reference.ReferenceRows)
         if ref is not None:
             return ref.using(chunks)
@@ -152,6 +160,47 @@ class _HoistedUNet(nn.Module):
         state = compiled_state(self.compiled, "reference", reference.ReferenceRows)
         if state is not None and self._perturbed_chunks and not torch.cuda.is_current_stream_capturing():
             state.own_gate(sample.device)
+
+    # ---- HyperTile (hypertile.py): per-site device tables read at this wrapper's own call counter; the captured graphs stay ----------
+    HYPERTILE_DRAWS = 64
+
+    def enable_hypertile(self, tile: int = 32, swap: int = 2, seed: int = 0) -> None:
+        """The self-attention sites compiled in with `hypertile_layers` run windowed in every following call: per site, HYPERTILE_DRAWS
+        tilings are drawn as `DenoiseLoop.set_hypertile` draws its steps' (window sides among the `swap` smallest divisors of an axis
+        that are >= min(axis, tile) tokens, seeded with (seed, site)) and call i after this one reads draw i % HYPERTILE_DRAWS: a bare
+        UNet call carries no step counter, so the wrapper counts its own calls in a device row.  The tables are written in place: a
+        wrapper compiled with the sites always runs them under its counter, off = every row (1, 1) = the bits of ordinary attention,
+        and no graph is captured again - except on the slow path (fp32, head sizes other than 64; swap=1 only), whose tiling is a
+        host value: those graphs are dropped and captured again at the next call.  Raises on a wrapper compiled without
+        `hypertile_layers`."""
+        from . import hypertile
+        self._set_hypertile(hypertile.state_of(self.compiled, "enable_hypertile"), tile, swap, seed)
+
+    def disable_hypertile(self) -> None:
+        from . import hypertile
+        self._set_hypertile(hypertile.state_of(self.compiled, "disable_hypertile"), None)
+
+    def _set_hypertile(self, state, *params) -> None:
+        state.set(*params)
+        self._hypertile_calls = 0
+        if state.host_tiled:
+            self._steps.clear()
+
+    def _apply_hypertile(self, sample: torch.Tensor) -> None:
+        """This call's draw: the wrapper's counter on this call's device (allocated outside any capture; the sites only read it),
+        written before the launch.  The state's tables hold HYPERTILE_DRAWS rows unless a DenoiseLoop bound them first."""
+        from . import hypertile
+        state = compiled_state(self.compiled, "hypertile", hypertile.HyperTile)
+        if state is None or torch.cuda.is_current_stream_capturing():
+            return
+        if state.n_steps == 0:
+            state.bind(self.HYPERTILE_DRAWS)
+        key = (sample.device.type, sample.device.index)
+        if key not in self._hypertile_steps:
+            self._hypertile_steps[key] = torch.zeros(1, dtype=torch.int32, device=sample.device)
+        self._hypertile_step = self._hypertile_steps[key]
+        self._hypertile_step.fill_(self._hypertile_calls % state.n_steps)
+        self._hypertile_calls += 1
 
     # ---- smoothed energy guidance (seg.py): which rows of a call take blurred queries; sigma is a device row, written in place ----
     def enable_seg(self, chunks: int, sigma: float = float("inf")) -> None:
@@ -419,6 +468,7 @@ class _HoistedUNet(nn.Module):
         self._apply_ip_adapter(sample)
         self._apply_seg(sample)
         self._apply_reference(sample)
+        self._apply_hypertile(sample)
         self._apply_residuals(sample, self._t2i_state(), t2i, "T2I-Adapter residuals")
         self._apply_residuals(sample, self._cn_state(), controlnet, "ControlNet residuals")
         self._context_for(ehs)
@@ -506,7 +556,7 @@ class DiffusersUNet(_HoistedUNet):
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                                  region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                                 controlnet: bool = False, reference_layers=None) -> DiffusersUNet:
+                                 controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
@@ -524,7 +574,9 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     `controlnet=True` compiles the ControlNet sites in (controlnet.py; not with `t2i_adapter`): `down_block_additional_residuals` and
     `mid_block_additional_residual` of a call are then added for the decoder (None: off), the T2I-Adapter's argument raises.
     `reference_layers=(".*",)` compiles the reference-only sites in (reference.py; not with `pag_layers` / `seg_layers`):
-    `enable_reference(chunks)` / `disable_reference()` then say which rows of a call are the reference rows."""
+    `enable_reference(chunks)` / `disable_reference()` then say which rows of a call are the reference rows.
+    `hypertile_layers=(".*",)` compiles the windowed self-attention sites in (hypertile.py; not with `pag_layers` / `seg_layers` /
+    `reference_layers`): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()` drive them."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
@@ -533,19 +585,19 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
                               ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
-                              reference_layers=reference_layers)
+                              reference_layers=reference_layers, hypertile_layers=hypertile_layers)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                         regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                        controlnet: bool = False, reference_layers=None):
+                        controlnet: bool = False, reference_layers=None, hypertile_layers=None):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
                                              regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers,
-                                             t2i_adapter=t2i_adapter, controlnet=controlnet, reference_layers=reference_layers)
+                                             t2i_adapter=t2i_adapter, controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers)
     return pipe
 
 
@@ -575,7 +627,7 @@ class ComfyUNet(_HoistedUNet):
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                        region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                       controlnet: bool = False, reference_layers=None) -> ComfyUNet:
+                       controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
@@ -588,20 +640,21 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
     `controlnet=True`: with ControlNet sites (not with `t2i_adapter`): `control={"output": [...], "middle": [...]}` of a call, entry i of
     `output` being skip i in encoder order (ComfyUI pops from the end while the decoder consumes its skips last-first); a non-empty
     `"input"` raises.  `reference_layers=(".*",)`: with reference-only sites (the ReferenceOnlySimple node's batch of
-    [generated | reference] latents is `enable_reference(2)`)."""
+    [generated | reference] latents is `enable_reference(2)`).  `hypertile_layers=(".*",)`: with windowed self-attention sites (the
+    HyperTile node): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()`."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
                               region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
-                              controlnet=controlnet, reference_layers=reference_layers)
+                              controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                       regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                      controlnet: bool = False, reference_layers=None) -> ComfyUNet:
+                      controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
     adapter = compile_comfy_unet(unet, cuda_graph, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
                                  ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
-                                 reference_layers=reference_layers)
+                                 reference_layers=reference_layers, hypertile_layers=hypertile_layers)
     model_patcher.model.diffusion_model = adapter
     return adapter

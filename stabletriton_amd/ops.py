@@ -1373,6 +1373,81 @@ def attention_joint(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k2: torch
     return out
 
 
+def attention_windows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float, grid_hw, tiling=None, table=None,
+                      fused: Optional[bool] = None, rows: Optional[int] = None) -> torch.Tensor:
+    """Windowed self-attention - HyperTile (hypertile.py, csrc/attention_windows.hip): q, k, v (B, T, H*D) as `attention` takes them,
+    T = gh * gw tokens of the row-major `grid_hw` grid; `tiling` = (nh, nw) cuts it into nh * nw windows and every window attends to
+    itself alone.  `table` = (step, tilings) instead: an int32 device tensor of one entry and a contiguous int32 device tensor (n, 2),
+    read at every launch at row clamp(*step) - a captured launch follows in-place writes; EVERY row must pass
+    hypertile.check_tiling(grid_hw, row, rows), the kernel trusts it.  `rows`: the kernel's query rows per block (256, 128 or 96; None:
+    its own choice among those that divide the window of `tiling`; with a table it must be given).
+    bf16 / fp16 at head size 64 with window widths that are multiples of 8 and windows of a multiple of 96 or 128 tokens is ONE launch:
+    per window the bits of `attention` (T >= 256) on the gathered window.  Everything else (fp32 strict mode, other head sizes, other
+    window shapes) takes the slow path, at a host tiling only: gather into window-major copies, `attention`, scatter back.  fused=False
+    forces the slow path, fused=True raises where the kernel does not apply.  CPU tensors take the plain torch statement of
+    hypertile.windows_attention_reference."""
+    from . import hypertile
+    if q.dim() != 3 or q.shape != k.shape or q.shape != v.shape or len({t.dtype for t in (q, k, v)}) != 1:
+        raise BackendError("attention_windows expects q, k and v of one (B, T, H*D) shape and dtype")
+    B, T, Cc = q.shape
+    gh, gw = int(grid_hw[0]), int(grid_hw[1])
+    D = Cc // num_heads
+    if gh * gw != T:
+        raise BackendError(f"attention_windows: a {gh} x {gw} grid is not {T} tokens")
+    if (tiling is None) == (table is None):
+        raise BackendError("attention_windows: pass tiling=(nh, nw) or table=(step, tilings), one of them")
+    if tiling is not None:
+        tiling = hypertile.check_tiling((gh, gw), tuple(tiling))
+    if q.device.type == "cpu":
+        if table is not None:
+            step, rows_t = table
+            tiling = tuple(int(x) for x in rows_t[min(max(int(step.reshape(-1)[0]), 0), rows_t.shape[0] - 1)])
+        return hypertile.windows_attention_reference(q, k, v, num_heads, scale, (gh, gw), tiling)
+    _C.require_device(q, k, v)
+    applies = q.dtype in (torch.bfloat16, torch.float16) and D == 64
+    fits = 0
+    if applies and tiling is not None:
+        tw, Tw = gw // tiling[1], (gh // tiling[0]) * (gw // tiling[1])
+        fits = sum(1 << i for i, r in enumerate(hypertile.ROW_FORMS) if Tw % r == 0 and rows in (None, r)) if tw % 8 == 0 else 0
+        applies = fits != 0
+    if table is not None:
+        step, rows_t = table
+        _C.require_device(step, rows_t)
+        if not applies or fused is False:
+            raise BackendError("attention_windows: a device table needs the kernel (bf16 / fp16 at head size 64); the slow path takes a host tiling")
+        if rows not in hypertile.ROW_FORMS:
+            raise BackendError(f"attention_windows: with a table, rows must be one of {hypertile.ROW_FORMS}, got {rows!r}")
+        if (step.dtype != torch.int32 or step.numel() != 1 or rows_t.dtype != torch.int32 or rows_t.dim() != 2 or rows_t.shape[1] != 2
+                or rows_t.shape[0] < 1 or not rows_t.is_contiguous()):
+            raise BackendError("attention_windows: table = (int32 step of one entry, contiguous int32 tilings (n, 2))")
+        fits = 1 << hypertile.ROW_FORMS.index(rows)
+    if fused and not applies:
+        raise BackendError(f"attention_windows: the kernel takes bf16 / fp16 at head size 64, window widths that are multiples of 8 and windows of "
+                           f"a multiple of {rows or '96 or 128'} tokens; got {q.dtype}, head size {D}, tiling {tiling} of {gh} x {gw}")
+    if fused is False or not applies:
+        if tiling == (1, 1):
+            return attention(q, k, v, num_heads, scale)
+        g = lambda t: hypertile.windows_gather(t, (gh, gw), tiling)
+        return hypertile.windows_scatter(attention(g(q), g(k), g(v), num_heads, scale), (gh, gw), tiling)
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    q_, ldq = tok(q)
+    k_, ldk = tok(k)
+    v_, ldv = tok(v)
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    nh, nw = tiling if tiling is not None else (1, 1)
+    _C.check(_C.load().st_attention_windows(q_.data_ptr(), k_.data_ptr(), v_.data_ptr(), out.data_ptr(), B, gh, gw, num_heads, D, ldq, ldk, ldv, Cc,
+                                            float(scale), nh, nw, _ptr(rows_t) if table is not None else None,
+                                            _ptr(step) if table is not None else None, rows_t.shape[0] if table is not None else 0, fits,
+                                            _C.dtype_code(q.dtype), _C.stream_ptr()), "attention_windows")
+    return out
+
+
 # ----------------------------------------------------------------------------- conv
 def conv2d(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], stride: int, padding: int, *,
            upsample2x: bool = False, rowbias: Optional[torch.Tensor] = None,

@@ -180,6 +180,10 @@ class DenoiseLoop:
                     raise ValueError(f"DenoiseLoop: reference=True cannot be combined with a UNet compiled with {name}: its row-bound "
                                      "state is not verified with a reference row block")
         self._reference_chunks = 0 if not reference else (3 if guidance_scale is not None else 2)
+        # HyperTile: a UNet compiled with hypertile_layers runs its sites under this loop's latent size and step counter; the per-site
+        # tables start all (1, 1) = the bits of ordinary attention (set_hypertile)
+        from . import hypertile as _hypertile
+        self._hypertile = compiled_state(unet, "hypertile", _hypertile.HyperTile)
         # regional prompts: the sites are part of the compiled UNet, the text context carries its R prompts side by side
         self._regions_state = compiled_state(unet, "regions", _regions.Regions)
         if self._regions_state is not None and tokens != self._regions_state.R * self._regions_state.seg_len:
@@ -319,6 +323,8 @@ class DenoiseLoop:
             self.reference_table = torch.zeros(n, dtype=torch.float32, device=dev)
             if self.sigma_next is None:
                 self.sigma_next = torch.tensor(self.tables.sigmas[1:], dtype=torch.float32, device=dev)
+        if self._hypertile is not None:
+            self._hypertile.bind(n)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -541,6 +547,16 @@ class DenoiseLoop:
         self.reference_noise.copy_(z)
         self.reference_table.copy_(table)
         self._write_reference_input(int(self.step.item()) % n)
+
+    def set_hypertile(self, tile: Optional[int] = 32, swap: int = 2, seed: int = 0, start: float = 0.0, end: float = 1.0) -> None:
+        """HyperTile (hypertile.py) on a UNet compiled with `hypertile_layers`: per step in [int(start * n), int(end * n)) and site, a
+        window side per axis is drawn among the `swap` smallest divisors of the axis that are >= min(axis, tile) tokens, from a
+        generator seeded with (seed, site); other steps, and `set_hypertile(None)`, attend over the whole grid.  Written into the
+        sites' device tables in place, before or after `capture()`: no new capture."""
+        if self._hypertile is None:
+            raise ValueError("set_hypertile: this loop's UNet was compiled without windowed self-attention sites: compile it with "
+                             'hypertile_layers=(".*",)')
+        self._hypertile.set(tile, swap, seed, start, end)
 
     def _rederive_conditioning(self) -> None:
         """Everything the loop computes once per prompt from the weights and its own static `ehs`, `text_embeds` and
@@ -885,6 +901,8 @@ class DenoiseLoop:
             if self._reference is not None:      # the last B rows are the reference block; the sites read this loop's gate at `step`
                 scopes.enter_context(self._reference.using(self._reference_chunks, step=self.step_ids[0:1] if step is None else step,
                                                            table=self.reference_table))
+            if self._hypertile is not None:      # the sites derive their token grids from the latent size and read their tables at `step`
+                scopes.enter_context(self._hypertile.using(self._latent_hw, self.step_ids[0:1] if step is None else step))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
                 scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
             return self._unet_call(t, time_row)
