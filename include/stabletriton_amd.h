@@ -537,6 +537,35 @@ int st_attention_joint(const void* q, const void* k, const void* v, const void* 
                        long ldq, long ldk, long ldv, long ldk2, long ldv2, long bsk2, long bsv2, long ldo, float scale,
                        const float* gate_table, const int* gate_step, int gate_n, int dtype, void* stream);
 
+/* ---- StyleAligned (no reference counterpart: Hertz et al. 2023, diffusers' community pipeline_sdxl_style_aligned, ComfyUI's
+ * "StyleAligned Batch Align" node): the batch is cut into blocks of `per` entries, the first entry of a block is its style row.
+ * ABI 18, added without a bump: new entry points, no existing signature or contract changed.
+ *
+ * st_attention_shared: st_attention_joint under the block rule, the second source being k / v themselves:
+ *   Kcat[b] = [ k[b, 0:S1] ; k[b - b % per, 0:S2_eff(b)] ]      (V likewise)
+ *   S2_eff(b) = S1 if b % per != 0 and the gate is on, else 0.
+ * Gate, bit contracts ((a) against st_attention on the concatenation, (b) a style row or the gate off: the bits of st_attention
+ * on that row, no address of another entry formed), kernel form and requirements are st_attention_joint's; per >= 1 (1: every
+ * entry is a style row) (csrc/attention_joint.hip).
+ *
+ * st_style_adain: AdaIN along the token axis, in place, on n_slices (1..3) column slices x0, x1, x2 of one buffer - the q, k and
+ * optionally v columns of the fused projection -, each (B, T, C) with unit channel stride, token stride ld_i and batch stride
+ * T*ld_i.  For b % per != 0, s = b - b % per:
+ *   x[b,t,c] <- fl( x[b,t,c] * a + c' ),  a = sd[s,c] / sd[b,c],  c' = mu[s,c] - mu[b,c] * a            (fp32, one rounding)
+ *   mu = mean over t, sd = sqrt(M2 / (T - 1) + 1e-5), M2 the sum of squared deviations (Welford / Chan in fp32, fixed order).
+ * Style rows (b % per == 0) are never written.  Two launches (statistics per 256-token slab into `workspace`, then the affine),
+ * no atomics, the same bits from every run.  With the gate off (as st_attention_joint's) neither x nor the workspace is touched.
+ * dtype ST_BF16 or ST_F16, T >= 2, C a multiple of 8, slices 16-byte aligned and not overlapping, ld_i multiples of 8, >= C and
+ * under 2^31; workspace: st_style_adain_workspace(B, T, C, n_slices) floats, 8-byte aligned, not shared between concurrent
+ * launches (csrc/style_adain.hip).  Parity with either published implementation is unpinned. */
+int st_attention_shared(const void* q, const void* k, const void* v, void* out, int B, int T, int S1, int H, int D, int per,
+                        long ldq, long ldk, long ldv, long ldo, float scale,
+                        const float* gate_table, const int* gate_step, int gate_n, int dtype, void* stream);
+long st_style_adain_workspace(int B, int T, int C, int n_slices);
+int st_style_adain(void* x0, void* x1, void* x2, int n_slices, int B, int T, int C, long ld0, long ld1, long ld2, int per,
+                   float* workspace, long workspace_floats, const float* gate_table, const int* gate_step, int gate_n,
+                   int dtype, void* stream);
+
 /* ---- windowed self-attention (no reference counterpart: HyperTile, the A1111 / ComfyUI switch): the T = gh * gw tokens of a site
  * are a row-major gh x gw grid, a tiling (nh, nw) cuts it into nh * nw windows of th x tw tokens (th = gh / nh, tw = gw / nw) and
  * every window attends to itself alone.  ABI 18, added without a bump: a new entry point, no existing signature or contract changed.

@@ -64,6 +64,9 @@ SIGNATURES = {
     "st_attention_regions": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _p]),
     "st_attention_segments": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _l, _l, _f, _i, _p]),
     "st_attention_joint": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _l, _l, _l, _l, _f, _p, _p, _i, _i, _p]),
+    "st_attention_shared": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _p, _p, _i, _i, _p]),
+    "st_style_adain_workspace": (_l, [_i, _i, _i, _i]),
+    "st_style_adain": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _l, _i, _p, _l, _p, _p, _i, _i, _p]),
     "st_attention_windows": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _p, _p, _i, _i, _i, _p]),
     "st_attention_windows_rows": (_i, [_i, _i, _i, _i]),
     "st_pag_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),

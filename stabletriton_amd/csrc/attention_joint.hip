@@ -15,6 +15,9 @@
 // tile of the second source); only a tile that holds the boundary or the tail evaluates the rule per lane.
 // S2_eff is 0 unless b < lead and the gate is on; the gate is one scalar load of a value no launch writes, uniform over the grid,
 // and with S2_eff = 0 no address of k2 / v2 is ever formed into a load.
+//
+// st_attention_shared (StyleAligned, style_aligned.py) is the same kernel under another prologue, the block rule: k2 / v2 are k / v,
+// S2 = S1, entry b reads entry b - b % per, and S2_eff is 0 for the first entry of every block of `per` (the style row).
 #include "attention_core.h"
 
 template <typename E>
@@ -22,6 +25,7 @@ struct JointArgs {
     const E *Q, *K, *V, *K2, *V2;
     E* O;
     int T, S1, S2, B2, lead, H;
+    int per;                                           // 0: the rule above; > 0: the block rule of st_attention_shared
     int ldq, ldk, ldv, ldk2, ldv2, ldo;                // token strides (the host checks that they fit: fewer scalar registers than long)
     long bsk2, bsv2;
     float scale_log2e;
@@ -118,8 +122,11 @@ __global__ __launch_bounds__((NW + (LD ? 1 : 0)) * 64) void attnj32i_kernel(cons
     att_xcd_decode<true>(T, 32 * NW, a.H, b, head, xblk);
 
     // the gate: scalar loads of values no launch writes; S = keys this entry attends to
+    // which entry reads a second source, and whose: b < lead reads entry b % B2 of k2 / v2; under the block rule (per > 0) entry b
+    // reads the first entry of its own block of `per`, b - b % per, of k2 / v2 (the host passes k / v), and that first entry nothing
+    const int rem = a.per ? b % a.per : 0;
     int s2 = 0;
-    if (b < a.lead) {
+    if (a.per ? rem != 0 : b < a.lead) {
         bool on = true;
         if (a.table) {
             const int i = *a.step;
@@ -133,9 +140,14 @@ __global__ __launch_bounds__((NW + (LD ? 1 : 0)) * 64) void attnj32i_kernel(cons
     keys.S = __builtin_amdgcn_readfirstlane(S1 + s2);
     keys.Kb = a.K + (size_t)b * S1 * keys.ldk + (size_t)head * ATT_D;
     keys.Vb = a.V + (size_t)b * S1 * keys.ldv + (size_t)head * ATT_D;
-    const int b2 = b % a.B2;
-    keys.K2b = a.K2 + (size_t)b2 * a.bsk2 + (size_t)head * ATT_D;
-    keys.V2b = a.V2 + (size_t)b2 * a.bsv2 + (size_t)head * ATT_D;
+    if (a.per) {                                       // the block rule forms no address of the second source unless it is read
+        keys.K2b = s2 ? a.K2 + (size_t)(b - rem) * a.bsk2 + (size_t)head * ATT_D : keys.Kb;
+        keys.V2b = s2 ? a.V2 + (size_t)(b - rem) * a.bsv2 + (size_t)head * ATT_D : keys.Vb;
+    } else {
+        const int b2 = b % a.B2;
+        keys.K2b = a.K2 + (size_t)b2 * a.bsk2 + (size_t)head * ATT_D;
+        keys.V2b = a.V2 + (size_t)b2 * a.bsv2 + (size_t)head * ATT_D;
+    }
     const long ldq = a.ldq, ldo = a.ldo;
     attn32i_core<E, NW, LD>(a.Q + (size_t)b * T * ldq + (size_t)head * ATT_D, ldq, T, xblk,
                             a.O + (size_t)b * T * ldo + (size_t)head * ATT_D, ldo, a.scale_log2e, lds, keys);
@@ -183,11 +195,45 @@ extern "C" int st_attention_joint(const void* q, const void* k, const void* v, c
     hipStream_t st = (hipStream_t)stream;
     const float c = scale * 1.4426950408889634f;
     if (dtype == ST_BF16) {
-        const JointArgs<bf16> a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)k2, (const bf16*)v2, (bf16*)out, T, S1, S2, B2, lead, H,
+        const JointArgs<bf16> a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)k2, (const bf16*)v2, (bf16*)out, T, S1, S2, B2, lead, H, 0,
                                 (int)ldq, (int)ldk, (int)ldv, (int)ldk2, (int)ldv2, (int)ldo, bsk2, bsv2, c, gate_table, gate_step, gate_n};
         return attention_joint_launch<bf16>(a, B, st);
     }
-    const JointArgs<f16> a{(const f16*)q, (const f16*)k, (const f16*)v, (const f16*)k2, (const f16*)v2, (f16*)out, T, S1, S2, B2, lead, H,
+    const JointArgs<f16> a{(const f16*)q, (const f16*)k, (const f16*)v, (const f16*)k2, (const f16*)v2, (f16*)out, T, S1, S2, B2, lead, H, 0,
                            (int)ldq, (int)ldk, (int)ldv, (int)ldk2, (int)ldv2, (int)ldo, bsk2, bsv2, c, gate_table, gate_step, gate_n};
+    return attention_joint_launch<f16>(a, B, st);
+}
+
+// StyleAligned's shared attention: the same kernel under the block rule.  The second source is k / v themselves (entry b - b % per,
+// S1 keys), so the launch needs no second pair of pointers and a style row (b % per == 0) is st_attention on that row.
+extern "C" int st_attention_shared(const void* q, const void* k, const void* v, void* out, int B, int T, int S1, int H, int D, int per,
+                                   long ldq, long ldk, long ldv, long ldo, float scale,
+                                   const float* gate_table, const int* gate_step, int gate_n, int dtype, void* stream) {
+    ST_REQUIRE(q && k && v && out, "attention_shared: null pointer");
+    ST_REQUIRE(B > 0 && T > 0 && H > 0 && per >= 1, "attention_shared: bad shape B=%d T=%d H=%d per=%d", B, T, H, per);
+    ST_REQUIRE(dtype == ST_BF16 || dtype == ST_F16, "attention_shared: 16-bit types only (dtype %d); other types take the host's slow path", dtype);
+    ST_REQUIRE(D == ATT_D, "attention_shared: head_dim %d not supported (only %d)", D, ATT_D);
+    ST_REQUIRE(S1 >= 256, "attention_shared: S1 = %d, the kernel starts at 256 keys per entry", S1);
+    ST_REQUIRE(2L * S1 <= (1L << 30), "attention_shared: S1 too large");
+    ST_REQUIRE(H <= 65535 && B <= 65535, "attention_shared: too many heads/batches for one launch");
+    ST_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 4 == 0, "attention_shared: strides must keep 16-byte alignment");
+    ST_REQUIRE((ldq | ldk | ldv | ldo) >= 0 && (ldq | ldk | ldv | ldo) < (1L << 31), "attention_shared: token strides must fit 31 bits");
+    ST_REQUIRE(ldk >= (long)H * D && ldv >= (long)H * D, "attention_shared: key / value strides must hold a row of H*D values");
+    ST_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) % 16 == 0, "attention_shared: pointers must be 16-byte aligned");
+    ST_REQUIRE((gate_table == nullptr) == (gate_step == nullptr), "attention_shared: the gate is a table AND a step, or neither");
+    ST_REQUIRE(!gate_table || gate_n > 0, "attention_shared: gate table of %d entries", gate_n);
+    ST_REQUIRE((((uintptr_t)gate_table | (uintptr_t)gate_step) & 3) == 0, "attention_shared: misaligned gate pointer");
+    void* out_split = nullptr;
+    if (int e = st_take_split_arm("attention_shared", (long)B * T, H * D, false, &out_split)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const float c = scale * 1.4426950408889634f;
+    const long bsk = (long)S1 * ldk, bsv = (long)S1 * ldv;
+    if (dtype == ST_BF16) {
+        const JointArgs<bf16> a{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)k, (const bf16*)v, (bf16*)out, T, S1, S1, B, 0, H, per,
+                                (int)ldq, (int)ldk, (int)ldv, (int)ldk, (int)ldv, (int)ldo, bsk, bsv, c, gate_table, gate_step, gate_n};
+        return attention_joint_launch<bf16>(a, B, st);
+    }
+    const JointArgs<f16> a{(const f16*)q, (const f16*)k, (const f16*)v, (const f16*)k, (const f16*)v, (f16*)out, T, S1, S1, B, 0, H, per,
+                           (int)ldq, (int)ldk, (int)ldv, (int)ldk, (int)ldv, (int)ldo, bsk, bsv, c, gate_table, gate_step, gate_n};
     return attention_joint_launch<f16>(a, B, st);
 }

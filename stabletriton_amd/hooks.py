@@ -122,9 +122,15 @@ class _HoistedUNet(nn.Module):
         pag.state_of(self.compiled, "disable_pag")
         self._perturbed_chunks = 0
 
-    def _perturbed_scope(self, chunks: int, latent_hw):
-        """The PAG, SEG, reference or HyperTile state's `using` (a module has at most one of them) around this wrapper's own calls."""
-        from . import hypertile, pag, reference, seg
+    def _perturbed_scope(self, chunks: int, latent_hw, rows: int = 0):
+        """The PAG, SEG, reference, StyleAligned or HyperTile state's `using` (a module has at most one of them) around this wrapper's
+        own calls."""
+        from . import hypertile, pag, reference, seg, style_aligned
+        style = compiled_state(self.compiled, "style_aligned", style_aligned.StyleAligned)
+        if style is not None:
+            if chunks and rows % chunks:
+                raise ValueError(f"style_aligned: a UNet batch of {rows} rows does not divide into {chunks} chunks")
+            return style.using(rows // chunks if chunks else 0)
         tiles = compiled_state(self.compiled, "hypertile", hypertile.HyperTile)
         if tiles is not None:
             if self._hypertile_step is None:
@@ -160,6 +166,31 @@ class _HoistedUNet(nn.Module):
         state = compiled_state(self.compiled, "reference", reference.ReferenceRows)
         if state is not None and self._perturbed_chunks and not torch.cuda.is_current_stream_capturing():
             state.own_gate(sample.device)
+
+    # ---- StyleAligned (style_aligned.py): which rows of a call are the style rows; one captured graph per setting ----
+    def enable_style_aligned(self, chunks: int) -> None:
+        """Every following call's batch of B rows is `chunks` blocks of per = B // chunks rows whose first row is the style row: at the
+        sites compiled in with `style_aligned_layers` every other row's queries and keys are renormalised to its style row's
+        statistics and it attends to its own tokens and to the style row's under one softmax; 2 for [uncond | cond] batches, 1 for
+        one block (ComfyUI's node on a cond-only call).  Raises on a wrapper compiled without `style_aligned_layers`."""
+        from . import style_aligned
+        style_aligned.state_of(self.compiled, "enable_style_aligned")
+        if isinstance(chunks, bool) or not isinstance(chunks, int) or chunks < 1:
+            raise ValueError(f"enable_style_aligned: chunks must be a positive integer (2 or 1), got {chunks!r}")
+        self._perturbed_chunks = chunks
+
+    def disable_style_aligned(self) -> None:
+        from . import style_aligned
+        style_aligned.state_of(self.compiled, "disable_style_aligned")
+        self._perturbed_chunks = 0
+
+    def _apply_style_aligned(self, sample: torch.Tensor) -> None:
+        """The state's own always-on gate and the AdaIN scratch of this call's rows and latent size: allocated outside any capture."""
+        from . import style_aligned
+        state = compiled_state(self.compiled, "style_aligned", style_aligned.StyleAligned)
+        if state is not None and self._perturbed_chunks and not torch.cuda.is_current_stream_capturing():
+            state.own_gate(sample.device)
+            state.bind(sample.shape[0], tuple(sample.shape[-2:]), sample.device)
 
     # ---- HyperTile (hypertile.py): per-site device tables read at this wrapper's own call counter; the captured graphs stay ----------
     HYPERTILE_DRAWS = 64
@@ -428,7 +459,7 @@ class _HoistedUNet(nn.Module):
             ctx = self._ctx[shape]                 # closed over: the graph reads these buffers in place
 
             def step(sample, timesteps, cond, chunks=0):      # (a plain integer: part of the graph cache's key)
-                with self._perturbed_scope(chunks, tuple(sample.shape[-2:])):
+                with self._perturbed_scope(chunks, tuple(sample.shape[-2:]), sample.shape[0]):
                     return self.compiled.forward_with_context(sample, timesteps, ctx, cond)[0]
 
             fn = make_dynamic_graphed_callable(step) if self.cuda_graph else step
@@ -451,7 +482,7 @@ class _HoistedUNet(nn.Module):
             from .optimization import recalibrate_fp8
             ctx = self._ctx[shape]
             def run_once():
-                with self._perturbed_scope(self._perturbed_chunks, tuple(x.shape[-2:])):
+                with self._perturbed_scope(self._perturbed_chunks, tuple(x.shape[-2:]), x.shape[0]):
                     return self.compiled.forward_with_context(x, timesteps, ctx, cond)
 
             ectx = getattr(self.compiled, "exec_context", None)
@@ -468,6 +499,7 @@ class _HoistedUNet(nn.Module):
         self._apply_ip_adapter(sample)
         self._apply_seg(sample)
         self._apply_reference(sample)
+        self._apply_style_aligned(sample)
         self._apply_hypertile(sample)
         self._apply_residuals(sample, self._t2i_state(), t2i, "T2I-Adapter residuals")
         self._apply_residuals(sample, self._cn_state(), controlnet, "ControlNet residuals")
@@ -556,7 +588,8 @@ class DiffusersUNet(_HoistedUNet):
 def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=None, device="cuda",
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                                  region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                                 controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> DiffusersUNet:
+                                 controlnet: bool = False, reference_layers=None, hypertile_layers=None,
+                                 style_aligned_layers=None) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
@@ -576,7 +609,9 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     `reference_layers=(".*",)` compiles the reference-only sites in (reference.py; not with `pag_layers` / `seg_layers`):
     `enable_reference(chunks)` / `disable_reference()` then say which rows of a call are the reference rows.
     `hypertile_layers=(".*",)` compiles the windowed self-attention sites in (hypertile.py; not with `pag_layers` / `seg_layers` /
-    `reference_layers`): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()` drive them."""
+    `reference_layers`): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()` drive them.
+    `style_aligned_layers=(".*",)` compiles the StyleAligned sites in (style_aligned.py; not with any of the four before):
+    `enable_style_aligned(chunks)` / `disable_style_aligned()` then say how a call's rows divide into blocks led by a style row."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
@@ -585,19 +620,20 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
                               ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
-                              reference_layers=reference_layers, hypertile_layers=hypertile_layers)
+                              reference_layers=reference_layers, hypertile_layers=hypertile_layers, style_aligned_layers=style_aligned_layers)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                         regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                        controlnet: bool = False, reference_layers=None, hypertile_layers=None):
+                        controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
                                              regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers,
-                                             t2i_adapter=t2i_adapter, controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers)
+                                             t2i_adapter=t2i_adapter, controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
+                                             style_aligned_layers=style_aligned_layers)
     return pipe
 
 
@@ -627,7 +663,7 @@ class ComfyUNet(_HoistedUNet):
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                        region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                       controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> ComfyUNet:
+                       controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
@@ -641,20 +677,23 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
     `output` being skip i in encoder order (ComfyUI pops from the end while the decoder consumes its skips last-first); a non-empty
     `"input"` raises.  `reference_layers=(".*",)`: with reference-only sites (the ReferenceOnlySimple node's batch of
     [generated | reference] latents is `enable_reference(2)`).  `hypertile_layers=(".*",)`: with windowed self-attention sites (the
-    HyperTile node): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()`."""
+    HyperTile node): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()`.  `style_aligned_layers=(".*",)`: with StyleAligned
+    sites (the StyleAligned Batch Align node with share_attn q+k, share_norm disabled): `enable_style_aligned(chunks)` - 1 for a
+    cond-only call, 2 for [uncond | cond] - / `disable_style_aligned()`."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
                               region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
-                              controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers)
+                              controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
+                              style_aligned_layers=style_aligned_layers)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                       regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                      controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> ComfyUNet:
+                      controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
     adapter = compile_comfy_unet(unet, cuda_graph, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
                                  ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
-                                 reference_layers=reference_layers, hypertile_layers=hypertile_layers)
+                                 reference_layers=reference_layers, hypertile_layers=hypertile_layers, style_aligned_layers=style_aligned_layers)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -1373,6 +1373,125 @@ def attention_joint(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, k2: torch
     return out
 
 
+def attention_shared(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float, per: int, gate=None,
+                     fused: Optional[bool] = None) -> torch.Tensor:
+    """Self-attention whose batch is cut into blocks of `per` entries that share their first entry's keys - StyleAligned
+    (style_aligned.py, csrc/attention_joint.hip): q, k, v (B, T, H*D) as `attention` takes them (column slices of the fused q|k|v
+    buffer are taken as they are).  Entry b with b % per != 0 attends to [k[b] ; k[b - b % per]] under ONE softmax; the first entry
+    of a block, the style row, to k[b] alone; per == 1 is `attention`.  `gate` = (step, table) as `attention_joint` takes it: with
+    table[clamp(*step)] == 0 every entry attends to k[b] alone.  None: always on.
+    bf16 / fp16 at head size 64 with S1 >= 256 is ONE launch: the bits of `attention` on the concatenation for the other rows with
+    the gate on, the bits of `attention(q, k, v)` otherwise.  Everything else (fp32 strict mode, other head sizes, short S1) takes
+    the slow path: `attention` on `torch.cat` of every entry's keys with its style row's, `attention` on the plain keys, and a
+    `torch.where` between the two over the style rows and the device gate - all legal inside a capture.  fused=False forces the slow
+    path, fused=True raises where the kernel does not apply.  CPU tensors take style_aligned.shared_attention_reference."""
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
+        raise BackendError("attention_shared expects (B, T, H*D) tensors")
+    B, T, Cc = q.shape
+    S1 = k.shape[1]
+    D = Cc // num_heads
+    if isinstance(per, bool) or not isinstance(per, int) or per < 1:
+        raise BackendError(f"attention_shared: per must be an integer of 1 or more (rows per block), got {per!r}")
+    if k.shape != v.shape or k.shape[0] != B or k.shape[2] != Cc:
+        raise BackendError(f"attention_shared: k / v must be (B, S1, H*D) for q {tuple(q.shape)}, got k {tuple(k.shape)}, v {tuple(v.shape)}")
+    if len({t.dtype for t in (q, k, v)}) != 1:
+        raise BackendError("attention_shared: q, k and v must share a dtype")
+    if q.device.type == "cpu":
+        from .style_aligned import shared_attention_reference
+        on = _gate_on(gate, "attention_shared")
+        shared = shared_attention_reference(q, k, v, num_heads, scale, per)
+        return shared if on is None else torch.where(on, shared, shared_attention_reference(q, k, v, num_heads, scale, 1))
+    _C.require_device(q, k, v)
+    if gate is not None:
+        _C.require_device(*gate)
+        _residual_table("attention_shared", gate[1], gate[0])
+    applies = q.dtype in (torch.bfloat16, torch.float16) and D == 64 and S1 >= JOINT_MIN_S1
+    if fused and not applies:
+        raise BackendError(f"attention_shared: the kernel takes bf16 / fp16 at head size 64 with S1 >= {JOINT_MIN_S1}; got {q.dtype}, head size {D}, "
+                           f"S1 = {S1}")
+    if fused is False or not applies:
+        plain = attention(q, k, v, num_heads, scale)
+        if per == 1 or B == 1:
+            return plain
+        rows = torch.arange(B, device=q.device)
+        style = rows - rows % per
+        joint = attention(q, torch.cat([k, k.index_select(0, style)], dim=1), torch.cat([v, v.index_select(0, style)], dim=1), num_heads, scale)
+        keep = rows == style                                   # the style rows, and every row while the gate is off
+        on = _gate_on(gate, "attention_shared")
+        if on is not None:
+            keep = keep | ~on
+        return torch.where(keep.reshape(B, 1, 1), plain, joint)
+
+    def tok(t):
+        if t.stride(2) == 1 and t.stride(0) == t.stride(1) * t.shape[1]:
+            return t, t.stride(1)
+        t = t.contiguous()
+        return t, t.shape[2]
+
+    q_, ldq = tok(q)
+    k_, ldk = tok(k)
+    v_, ldv = tok(v)
+    out = torch.empty((B, T, Cc), dtype=q.dtype, device=q.device)
+    step, table = gate if gate is not None else (None, None)
+    _C.check(_C.load().st_attention_shared(q_.data_ptr(), k_.data_ptr(), v_.data_ptr(), out.data_ptr(), B, T, S1, num_heads, D, per, ldq, ldk, ldv,
+                                           Cc, float(scale), _ptr(table), _ptr(step), 0 if table is None else table.numel(),
+                                           _C.dtype_code(q.dtype), _C.stream_ptr()), "attention_shared")
+    return out
+
+
+def style_adain_workspace(B: int, T: int, C: int, n_slices: int, device) -> torch.Tensor:
+    """fp32 scratch of `style_adain` for slices of (B, T, C) (allocate once; a captured graph keeps its address)."""
+    return torch.empty(max(1, _C.load().st_style_adain_workspace(B, T, C, n_slices)), dtype=torch.float32, device=device)
+
+
+def style_adain(slices, per: int, gate=None, workspace: Optional[torch.Tensor] = None):
+    """AdaIN along the token axis inside blocks of `per` batch entries - StyleAligned's renormalisation of queries and keys
+    (style_aligned.py, csrc/style_adain.hip): `slices` are 1 to 3 tensors (B, T, C) of one dtype, the q, k (and v) columns of the
+    fused projection buffer.  Entry b with b % per != 0 becomes (x - mu[b]) / sd[b] * sd[s] + mu[s], s = b - b % per the block's style
+    row, mu the mean and sd = sqrt(unbiased variance + 1e-5) over the T tokens of each (entry, channel); style rows keep their
+    bits.  `gate` = (step, table) as `attention_joint` takes it: with table[clamp(*step)] == 0 nothing changes.  None: always on.
+    Returns the tensors to attend with.  bf16 / fp16 device tensors with unit channel stride, C a multiple of 8 and 16-byte
+    aligned rows are rewritten IN PLACE by two launches (per-slab Welford statistics into `workspace`, then one fp32 fma per value
+    with one rounding; no atomics, the same bits from every run; gated off, neither the tensors nor the workspace are touched)
+    and returned as they are; `workspace`: style_adain_workspace's, or None to allocate one here.  Everything else (fp32 strict
+    mode, CPU tensors, odd layouts) takes the slow path: style_aligned.adain_reference in fp32, out of place, and with a device
+    gate a `torch.where` between the result and the input - legal inside a capture; the inputs are then left alone."""
+    slices = tuple(slices)
+    if not 1 <= len(slices) <= 3 or not all(torch.is_tensor(t) and t.dim() == 3 for t in slices):
+        raise BackendError("style_adain: 1 to 3 tensors (B, T, C) expected")
+    x0 = slices[0]
+    B, T, Cc = x0.shape
+    if any(t.shape != x0.shape or t.dtype != x0.dtype or t.device != x0.device for t in slices):
+        raise BackendError("style_adain: the slices must share shape, dtype and device")
+    if isinstance(per, bool) or not isinstance(per, int) or per < 1:
+        raise BackendError(f"style_adain: per must be an integer of 1 or more (rows per block), got {per!r}")
+    if T < 2:
+        raise BackendError("style_adain: T = 1, the unbiased variance over the tokens is undefined")
+    if per == 1 or B == 1:
+        return slices
+    applies = x0.device.type == "cuda" and x0.dtype in (torch.bfloat16, torch.float16) and Cc % 8 == 0 and all(
+        t.stride(2) == 1 and t.stride(0) == t.stride(1) * T and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0 for t in slices)
+    if not applies:
+        from .style_aligned import adain_reference
+        on = _gate_on(gate, "style_adain")
+        outs = tuple(adain_reference(t.float(), per).to(t.dtype) for t in slices)
+        return outs if on is None else tuple(torch.where(on, o, t) for o, t in zip(outs, slices))
+    if gate is not None:
+        _C.require_device(*gate)
+        _residual_table("style_adain", gate[1], gate[0])
+    if workspace is None:
+        workspace = style_adain_workspace(B, T, Cc, len(slices), x0.device)
+    _C.require_device(workspace)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise BackendError("style_adain: workspace must be a contiguous fp32 tensor (style_adain_workspace)")
+    step, table = gate if gate is not None else (None, None)
+    ptrs = [t.data_ptr() for t in slices] + [None] * (3 - len(slices))
+    lds = [t.stride(1) for t in slices] + [0] * (3 - len(slices))
+    _C.check(_C.load().st_style_adain(*ptrs, len(slices), B, T, Cc, *lds, per, workspace.data_ptr(), workspace.numel(), _ptr(table), _ptr(step),
+                                      0 if table is None else table.numel(), _C.dtype_code(x0.dtype), _C.stream_ptr()), "style_adain")
+    return slices
+
+
 def attention_windows(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, scale: float, grid_hw, tiling=None, table=None,
                       fused: Optional[bool] = None, rows: Optional[int] = None) -> torch.Tensor:
     """Windowed self-attention - HyperTile (hypertile.py, csrc/attention_windows.hip): q, k, v (B, T, H*D) as `attention` takes them,

@@ -21,7 +21,7 @@ from . import t2i_adapter as _t2i
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_hypertile, insert_reference, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_hypertile, insert_reference, insert_style_aligned, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
@@ -29,7 +29,7 @@ from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention,
 def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
                     ip_adapter=None, seg_layers=None, t2i_adapter: bool = False, controlnet: bool = False,
-                    reference_layers=None, hypertile_layers=None) -> fx.GraphModule:
+                    reference_layers=None, hypertile_layers=None, style_aligned_layers=None) -> fx.GraphModule:
     """Pass pipeline over a traced module; an untraced nn.Module is traced here, after the flags were checked against each other
     (optimize_model relies on it: a bad combination raises before the trace).  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
@@ -57,8 +57,13 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     reference.py); the state, `gm.reference`, starts with chunks 0 = ordinary attention; not with `pag_layers` or `seg_layers` (a
     site carries one leaf).  `hypertile_layers` (addition, off by default, likewise): regular expressions selecting the self-attention
     sites that can run windowed (HyperTile; optimizers/insert_hypertile.py, hypertile.py); the state, `gm.hypertile`, is ordinary
-    attention outside its `using`; not with `pag_layers`, `seg_layers` or `reference_layers` (a site carries one leaf)."""
-    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet, reference_layers, hypertile_layers)
+    attention outside its `using`; not with `pag_layers`, `seg_layers` or `reference_layers` (a site carries one leaf).
+    `style_aligned_layers` (addition, off by default, likewise): regular expressions selecting the self-attention sites whose batch
+    entries renormalise their queries and keys to, and share the keys of, the first entry of their block (StyleAligned;
+    optimizers/insert_style_aligned.py, style_aligned.py); the state, `gm.style_aligned`, starts with per 0 = ordinary attention; not
+    with `pag_layers`, `seg_layers`, `reference_layers` or `hypertile_layers` (a site carries one leaf)."""
+    check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet, reference_layers, hypertile_layers,
+                              style_aligned_layers)
     if not isinstance(gm, fx.GraphModule):
         gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
@@ -80,6 +85,8 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
         stats["reference_sites"] = insert_reference(gm, reference_layers)
     if hypertile_layers is not None:      # likewise (never with any of the three: check_feature_combination)
         stats["hypertile_sites"] = insert_hypertile(gm, hypertile_layers)
+    if style_aligned_layers is not None:      # likewise (never with any of the four: check_feature_combination)
+        stats["style_aligned_sites"] = insert_style_aligned(gm, style_aligned_layers)
     if regions is not None:         # likewise
         stats["region_sites"] = insert_regions(gm, regions, region_tokens)
     if ip_adapter is not None:      # likewise
@@ -113,8 +120,11 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
 
 
 def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet=False, reference_layers=None,
-                              hypertile_layers=None) -> None:
+                              hypertile_layers=None, style_aligned_layers=None) -> None:
     """The compile flags that exclude each other."""
+    if style_aligned_layers is not None and any(v is not None for v in (pag_layers, seg_layers, reference_layers, hypertile_layers)):
+        raise ValueError("style_aligned_layers cannot be combined with pag_layers, seg_layers, reference_layers or hypertile_layers: a "
+                         "self-attention site carries one leaf")
     if hypertile_layers is not None and (pag_layers is not None or seg_layers is not None or reference_layers is not None):
         raise ValueError("hypertile_layers cannot be combined with pag_layers, seg_layers or reference_layers: a self-attention site carries "
                          "one leaf")
@@ -136,8 +146,17 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
                    pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None,
-                   t2i_adapter: bool = False, controlnet: bool = False, reference_layers=None, hypertile_layers=None) -> fx.GraphModule:
-    """`hypertile_layers=(".*",)` (addition): HyperTile (hypertile.py).  The selected self-attention sites can cut their token grid into
+                   t2i_adapter: bool = False, controlnet: bool = False, reference_layers=None, hypertile_layers=None,
+                   style_aligned_layers=None) -> fx.GraphModule:
+    """`style_aligned_layers=(".*",)` (addition): StyleAligned (style_aligned.py).  The selected self-attention sites can cut the batch
+    of a call into blocks of `per` entries whose first entry is the style row: every other entry's queries and keys are renormalised
+    to the style row's per-channel statistics over the tokens (two launches in place on the fused projection buffer,
+    csrc/style_adain.hip) and it attends to its own tokens and to the style row's under one softmax (one launch,
+    csrc/attention_joint.hip).  `gm.style_aligned.using(per, step=..., table=...)` around the caller's own calls, `step` / `table` an
+    optional device gate read at every launch; per 0, the initial state, is ordinary attention; `set_adain("qk" | "qkv" | None)`.
+    With `cuda_graph=True` the module's own cached graphs never align (DenoiseLoop and the hooks capture their own over a
+    `cuda_graph=False` module).  Not with `pag_layers`, `seg_layers`, `reference_layers` or `hypertile_layers`.
+    `hypertile_layers=(".*",)` (addition): HyperTile (hypertile.py).  The selected self-attention sites can cut their token grid into
     windows that attend to themselves alone (one launch, csrc/attention_windows.hip), the tiling read per step from per-site device
     tables: `gm.hypertile.bind(n_steps)`, `set(tile, swap, seed, start, end)` / `set(None)` in place, no new capture, and
     `using(latent_hw, step)` around the caller's own calls; outside `using` the sites are ordinary attention (so with
@@ -202,7 +221,8 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
         raise RuntimeError("fp8 projections need a bfloat16 model")
     gm = replace_backend(model, fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
                          region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
-                         controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers)
+                         controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
+                         style_aligned_layers=style_aligned_layers)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

@@ -19,6 +19,7 @@ from .insert_pag import insert_pag
 from .insert_seg import insert_seg
 from .insert_reference import insert_reference
 from .insert_hypertile import insert_hypertile
+from .insert_style_aligned import insert_style_aligned
 from .insert_regions import insert_regions
 from .insert_ip_adapter import insert_ip_adapter
 from .cleanup import dedupe_pure_calls, fuse_token_residual

@@ -119,6 +119,17 @@ read) at the step counter: `set_reference` / `set_reference(None)` are in-place 
 is static, so a loop gated off still evaluates the reference rows.  Not with `pag_scale`, `seg_scale`, `tile_hw`, or UNets compiled with
 `regions`, `ip_adapter`, `t2i_adapter`, `controlnet`.  Parity with A1111, ComfyUI and diffusers is unpinned; `style_fidelity`, a continuous
 strength and the AdaIN variant are out of scope.
+
+StyleAligned (`style_aligned=True`, `set_style_aligned`; style_aligned.py) on a UNet compiled with `style_aligned_layers`, batch >= 2:
+image 0 is the style image.  No rows are added: in every row block, [negative | positive] with guidance, the selected self-attention
+sites renormalise the queries and keys of rows 1.. to row 0's per-channel token statistics (two launches in place on the fused
+projection buffer, csrc/style_adain.hip) and let them attend to row 0's tokens beside their own (one launch, csrc/attention_joint.hip);
+row 0 runs ordinary attention, so image 0 is what the loop without the flag gives.  The sites read a per-step device table (1 inside
+[start * n, end * n), 0 = ordinary attention on untouched q / k) at the step counter: `set_style_aligned` / `set_style_aligned(None)`
+are in-place writes, before or after `capture()`; the table starts all 0.  While no step is on the loop's calls name no blocks and the
+captured graph is the plain loop's; a change between "no step on" and "some step on" drops the graph for one new capture.  Not with `pag_scale`, `seg_scale`, `tile_hw`,
+`reference=True`, or UNets compiled with `regions`, `ip_adapter`, `t2i_adapter`, `controlnet`.  Parity with either published
+implementation is unpinned; shared normalisation statistics, score scale / shift and full attention sharing are out of scope.
 """
 from __future__ import annotations
 
@@ -146,7 +157,7 @@ class DenoiseLoop:
                  pag_scale: Optional[Union[float, Sequence[float]]] = None,
                  seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf"),
                  tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform", controlnet: Optional[Callable] = None,
-                 inpaint: bool = False, reference: bool = False):
+                 inpaint: bool = False, reference: bool = False, style_aligned: bool = False):
         assert mode in ("loop", "step", "eager")
         if seg_scale is not None and pag_scale is not None:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
@@ -180,6 +191,21 @@ class DenoiseLoop:
                     raise ValueError(f"DenoiseLoop: reference=True cannot be combined with a UNet compiled with {name}: its row-bound "
                                      "state is not verified with a reference row block")
         self._reference_chunks = 0 if not reference else (3 if guidance_scale is not None else 2)
+        # StyleAligned: the UNet's sites must exist; image 0 is the style image, so every row block of `batch` rows is one block of the
+        # sites (per = batch) and its first row the style row
+        self._style = None
+        if style_aligned:
+            from . import style_aligned as _style
+            self._style = _style.state_of(unet, "DenoiseLoop(style_aligned=True)")
+            if batch < 2:
+                raise ValueError("DenoiseLoop: style_aligned=True needs batch >= 2 (image 0 is the style image of the others)")
+            if pag_scale is not None or tile_hw is not None or reference:
+                raise ValueError("DenoiseLoop: style_aligned=True cannot be combined with pag_scale, seg_scale, tile_hw or reference=True")
+            for name, cls in (("regions", _regions.Regions), ("ip_adapter", _ip.IPAdapter), ("t2i_adapter", _t2i.T2IAdapterState),
+                              ("controlnet", _cn.ControlNetState)):
+                if compiled_state(unet, name, cls) is not None:
+                    raise ValueError(f"DenoiseLoop: style_aligned=True cannot be combined with a UNet compiled with {name}: its row-bound "
+                                     "state is not verified with rows that read each other")
         # HyperTile: a UNet compiled with hypertile_layers runs its sites under this loop's latent size and step counter; the per-site
         # tables start all (1, 1) = the bits of ordinary attention (set_hypertile)
         from . import hypertile as _hypertile
@@ -325,6 +351,13 @@ class DenoiseLoop:
                 self.sigma_next = torch.tensor(self.tables.sigmas[1:], dtype=torch.float32, device=dev)
         if self._hypertile is not None:
             self._hypertile.bind(n)
+        # StyleAligned: the sites' per-step gate (all 0 = off: ordinary attention, q / k untouched) and their AdaIN scratch; read by
+        # address, allocated once, outside capture
+        self.style_aligned_table, self._style_live = None, False      # (live: some step of the table is on; a host value)
+        if self._style is not None:
+            self.style_aligned_table = torch.zeros(n, dtype=torch.float32, device=dev)
+            if dev.type == "cuda":
+                self._style.bind(rows, (lh, lw), dev)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -547,6 +580,26 @@ class DenoiseLoop:
         self.reference_noise.copy_(z)
         self.reference_table.copy_(table)
         self._write_reference_input(int(self.step.item()) % n)
+
+    def set_style_aligned(self, start: Optional[float] = 0.0, end: float = 1.0) -> None:
+        """StyleAligned (style_aligned.py) on a loop built with `style_aligned=True`: at the steps in [int(start * n), int(end * n)) the
+        selected self-attention sites renormalise the queries and keys of images 1.. to image 0's statistics and let them attend to
+        image 0's tokens beside their own; `set_style_aligned(None)` switches it off: ordinary attention on untouched q / k.  An
+        in-place write of the per-step device table, before or after `capture()`; image 0 never depends on the others.
+        While no step is on, the loop's UNet calls do not name the blocks at all (per 0): the sites are the plain attention launch and
+        the loop costs what a loop without the flag costs.  A gated-off site still launches its two AdaIN grids, so going from "no
+        step on" to "some step on" or back drops the captured graph and the next run captures again; moving the window while on does
+        not."""
+        if self._style is None:
+            raise ValueError("set_style_aligned: this loop was built without style_aligned=True")
+        if start is not None and not 0.0 <= start <= end <= 1.0:
+            raise ValueError(f"set_style_aligned: 0 <= start <= end <= 1 expected, got start={start}, end={end}")
+        n = self.n_steps
+        on = [0.0] * n if start is None else [1.0 if int(start * n) <= i < int(end * n) else 0.0 for i in range(n)]
+        self.style_aligned_table.copy_(torch.tensor(on))
+        if any(on) != self._style_live:                    # the captured launches differ: plain attention against AdaIN + shared attention
+            self._style_live = any(on)
+            self.graph, self._captured_steps = None, 0
 
     def set_hypertile(self, tile: Optional[int] = 32, swap: int = 2, seed: int = 0, start: float = 0.0, end: float = 1.0) -> None:
         """HyperTile (hypertile.py) on a UNet compiled with `hypertile_layers`: per step in [int(start * n), int(end * n)) and site, a
@@ -901,6 +954,10 @@ class DenoiseLoop:
             if self._reference is not None:      # the last B rows are the reference block; the sites read this loop's gate at `step`
                 scopes.enter_context(self._reference.using(self._reference_chunks, step=self.step_ids[0:1] if step is None else step,
                                                            table=self.reference_table))
+            if self._style is not None:          # every row block of `batch` rows is led by its style row; the sites read this loop's gate at
+                # `step`.  With no step on the blocks are not named: no launch of the feature is captured (set_style_aligned)
+                scopes.enter_context(self._style.using(self.batch if self._style_live else 0, step=self.step_ids[0:1] if step is None else step,
+                                                       table=self.style_aligned_table))
             if self._hypertile is not None:      # the sites derive their token grids from the latent size and read their tables at `step`
                 scopes.enter_context(self._hypertile.using(self._latent_hw, self.step_ids[0:1] if step is None else step))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
