@@ -60,7 +60,9 @@ int         st_abi_version(void);          /* bumps on any signature or contract
                                               st_pag_euler_step, st_pag_dpmpp2m_step and st_pag_sde_step, and then a DoRA and a LoHa / LoKr entry point beside
                                               st_lora_merge, added without a bump: new entry points, no existing signature or contract changed (st_attention_regions, st_attention_segments and st_attention_joint, after 18, likewise);
                                               18: st_lora_merge takes one ST_LORA_FORM_WORDS segment row, the norm pass's tables and `forms`, and is
-                                              the only LoRA entry point again: the two beside it are removed) */
+                                              the only LoRA entry point again: the two beside it are removed;
+                                              st_attention_colsum, st_attention_colsum_workspace, st_sag_degrade, st_sag_euler_step, st_sag_dpmpp2m_step and st_sag_sde_step,
+                                              after 18, are new entry points without a bump like those above) */
 const char* st_last_error(void);           /* host string, thread-local     */
 
 /* GroupNorm (+SiLU).  Replaces reference group_norm_wrapper
@@ -613,6 +615,46 @@ int st_pag_sde_step(float* latent, const void* eps, void* next_in, float* histor
                     const float* guidance, const float* rescale, const float* pag, const int* step, const int* start,
                     const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* ---- Self-attention guidance (SAG; Hong et al. 2023; ComfyUI's nodes_sag.py restated for an eps-predicting loop; no reference
+ * counterpart).  Added after ABI 18 without a bump: new entry points, no existing signature or contract changed.
+ *
+ * st_attention_colsum: A[b, j] = (1 / H) sum_h sum_i softmax_j(q_i . k_j * scale)[i, j], the column sums of a self-attention's
+ * probability matrix averaged over the heads, fp32 (B, T), for the B leading batch entries the caller names.  q and k as
+ * st_attention takes them (token stride ldq / ldk, batch stride T * ld, head h at columns h * D), T == S, D == 64, ST_BF16 or
+ * ST_F16, 16-byte aligned, ld multiples of 8.  Three launches - lse per query row, per-(head, key) sums of exp2(s - lse), the heads -
+ * with fp32 scores from the matrix pipe; no atomics, every sum's order is fixed by the shape: the same bits from every run.
+ * workspace: st_attention_colsum_workspace(B, T, H) floats, not shared between concurrent launches (csrc/attention_colsum.hip).
+ *
+ * st_sag_degrade: the input of a step's second UNet call.  latent (B, lh, lw, 4) fp32 and eps_neg / out (B, lh, lw, 4) of `dtype`,
+ * dense NHWC, 16-byte aligned; amap (B, th, tw) fp32, st_attention_colsum's output on the site's token grid; mask (B, lh, lw) fp32.
+ * With i = *step clamped to [0, n_steps), sigma = sigmas[i], params = a DEVICE row (threshold, blur sigma), all read when it runs:
+ *   x0 = latent - sigma * eps_neg;  mask = amap[b, floor(y * th / lh), floor(x * tw / lw)] > threshold (written as 1 / 0);
+ *   blur = the separable nine-tap Gaussian of x0 per channel, taps exp(-(d / blur sigma)^2 / 2) normalised, reflect padding;
+ *   out = ((mask ? blur : x0) + sigma * eps_neg) * in_scale[i], fp32 arithmetic, one rounding.
+ * One launch; lh, lw > 4; th <= lh, tw <= lw (csrc/sag.hip).
+ *
+ * st_sag_*_step: st_cfg_euler_step, st_dpmpp2m_step and st_sde_step under guidance (guidance never NULL; eps and next_in keep their
+ * 2 * batch rows [negative | positive]) with the prediction of that second call, e_sag (batch rows of `dtype`, 16-byte aligned), and
+ * one more device table `sag` of n_steps floats: behind the guidance and its rescale, e = fma(sag[i], e_neg - e_sag, e).  Everything
+ * after e is the two-way entry point's arithmetic; sag[i] == 0 gives its latent, next_in and history bit for bit. */
+long st_attention_colsum_workspace(int B, int T, int H);
+int st_attention_colsum(const void* q, const void* k, float* out, int B, int T, int H, int D, long ldq, long ldk, float scale,
+                        float* workspace, long workspace_floats, int dtype, void* stream);
+int st_sag_degrade(const float* latent, const void* eps_neg, const float* amap, const float* sigmas, const float* in_scale,
+                   const int* step, const float* params, void* out, float* mask, int B, int lh, int lw, int th, int tw, int n_steps,
+                   int dtype, void* stream);
+int st_sag_euler_step(float* latent, const void* eps, const void* e_sag, void* next_in, const float* dsigma, const float* in_scale,
+                      const float* guidance, const float* rescale, const float* sag, const int* step, int batch, long per_sample,
+                      int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream);
+int st_sag_dpmpp2m_step(float* latent, const void* eps, const void* e_sag, void* next_in, float* history, const float* coef,
+                        const float* in_scale, const float* guidance, const float* rescale, const float* sag, const int* step,
+                        const int* start, int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int st_sag_sde_step(float* latent, const void* eps, const void* e_sag, void* next_in, float* history, const float* coef,
+                    const float* in_scale, const float* guidance, const float* rescale, const float* sag, const int* step,
+                    const int* start, const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- T2I-Adapter residual sites (no reference counterpart: diffusers' `down_intrablock_additional_residuals`, ComfyUI's
  * `control["input"]` / `["middle"]` entries of a T2I adapter).  Added after ABI 18 without a bump: a new entry point, no existing

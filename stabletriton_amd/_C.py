@@ -72,6 +72,12 @@ SIGNATURES = {
     "st_pag_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_pag_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
+    "st_attention_colsum_workspace": (_l, [_i, _i, _i]),
+    "st_attention_colsum": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _f, _p, _l, _i, _p]),
+    "st_sag_degrade": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "st_sag_euler_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
+    "st_sag_dpmpp2m_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
+    "st_sag_sde_step": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _l, _i, _i, _p, _z, _p]),
     "st_seg_blur_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "st_seg_blur": (_i, [_p, _p, _p, _i, _i, _i, _i, _l, _l, _i, _p, _z, _p]),
     "st_attention_seg": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _l, _l, _f, _i, _i, _i, _i, _p, _p, _z, _p]),

@@ -129,6 +129,24 @@ __device__ __forceinline__ void cfg_store8(T* p, const float (&v)[8]) {
 // keep the parameter list (and with it the kernel-argument layout and the code) they always had.
 __device__ __forceinline__ const float* pag_table() { return nullptr; }
 __device__ __forceinline__ const float* pag_table(const float* p) { return p; }
+// The SAG instantiations (self-attention guidance, below) take two: the `sag` table and the second UNet call's prediction.  Their pack
+// names no pag table, and the plain and PAG instantiations have no SAG term.
+template <typename T> __device__ __forceinline__ const float* pag_table(const float*, const T*) { return nullptr; }
+template <typename T>
+__device__ __forceinline__ void sag_term8(const T*, int, long, long, int, float (&)[8]) {}
+template <typename T>
+__device__ __forceinline__ void sag_term8(const T*, int, long, long, int, float (&)[8], const float*) {}
+// e += s * (e_neg - e_sag) on the finished (guided, rescaled) value, one fma each: s = 0 leaves e's bits
+template <typename T>
+__device__ __forceinline__ void sag_term8(const T* __restrict__ eps, int b, long per_sample, long j, int i, float (&e)[8],
+                                          const float* __restrict__ sag, const T* __restrict__ e_sag) {
+    float neg[8], deg[8];
+    cfg_load8(eps + (long)b * per_sample + j, neg);
+    cfg_load8(e_sag + (long)b * per_sample + j, deg);
+    const float s = sag[i];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) e[k] = fmaf(s, neg[k] - deg[k], e[k]);
+}
 
 // the guided eps of 8 values at offset j of sample b (also returns e_pos for the statistics).  PAG (perturbed-attention
 // guidance, below): one more row block [.. | perturbed] and e += s * (e_pos - e_pert); GUIDED = false (PAG only): rows
@@ -244,6 +262,7 @@ __global__ __launch_bounds__(CFG_THREADS) void cfg_euler_kernel(float* __restric
 #pragma unroll
         for (int k = 0; k < 8; ++k) e[k] = phi * (e[k] * ratio) + keep * e[k];      // phi = 0: 0 * r + 1 * e == e, the plain path's bits
     }
+    sag_term8(eps, b, per_sample, j, i, e, extra...);
     float* lat = latent + (long)b * per_sample + j;
     {
         const f32x4 a = *reinterpret_cast<const f32x4*>(lat), c = *reinterpret_cast<const f32x4*>(lat + 4);
@@ -274,8 +293,21 @@ extern "C" size_t st_cfg_step_workspace_bytes(int batch, long per_sample) {
 template <typename T>
 static int cfg_launch(float* latent, const void* eps, void* next_in, const float* dsigma, const float* in_scale, const float* guidance,
                        const float* rescale, const float* pag, const int* step, int batch, long per_sample, int n_steps, double* ws,
-                       hipStream_t st) {
+                       hipStream_t st, const float* sag = nullptr, const void* e_sag = nullptr) {
     const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (sag) {                                   // the SAG instantiations (st_sag_euler_step): the statistics are the two-way kernel's
+        if (rescale) {
+            hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
+            if (st_check_launch("sag_euler_step (statistics)")) return 1;
+            hipLaunchKernelGGL((cfg_euler_kernel<T, true, false, true, const float*, const T*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps,
+                               (T*)next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)ws, sag, (const T*)e_sag);
+        } else {
+            hipLaunchKernelGGL((cfg_euler_kernel<T, false, false, true, const float*, const T*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps,
+                               (T*)next_in, dsigma, in_scale, guidance, rescale, step, batch, per_sample, n_steps, (const double*)nullptr, sag,
+                               (const T*)e_sag);
+        }
+        return st_check_launch("sag_euler_step");
+    }
     if (pag) {                                   // the three-way instantiations (st_pag_euler_step)
         if (rescale) {
             hipLaunchKernelGGL((cfg_stats_kernel<T, true, const float*>), grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws, pag);
@@ -306,8 +338,10 @@ static int cfg_launch(float* latent, const void* eps, void* next_in, const float
 // shared by st_cfg_euler_step (pag_entry false: `pag` is NULL, `guidance` required) and st_pag_euler_step
 static int cfg_euler_entry(const char* who, bool pag_entry, float* latent, const void* eps, void* next_in, const float* dsigma,
                            const float* in_scale, const float* guidance, const float* rescale, const float* pag, const int* step,
-                           int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+                           int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream,
+                           const float* sag = nullptr, const void* e_sag = nullptr) {
     ST_REQUIRE(latent && eps && next_in && dsigma && in_scale && (pag_entry ? pag != nullptr : guidance != nullptr) && step, "%s: null pointer", who);
+    ST_REQUIRE((sag == nullptr) == (e_sag == nullptr) && (uintptr_t)e_sag % 16 == 0, "%s: the sag table and a 16-byte aligned e_sag go together", who);
     ST_REQUIRE(!rescale || guidance, "%s: a rescale table needs a guidance table", who);
     ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "%s: bad sizes (batch %d, per_sample %ld, n_steps %d)", who,
                batch, per_sample, n_steps);
@@ -324,11 +358,11 @@ static int cfg_euler_entry(const char* who, bool pag_entry, float* latent, const
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
     if (dtype == ST_BF16)
-        return cfg_launch<bf16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st);
+        return cfg_launch<bf16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st, sag, e_sag);
     if (dtype == ST_F16)
-        return cfg_launch<f16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st);
+        return cfg_launch<f16>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st, sag, e_sag);
     if (dtype == ST_F32)
-        return cfg_launch<float>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st);
+        return cfg_launch<float>(latent, eps, next_in, dsigma, in_scale, guidance, rescale, pag, step, batch, per_sample, n_steps, ws, st, sag, e_sag);
     return st_fail("%s: unsupported dtype %d", who, dtype);
 }
 
@@ -394,6 +428,7 @@ __global__ __launch_bounds__(CFG_THREADS) void dpmpp2m_kernel(float* __restrict_
 #pragma unroll
             for (int q = 0; q < 8; ++q) e[q] = phi * (e[q] * ratio) + keep * e[q];   // phi = 0: the plain path's bits
         }
+        sag_term8(eps, b, per_sample, j, i, e, extra...);
     } else {
         cfg_load8(eps + (long)b * per_sample + j, e);
     }
@@ -425,8 +460,22 @@ __global__ __launch_bounds__(CFG_THREADS) void dpmpp2m_kernel(float* __restrict_
 template <typename T>
 static int dpm_launch(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
                       const float* guidance, const float* rescale, const float* pag, const int* step, const int* start, int batch,
-                      long per_sample, int n_steps, double* ws, hipStream_t st) {
+                      long per_sample, int n_steps, double* ws, hipStream_t st, const float* sag = nullptr, const void* e_sag = nullptr) {
     const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (sag) {                                   // the SAG instantiations (st_sag_dpmpp2m_step)
+        if (rescale) {
+            hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
+            if (st_check_launch("sag_dpmpp2m_step (statistics)")) return 1;
+            hipLaunchKernelGGL((dpmpp2m_kernel<T, true, true, false, const float*, const T*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps,
+                               (T*)next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)ws, sag,
+                               (const T*)e_sag);
+        } else {
+            hipLaunchKernelGGL((dpmpp2m_kernel<T, true, false, false, const float*, const T*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps,
+                               (T*)next_in, history, coef, in_scale, guidance, rescale, step, start, batch, per_sample, n_steps, (const double*)nullptr,
+                               sag, (const T*)e_sag);
+        }
+        return st_check_launch("sag_dpmpp2m_step");
+    }
     if (pag) {                                   // the three-way instantiations (st_pag_dpmpp2m_step)
         if (rescale) {
             hipLaunchKernelGGL((cfg_stats_kernel<T, true, const float*>), grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws, pag);
@@ -461,8 +510,10 @@ static int dpm_launch(float* latent, const void* eps, void* next_in, float* hist
 static int dpm_entry(const char* who, bool pag_entry, float* latent, const void* eps, void* next_in, float* history, const float* coef,
                      const float* in_scale, const float* guidance, const float* rescale, const float* pag, const int* step,
                      const int* start, int batch, long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes,
-                     void* stream) {
+                     void* stream, const float* sag = nullptr, const void* e_sag = nullptr) {
     ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start && (!pag_entry || pag), "%s: null pointer", who);
+    ST_REQUIRE((sag == nullptr) == (e_sag == nullptr) && (!sag || guidance) && (uintptr_t)e_sag % 16 == 0,
+               "%s: the sag table, a 16-byte aligned e_sag and a guidance table go together", who);
     ST_REQUIRE(!rescale || guidance, "%s: a rescale table needs a guidance table", who);
     ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "%s: bad sizes (batch %d, per_sample %ld, n_steps %d)", who,
                batch, per_sample, n_steps);
@@ -479,11 +530,11 @@ static int dpm_entry(const char* who, bool pag_entry, float* latent, const void*
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
     if (dtype == ST_BF16)
-        return dpm_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st);
+        return dpm_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st, sag, e_sag);
     if (dtype == ST_F16)
-        return dpm_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st);
+        return dpm_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st, sag, e_sag);
     if (dtype == ST_F32)
-        return dpm_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st);
+        return dpm_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, batch, per_sample, n_steps, ws, st, sag, e_sag);
     return st_fail("%s: unsupported dtype %d", who, dtype);
 }
 
@@ -542,6 +593,7 @@ __global__ __launch_bounds__(CFG_THREADS) void sde_kernel(float* __restrict__ la
 #pragma unroll
             for (int q = 0; q < 8; ++q) e[q] = phi * (e[q] * ratio) + keep * e[q];   // phi = 0: the plain path's bits
         }
+        sag_term8(eps, b, per_sample, j, i, e, extra...);
     } else {
         cfg_load8(eps + (long)b * per_sample + j, e);
     }
@@ -584,8 +636,23 @@ __global__ __launch_bounds__(CFG_THREADS) void sde_kernel(float* __restrict__ la
 template <typename T>
 static int sde_launch(float* latent, const void* eps, void* next_in, float* history, const float* coef, const float* in_scale,
                       const float* guidance, const float* rescale, const float* pag, const int* step, const int* start,
-                      const unsigned long long* seeds, int batch, long per_sample, int n_steps, double* ws, hipStream_t st) {
+                      const unsigned long long* seeds, int batch, long per_sample, int n_steps, double* ws, hipStream_t st,
+                      const float* sag = nullptr, const void* e_sag = nullptr) {
     const dim3 grid((unsigned)cfg_blocks_per_sample(per_sample), (unsigned)batch);
+    if (sag) {                                   // the SAG instantiations (st_sag_sde_step)
+        if (rescale) {
+            hipLaunchKernelGGL(cfg_stats_kernel<T>, grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws);
+            if (st_check_launch("sag_sde_step (statistics)")) return 1;
+            hipLaunchKernelGGL((sde_kernel<T, true, true, false, const float*, const T*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in,
+                               history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)ws, sag,
+                               (const T*)e_sag);
+        } else {
+            hipLaunchKernelGGL((sde_kernel<T, true, false, false, const float*, const T*>), grid, dim3(CFG_THREADS), 0, st, latent, (const T*)eps, (T*)next_in,
+                               history, coef, in_scale, guidance, rescale, step, start, seeds, batch, per_sample, n_steps, (const double*)nullptr, sag,
+                               (const T*)e_sag);
+        }
+        return st_check_launch("sag_sde_step");
+    }
     if (pag) {                                   // the three-way instantiations (st_pag_sde_step)
         if (rescale) {
             hipLaunchKernelGGL((cfg_stats_kernel<T, true, const float*>), grid, dim3(CFG_THREADS), 0, st, (const T*)eps, guidance, step, batch, per_sample, ws, pag);
@@ -623,8 +690,10 @@ constexpr long PHILOX_MAX_PER_SAMPLE = 4L << 32;
 static int sde_entry(const char* who, bool pag_entry, float* latent, const void* eps, void* next_in, float* history, const float* coef,
                      const float* in_scale, const float* guidance, const float* rescale, const float* pag, const int* step,
                      const int* start, const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype,
-                     void* workspace, size_t workspace_bytes, void* stream) {
+                     void* workspace, size_t workspace_bytes, void* stream, const float* sag = nullptr, const void* e_sag = nullptr) {
     ST_REQUIRE(latent && eps && next_in && history && coef && in_scale && step && start && seeds && (!pag_entry || pag), "%s: null pointer", who);
+    ST_REQUIRE((sag == nullptr) == (e_sag == nullptr) && (!sag || guidance) && (uintptr_t)e_sag % 16 == 0,
+               "%s: the sag table, a 16-byte aligned e_sag and a guidance table go together", who);
     ST_REQUIRE(!rescale || guidance, "%s: a rescale table needs a guidance table", who);
     ST_REQUIRE(batch > 0 && per_sample > 0 && n_steps > 0, "%s: bad sizes (batch %d, per_sample %ld, n_steps %d)", who,
                batch, per_sample, n_steps);
@@ -644,11 +713,11 @@ static int sde_entry(const char* who, bool pag_entry, float* latent, const void*
     hipStream_t st = (hipStream_t)stream;
     double* ws = (double*)workspace;
     if (dtype == ST_BF16)
-        return sde_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st);
+        return sde_launch<bf16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st, sag, e_sag);
     if (dtype == ST_F16)
-        return sde_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st);
+        return sde_launch<f16>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st, sag, e_sag);
     if (dtype == ST_F32)
-        return sde_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st);
+        return sde_launch<float>(latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch, per_sample, n_steps, ws, st, sag, e_sag);
     return st_fail("%s: unsupported dtype %d", who, dtype);
 }
 
@@ -667,6 +736,41 @@ extern "C" int st_pag_sde_step(float* latent, const void* eps, void* next_in, fl
                                size_t workspace_bytes, void* stream) {
     return sde_entry("pag_sde_step", true, latent, eps, next_in, history, coef, in_scale, guidance, rescale, pag, step, start, seeds, batch,
                      per_sample, n_steps, dtype, workspace, workspace_bytes, stream);
+}
+
+// ---- self-attention guidance (SAG; Hong et al. 2023; ComfyUI's nodes_sag.py restated in eps form) in the three updates ------------
+// eps and next_in keep the guided layout, rows [negative | positive] (2 * batch).  e_sag (batch rows, the element type of eps, 16-byte
+// aligned) is a SECOND UNet call's prediction - the negative conditioning on the degraded input of csrc/sag.hip - and `sag` one more
+// device table of n_steps floats, s = sag[i]:
+//   e = cfg(e_neg, e_pos) [+ guidance rescale, as before]  ->  e = fma(s, e_neg - e_sag, e)
+// The term is added behind the rescale (ComfyUI's order: the post-CFG function sees the finished CFG value), so the statistics launch
+// is the two-way one; everything after e is unchanged.  One fma onto the finished value: s = 0 gives the two-way kernels' latent,
+// next_in and history bit for bit.  The existing kernels under a parameter pack of two (the pack is empty in the plain
+// instantiations, one table in PAG's).
+extern "C" int st_sag_euler_step(float* latent, const void* eps, const void* e_sag, void* next_in, const float* dsigma, const float* in_scale,
+                                 const float* guidance, const float* rescale, const float* sag, const int* step, int batch,
+                                 long per_sample, int n_steps, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(sag && e_sag && guidance, "sag_euler_step: null pointer (the sag table, e_sag and the guidance table are required)");
+    return cfg_euler_entry("sag_euler_step", false, latent, eps, next_in, dsigma, in_scale, guidance, rescale, nullptr, step, batch,
+                           per_sample, n_steps, dtype, workspace, workspace_bytes, stream, sag, e_sag);
+}
+
+extern "C" int st_sag_dpmpp2m_step(float* latent, const void* eps, const void* e_sag, void* next_in, float* history, const float* coef,
+                                   const float* in_scale, const float* guidance, const float* rescale, const float* sag, const int* step,
+                                   const int* start, int batch, long per_sample, int n_steps, int dtype, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(sag && e_sag && guidance, "sag_dpmpp2m_step: null pointer (the sag table, e_sag and the guidance table are required)");
+    return dpm_entry("sag_dpmpp2m_step", false, latent, eps, next_in, history, coef, in_scale, guidance, rescale, nullptr, step, start, batch,
+                     per_sample, n_steps, dtype, workspace, workspace_bytes, stream, sag, e_sag);
+}
+
+extern "C" int st_sag_sde_step(float* latent, const void* eps, const void* e_sag, void* next_in, float* history, const float* coef,
+                               const float* in_scale, const float* guidance, const float* rescale, const float* sag, const int* step,
+                               const int* start, const unsigned long long* seeds, int batch, long per_sample, int n_steps, int dtype,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    ST_REQUIRE(sag && e_sag && guidance, "sag_sde_step: null pointer (the sag table, e_sag and the guidance table are required)");
+    return sde_entry("sag_sde_step", false, latent, eps, next_in, history, coef, in_scale, guidance, rescale, nullptr, step, start, seeds, batch,
+                     per_sample, n_steps, dtype, workspace, workspace_bytes, stream, sag, e_sag);
 }
 
 // out[b][4q .. 4q + 3] = the stream of seeds[b] at counter word ctr, one Philox call (16-byte store) per lane

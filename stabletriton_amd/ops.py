@@ -2036,6 +2036,168 @@ def pag_sde_step(latent: torch.Tensor, eps: torch.Tensor, next_in: torch.Tensor,
                                  _C.stream_ptr()), "pag_sde_step")
 
 
+def attention_colsum_workspace(B: int, T: int, num_heads: int, device) -> torch.Tensor:
+    """fp32 scratch of `attention_colsum` for B entries of T tokens (allocate once; a captured graph keeps its address)."""
+    return torch.empty(max(1, _C.load().st_attention_colsum_workspace(B, T, num_heads)), dtype=torch.float32, device=device)
+
+
+def attention_colsum(q: torch.Tensor, k: torch.Tensor, num_heads: int, scale: float, rows: Optional[int] = None,
+                     out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A[b, j] = (1 / H) sum_h sum_i softmax_j(q_i . k_j * scale)[i, j]: the column sums of a self-attention's probability matrix,
+    averaged over the heads - one fp32 value per key token, what self-attention guidance thresholds (sag.py,
+    csrc/attention_colsum.hip).  q and k (B, T, H*D) in projection layout, as `attention` takes them (views of the fused q|k|v buffer
+    are read in place).  Only the leading `rows` batch entries are computed (None: all); `out` (B, T) fp32 keeps the others' values
+    (None: a new tensor, zeros there).  bf16 / fp16 device tensors with D = 64: three launches, the (B H, T, T) matrix is never
+    stored, no atomics, the same bits from every run; `workspace`: attention_colsum_workspace's, or None to allocate one here.
+    Everything else (fp32 strict mode, other head sizes, CPU tensors) takes the slow path: sag.colsum_reference, the fp32 softmax of
+    the leading rows in plain torch - legal inside a capture."""
+    if q.dim() != 3 or k.shape != q.shape or q.dtype != k.dtype or q.device != k.device:
+        raise BackendError(f"attention_colsum expects q and k of one (B, T, H*D) shape, dtype and device; got {tuple(q.shape)} and {tuple(k.shape)}")
+    B, T, Cc = q.shape
+    if Cc % num_heads:
+        raise BackendError(f"attention_colsum: C = {Cc} does not divide into {num_heads} heads")
+    rows = B if rows is None else int(rows)
+    if not 0 <= rows <= B:
+        raise BackendError(f"attention_colsum: rows {rows} outside [0, B = {B}]")
+    if out is None:
+        out = torch.zeros((B, T), dtype=torch.float32, device=q.device)
+    elif out.shape != (B, T) or out.dtype != torch.float32 or out.device != q.device or not out.is_contiguous():
+        raise BackendError(f"attention_colsum: out must be a contiguous fp32 (B, T) = ({B}, {T}) tensor on {q.device}")
+    if rows == 0:
+        return out
+
+    def tok(t):
+        return t.stride(2) == 1 and t.stride(0) == t.stride(1) * T and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
+
+    if not (q.device.type == "cuda" and q.dtype in (torch.bfloat16, torch.float16) and Cc // num_heads == 64 and tok(q) and tok(k)):
+        from .sag import colsum_reference
+        out[:rows].copy_(colsum_reference(q[:rows], k[:rows], num_heads, scale))
+        return out
+    if workspace is None:
+        workspace = attention_colsum_workspace(rows, T, num_heads, q.device)
+    _C.require_device(workspace)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise BackendError("attention_colsum: workspace must be a contiguous fp32 tensor (attention_colsum_workspace)")
+    _C.check(_C.load().st_attention_colsum(q.data_ptr(), k.data_ptr(), out.data_ptr(), rows, T, num_heads, 64, q.stride(1), k.stride(1),
+                                           float(scale), workspace.data_ptr(), workspace.numel(), _C.dtype_code(q.dtype), _C.stream_ptr()),
+             "attention_colsum")
+    return out
+
+
+def sag_degrade(latent: torch.Tensor, eps_neg: torch.Tensor, amap: torch.Tensor, grid_hw, sigmas: torch.Tensor, in_scale: torch.Tensor,
+                step: torch.Tensor, params: torch.Tensor, out: torch.Tensor, mask: torch.Tensor) -> None:
+    """The input of self-attention guidance's second UNet call, one launch (sag.py, csrc/sag.hip): latent (B, 4, lh, lw) fp32 and
+    eps_neg / out (B, 4, lh, lw) of the model dtype, all channels_last; amap (B, th * tw) fp32, `attention_colsum` of the site on its
+    `grid_hw` = (th, tw) token grid; i = *step: x0 = latent - sigmas[i] eps_neg; mask = amap (nearest-upsampled) > params[0]; out =
+    ((mask ? nine-tap Gaussian blur of x0 at sigma params[1], reflect-padded : x0) + sigmas[i] eps_neg) * in_scale[i]; `mask`
+    (B, lh, lw) fp32 receives the 1 / 0 map that was used.  `params` is a device row of two floats read when the kernel runs."""
+    _C.require_device(latent, eps_neg, amap, sigmas, in_scale, step, params, out, mask)
+    if latent.dim() != 4 or latent.shape[1] != 4 or latent.dtype != torch.float32:
+        raise BackendError(f"sag_degrade: latent must be fp32 (B, 4, lh, lw), got {latent.dtype} {tuple(latent.shape)}")
+    B, _, lh, lw = latent.shape
+    th, tw = int(grid_hw[0]), int(grid_hw[1])
+    if eps_neg.shape != latent.shape or out.shape != latent.shape or eps_neg.dtype != out.dtype:
+        raise BackendError(f"sag_degrade: eps_neg and out must be {tuple(latent.shape)} of one dtype; got {tuple(eps_neg.shape)} {eps_neg.dtype} "
+                           f"and {tuple(out.shape)} {out.dtype}")
+    nhwc = (4 * lh * lw, 1, 4 * lw, 4)
+    if any(t.stride() != nhwc for t in (latent, eps_neg, out)):
+        raise BackendError("sag_degrade: latent, eps_neg and out must be dense channels_last tensors")
+    if lh <= 4 or lw <= 4 or not (0 < th <= lh and 0 < tw <= lw):
+        raise BackendError(f"sag_degrade: a latent of {lh} x {lw} (sides above 4) with a map grid of {th} x {tw} (no larger than the latent)")
+    if amap.dtype != torch.float32 or amap.numel() != B * th * tw or not amap.is_contiguous():
+        raise BackendError(f"sag_degrade: amap must be a contiguous fp32 (B, th * tw) = ({B}, {th * tw}) tensor, got {tuple(amap.shape)}")
+    if mask.dtype != torch.float32 or tuple(mask.shape) != (B, lh, lw) or not mask.is_contiguous():
+        raise BackendError(f"sag_degrade: mask must be a contiguous fp32 (B, lh, lw) = ({B}, {lh}, {lw}) tensor")
+    n = in_scale.numel()
+    for name, t, count in (("sigmas", sigmas, n), ("in_scale", in_scale, n), ("params", params, 2)):
+        if t.dtype != torch.float32 or t.numel() != count or not t.is_contiguous():
+            raise BackendError(f"sag_degrade: {name} must be a contiguous fp32 table of {count} values")
+    if step.dtype != torch.int32:
+        raise BackendError("sag_degrade: step must be int32")
+    _C.check(_C.load().st_sag_degrade(latent.data_ptr(), eps_neg.data_ptr(), amap.data_ptr(), sigmas.data_ptr(), in_scale.data_ptr(),
+                                      step.data_ptr(), params.data_ptr(), out.data_ptr(), mask.data_ptr(), B, lh, lw, th, tw, n,
+                                      _C.dtype_code(out.dtype), _C.stream_ptr()), "sag_degrade")
+
+
+def _sag_step_checks(what: str, latent, eps, e_sag, next_in, history, in_scale, guidance, rescale, sag, step, start, tables):
+    """The checks the three SAG updates share; returns (latent batch, n_steps)."""
+    if latent.dtype != torch.float32 or not (eps.dtype == next_in.dtype == e_sag.dtype) or (history is not None and history.dtype != torch.float32):
+        raise BackendError(f"{what}: latent (and history) must be fp32 and eps / e_sag / next_in share a dtype")
+    if not (latent.is_contiguous() or latent.is_contiguous(memory_format=torch.channels_last)):
+        raise BackendError(f"{what}: latent must be dense (contiguous or channels_last)")
+    b = latent.shape[0]
+    if history is not None and history.shape != latent.shape:
+        raise BackendError(f"{what}: history must match the latent {tuple(latent.shape)}; got {tuple(history.shape)}")
+    if eps.shape != next_in.shape or eps.shape[0] != 2 * b or eps.shape[1:] != latent.shape[1:] or e_sag.shape != latent.shape:
+        raise BackendError(f"{what}: eps and next_in must be (2B, ...) [negative | positive] = {(2 * b, *latent.shape[1:])} and e_sag "
+                           f"{tuple(latent.shape)}; got {tuple(eps.shape)}, {tuple(next_in.shape)} and {tuple(e_sag.shape)}")
+    strides = [latent.stride(), eps.stride(), next_in.stride(), e_sag.stride()] + ([history.stride()] if history is not None else [])
+    if any(st_ != strides[0] for st_ in strides):
+        raise BackendError(f"{what}: latent, history, eps, e_sag and next_in must share one dense layout")
+    n = in_scale.numel()
+    if guidance is None or sag is None:
+        raise BackendError(f"{what}: the guidance and sag tables are required (self-attention guidance needs classifier-free guidance)")
+    for name, t in (("in_scale", in_scale), ("guidance", guidance), ("rescale", rescale), ("sag", sag)) + tuple(tables):
+        if t is not None and (t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise BackendError(f"{what}: {name} must be a contiguous fp32 table of n_steps = {n} values")
+    if step.dtype != torch.int32 or (start is not None and start.dtype != torch.int32):
+        raise BackendError(f"{what}: step and start must be int32")
+    return b, n
+
+
+def sag_euler_step(latent: torch.Tensor, eps: torch.Tensor, e_sag: torch.Tensor, next_in: torch.Tensor, dsigma: torch.Tensor,
+                   in_scale: torch.Tensor, guidance: torch.Tensor, sag: torch.Tensor, step: torch.Tensor,
+                   rescale: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """cfg_euler_step with self-attention guidance's term: eps and next_in (2B, ...) rows [negative | positive], e_sag (B, ...) the
+    second UNet call's prediction; behind the guidance and its rescale, e = fma(sag[i], e_neg - e_sag, e).  sag[i] = 0 gives
+    cfg_euler_step's bits."""
+    _C.require_device(latent, eps, e_sag, next_in, dsigma, in_scale, guidance, sag, step, rescale, workspace)
+    b, n = _sag_step_checks("sag_euler_step", latent, eps, e_sag, next_in, None, in_scale, guidance, rescale, sag, step, None, (("dsigma", dsigma),))
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(_C.load().st_sag_euler_step(latent.data_ptr(), eps.data_ptr(), e_sag.data_ptr(), next_in.data_ptr(), dsigma.data_ptr(),
+                                         in_scale.data_ptr(), guidance.data_ptr(), _ptr(rescale), sag.data_ptr(), step.data_ptr(), b,
+                                         latent[0].numel(), n, _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()),
+             "sag_euler_step")
+
+
+def sag_dpmpp2m_step(latent: torch.Tensor, eps: torch.Tensor, e_sag: torch.Tensor, next_in: torch.Tensor, history: torch.Tensor,
+                     coef: torch.Tensor, in_scale: torch.Tensor, step: torch.Tensor, start: torch.Tensor, sag: torch.Tensor,
+                     guidance: torch.Tensor, rescale: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> None:
+    """dpmpp2m_step under guidance whose e carries sag_euler_step's term."""
+    _C.require_device(latent, eps, e_sag, next_in, history, coef, in_scale, step, start, sag, guidance, rescale, workspace)
+    b, n = _sag_step_checks("sag_dpmpp2m_step", latent, eps, e_sag, next_in, history, in_scale, guidance, rescale, sag, step, start, ())
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 4) or not coef.is_contiguous():
+        raise BackendError(f"sag_dpmpp2m_step: coef must be a contiguous fp32 (n_steps, 4) = ({n}, 4) table")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(_C.load().st_sag_dpmpp2m_step(latent.data_ptr(), eps.data_ptr(), e_sag.data_ptr(), next_in.data_ptr(), history.data_ptr(),
+                                           coef.data_ptr(), in_scale.data_ptr(), guidance.data_ptr(), _ptr(rescale), sag.data_ptr(),
+                                           step.data_ptr(), start.data_ptr(), b, latent[0].numel(), n, _C.dtype_code(eps.dtype),
+                                           _ptr(workspace), ws_bytes, _C.stream_ptr()), "sag_dpmpp2m_step")
+
+
+def sag_sde_step(latent: torch.Tensor, eps: torch.Tensor, e_sag: torch.Tensor, next_in: torch.Tensor, history: torch.Tensor,
+                 coef: torch.Tensor, in_scale: torch.Tensor, step: torch.Tensor, start: torch.Tensor, seeds: torch.Tensor,
+                 sag: torch.Tensor, guidance: torch.Tensor, rescale: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> None:
+    """sde_step under guidance whose e carries sag_euler_step's term; seeds stay one per latent sample."""
+    _C.require_device(latent, eps, e_sag, next_in, history, coef, in_scale, step, start, seeds, sag, guidance, rescale, workspace)
+    b, n = _sag_step_checks("sag_sde_step", latent, eps, e_sag, next_in, history, in_scale, guidance, rescale, sag, step, start, ())
+    if coef.dtype != torch.float32 or tuple(coef.shape) != (n, 5) or not coef.is_contiguous():
+        raise BackendError(f"sag_sde_step: coef must be a contiguous fp32 (n_steps, 5) = ({n}, 5) table")
+    _check_seeds(seeds, b, "sag_sde_step")
+    if rescale is not None and workspace is None:
+        workspace = cfg_workspace(latent)
+    ws_bytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _C.check(_C.load().st_sag_sde_step(latent.data_ptr(), eps.data_ptr(), e_sag.data_ptr(), next_in.data_ptr(), history.data_ptr(),
+                                       coef.data_ptr(), in_scale.data_ptr(), guidance.data_ptr(), _ptr(rescale), sag.data_ptr(),
+                                       step.data_ptr(), start.data_ptr(), seeds.data_ptr(), b, latent[0].numel(), n,
+                                       _C.dtype_code(eps.dtype), _ptr(workspace), ws_bytes, _C.stream_ptr()), "sag_sde_step")
+
+
 def step_advance(step: torch.Tensor, n_steps: int) -> None:
     _C.require_device(step)
     _C.check(_C.load().st_step_advance(step.data_ptr(), n_steps, _C.stream_ptr()), "step_advance")

@@ -21,7 +21,7 @@ from . import t2i_adapter as _t2i
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_hypertile, insert_reference, insert_style_aligned, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_sag, insert_hypertile, insert_reference, insert_style_aligned, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
@@ -29,7 +29,7 @@ from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention,
 def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
                     ip_adapter=None, seg_layers=None, t2i_adapter: bool = False, controlnet: bool = False,
-                    reference_layers=None, hypertile_layers=None, style_aligned_layers=None) -> fx.GraphModule:
+                    reference_layers=None, hypertile_layers=None, style_aligned_layers=None, sag_layer=None) -> fx.GraphModule:
     """Pass pipeline over a traced module; an untraced nn.Module is traced here, after the flags were checked against each other
     (optimize_model relies on it: a bad combination raises before the trace).  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
@@ -61,9 +61,13 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     `style_aligned_layers` (addition, off by default, likewise): regular expressions selecting the self-attention sites whose batch
     entries renormalise their queries and keys to, and share the keys of, the first entry of their block (StyleAligned;
     optimizers/insert_style_aligned.py, style_aligned.py); the state, `gm.style_aligned`, starts with per 0 = ordinary attention; not
-    with `pag_layers`, `seg_layers`, `reference_layers` or `hypertile_layers` (a site carries one leaf)."""
+    with `pag_layers`, `seg_layers`, `reference_layers` or `hypertile_layers` (a site carries one leaf).  `sag_layer` (addition, off by
+    default, likewise): True - the middle block's first self-attention - or one regular expression selecting exactly ONE
+    self-attention site, which can also record the column sums of its softmax matrix for the leading rows of a call (self-attention
+    guidance; optimizers/insert_sag.py, sag.py); the state, `gm.sag`, starts with rows 0 = ordinary attention; not with `pag_layers`,
+    `seg_layers`, `reference_layers`, `style_aligned_layers`, `regions`, `ip_adapter`, `t2i_adapter`, `controlnet` or `fp8`."""
     check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet, reference_layers, hypertile_layers,
-                              style_aligned_layers)
+                              style_aligned_layers, sag_layer)
     if not isinstance(gm, fx.GraphModule):
         gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
@@ -83,6 +87,8 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
         stats["seg_sites"] = insert_seg(gm, seg_layers)
     if reference_layers is not None:      # likewise (never with either: check_feature_combination)
         stats["reference_sites"] = insert_reference(gm, reference_layers)
+    if sag_layer is not None:       # likewise, ahead of HyperTile: a site carries one leaf, and the windowed sites are the self-attentions left
+        stats["sag_sites"] = insert_sag(gm, sag_layer)
     if hypertile_layers is not None:      # likewise (never with any of the three: check_feature_combination)
         stats["hypertile_sites"] = insert_hypertile(gm, hypertile_layers)
     if style_aligned_layers is not None:      # likewise (never with any of the four: check_feature_combination)
@@ -120,8 +126,16 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
 
 
 def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet=False, reference_layers=None,
-                              hypertile_layers=None, style_aligned_layers=None) -> None:
+                              hypertile_layers=None, style_aligned_layers=None, sag_layer=None) -> None:
     """The compile flags that exclude each other."""
+    if sag_layer is not None:
+        for name, on in (("pag_layers", pag_layers is not None), ("seg_layers", seg_layers is not None),
+                         ("reference_layers", reference_layers is not None), ("style_aligned_layers", style_aligned_layers is not None),
+                         ("regions", regions is not None), ("ip_adapter", ip_adapter is not None), ("t2i_adapter", bool(t2i_adapter)),
+                         ("controlnet", bool(controlnet)), ("fp8", bool(fp8))):
+            if on:
+                raise ValueError(f"sag_layer cannot be combined with {name}: self-attention guidance runs a second UNet call per step on "
+                                 "other rows, and that feature's rows, buffers or scales are not verified with it")
     if style_aligned_layers is not None and any(v is not None for v in (pag_layers, seg_layers, reference_layers, hypertile_layers)):
         raise ValueError("style_aligned_layers cannot be combined with pag_layers, seg_layers, reference_layers or hypertile_layers: a "
                          "self-attention site carries one leaf")
@@ -147,8 +161,16 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
                    pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None,
                    t2i_adapter: bool = False, controlnet: bool = False, reference_layers=None, hypertile_layers=None,
-                   style_aligned_layers=None) -> fx.GraphModule:
-    """`style_aligned_layers=(".*",)` (addition): StyleAligned (style_aligned.py).  The selected self-attention sites can cut the batch
+                   style_aligned_layers=None, sag_layer=None) -> fx.GraphModule:
+    """`sag_layer=True` (addition): self-attention guidance (sag.py).  One self-attention site - True: the first `attn1` of the middle
+    block; a string: a regular expression that must select exactly one `attn1` - can also record, for the leading `rows` batch entries
+    of a call, the column sums of its softmax matrix averaged over the heads (three launches behind the unchanged attention launch,
+    csrc/attention_colsum.hip; the matrix is never stored).  `gm.sag.using(rows, latent_hw)` around the caller's own calls; rows 0, the
+    initial state, is ordinary attention.  `DenoiseLoop(sag_scale=...)` runs the guidance; `sag.degrade` serves a caller's own loop.
+    With `cuda_graph=True` the module's own cached graphs never record (DenoiseLoop captures its own over a `cuda_graph=False`
+    module).  Not with `pag_layers`, `seg_layers`, `reference_layers`, `style_aligned_layers`, `regions`, `ip_adapter`, `t2i_adapter`,
+    `controlnet` or `fp8`.
+    `style_aligned_layers=(".*",)` (addition): StyleAligned (style_aligned.py).  The selected self-attention sites can cut the batch
     of a call into blocks of `per` entries whose first entry is the style row: every other entry's queries and keys are renormalised
     to the style row's per-channel statistics over the tokens (two launches in place on the fused projection buffer,
     csrc/style_adain.hip) and it attends to its own tokens and to the style row's under one softmax (one launch,
@@ -222,7 +244,7 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     gm = replace_backend(model, fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
                          region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
                          controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
-                         style_aligned_layers=style_aligned_layers)
+                         style_aligned_layers=style_aligned_layers, sag_layer=sag_layer)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

@@ -17,6 +17,7 @@ from .insert_t2i_adapter import insert_t2i_adapter
 from .insert_controlnet import insert_controlnet
 from .insert_pag import insert_pag
 from .insert_seg import insert_seg
+from .insert_sag import insert_sag
 from .insert_reference import insert_reference
 from .insert_hypertile import insert_hypertile
 from .insert_style_aligned import insert_style_aligned

@@ -130,6 +130,17 @@ are in-place writes, before or after `capture()`; the table starts all 0.  While
 captured graph is the plain loop's; a change between "no step on" and "some step on" drops the graph for one new capture.  Not with `pag_scale`, `seg_scale`, `tile_hw`,
 `reference=True`, or UNets compiled with `regions`, `ip_adapter`, `t2i_adapter`, `controlnet`.  Parity with either published
 implementation is unpinned; shared normalisation statistics, score scale / shift and full attention sharing are out of scope.
+
+Self-attention guidance (`sag_scale`, `sag_sigma`, `sag_threshold`, `set_sag`; sag.py) on a UNet compiled with `sag_layer`,
+under `guidance_scale`: a step makes TWO UNet calls.  The ordinary one on [negative | positive], unchanged, during which the site also
+records the negative rows' attention map (three launches); one launch, `st_sag_degrade`, that blurs the predicted clean latent where
+the map exceeds the threshold and writes a second static input of B rows; the UNet on those rows under the negative conditioning -
+with its own hoisted text K/V and time tables of B rows, derived in place beside the 2B set -; and the `st_sag_*` form of the loop's
+sampler, which adds sag[i] (e_neg - e_sag) behind the guidance and its rescale.  Both calls sit in one step scope: the weight plan sees
+one repeating sequence.  The scale is a device table of n_steps floats, sigma and threshold a device row: `set_sag` needs no new
+capture.  Scale 0 keeps the second call and gives the bits of the loop without `sag_scale`.  Every sampler, `inpaint=True`, LoRA, FreeU
+and HyperTile work as before.  Not with `pag_scale`, `seg_scale`, `tile_hw`, `reference=True`, `style_aligned=True` or a nine-channel
+inpainting UNet; parity with either published implementation is unpinned.
 """
 from __future__ import annotations
 
@@ -157,8 +168,21 @@ class DenoiseLoop:
                  pag_scale: Optional[Union[float, Sequence[float]]] = None,
                  seg_scale: Optional[Union[float, Sequence[float]]] = None, seg_sigma: float = float("inf"),
                  tile_hw=None, tile_stride=None, tile_wrap_w: bool = False, tile_weights="uniform", controlnet: Optional[Callable] = None,
-                 inpaint: bool = False, reference: bool = False, style_aligned: bool = False):
+                 inpaint: bool = False, reference: bool = False, style_aligned: bool = False,
+                 sag_scale: Optional[Union[float, Sequence[float]]] = None, sag_sigma: float = 2.0, sag_threshold: float = 1.0):
         assert mode in ("loop", "step", "eager")
+        # self-attention guidance: the UNet's site must exist; the step's second call runs on B rows of its own
+        self._sag = None
+        if sag_scale is not None:
+            from . import sag as _sag
+            if guidance_scale is None:
+                raise ValueError("DenoiseLoop: sag_scale needs guidance_scale (self-attention guidance degrades the negative prediction)")
+            for name, on in (("pag_scale", pag_scale is not None), ("seg_scale", seg_scale is not None), ("tile_hw", tile_hw is not None),
+                             ("reference=True", reference), ("style_aligned=True", style_aligned)):
+                if on:
+                    raise ValueError(f"DenoiseLoop: sag_scale cannot be combined with {name}")
+            self._sag = _sag.state_of(unet, "DenoiseLoop(sag_scale=...)")
+            _sag.check_params(sag_sigma, sag_threshold)
         if seg_scale is not None and pag_scale is not None:
             raise ValueError("seg_scale cannot be combined with pag_scale: both claim the perturbed row block of the UNet batch")
         if guidance_rescale is not None and guidance_scale is None:
@@ -254,6 +278,9 @@ class DenoiseLoop:
             if reference:
                 raise ValueError("DenoiseLoop: reference=True cannot be combined with a nine-channel inpainting UNet: a reference row "
                                  "has no mask and no masked image")
+            if self._sag is not None:
+                raise ValueError("DenoiseLoop: sag_scale cannot be combined with a nine-channel inpainting UNet: its condition is bound "
+                                 "for one row count, and the step's second call has another")
         # guidance: the UNet sees [negative | positive]; with pag_scale one more block, [.. | perturbed]
         canvas_rows = batch * ((2 if guidance_scale is not None else 1) + (1 if pag_scale is not None else 0) + (1 if reference else 0))
         self._lead_rows = canvas_rows - (batch if reference else 0)      # the row blocks the sampler update reads and writes
@@ -358,6 +385,15 @@ class DenoiseLoop:
             self.style_aligned_table = torch.zeros(n, dtype=torch.float32, device=dev)
             if dev.type == "cuda":
                 self._style.bind(rows, (lh, lw), dev)
+        # self-attention guidance: the per-step scale and sigma tables, the second call's static input (B rows) and - filled by
+        # _rederive_conditioning - its hoisted text K/V and time tables; read by address, allocated once, outside capture
+        self.sag = self.sigma = self.x_sag = self.ctx_sag = self.time_tables_sag = None
+        if self._sag is not None:
+            self.sag = torch.zeros(n, dtype=torch.float32, device=dev)
+            self.sag.copy_(self._step_table(sag_scale, "scale", "set_sag"))
+            self.sigma = torch.tensor(self.tables.sigmas[:n], dtype=torch.float32, device=dev)
+            self.x_sag = torch.zeros((batch, 4, lh, lw), dtype=dtype, device=dev).contiguous(memory_format=cl)
+            self._sag.set_params(sag_sigma, sag_threshold)
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self._captured_steps = 0
         # text-context projections are step-invariant: evaluated once per prompt when the compiled
@@ -414,6 +450,22 @@ class DenoiseLoop:
             self._perturbed.set_sigma(sigma)
         if table is not None:
             self.pag.copy_(table)
+
+    def set_sag(self, scale: Optional[Union[float, Sequence[float]]] = None, sigma: Optional[float] = None,
+                threshold: Optional[float] = None) -> None:
+        """Self-attention guidance: the scale per step (a float, or n_steps floats), the blur's sigma and / or the attention map's
+        threshold.  All in-place writes of device buffers the captured graph reads by address: no new capture; validated before
+        anything is written.  Scale 0 keeps the second UNet call and gives the value the loop computes without it.  sigma and
+        threshold belong to the UNet's SAG state: loops that share one compiled UNet share them."""
+        if self._sag is None:
+            raise ValueError("set_sag: this loop was built without sag_scale")
+        from . import sag as _sag
+        table = self._step_table(scale, "scale", "set_sag") if scale is not None else None
+        _sag.check_params(self._sag.sigma if sigma is None else sigma, self._sag.threshold if threshold is None else threshold)
+        if sigma is not None or threshold is not None:
+            self._sag.set_params(sigma, threshold)
+        if table is not None:
+            self.sag.copy_(table)
 
     def set_conditioning(self, encoder_hidden_states, text_embeds, time_ids, negative_encoder_hidden_states=None,
                          negative_text_embeds=None, negative_time_ids=None) -> None:
@@ -638,6 +690,30 @@ class DenoiseLoop:
             else:
                 for dst, src in zip(self.time_tables, new):
                     dst.copy_(src)
+        if self._sag is not None:
+            self._rederive_sag_conditioning()
+
+    def _rederive_sag_conditioning(self) -> None:
+        """The second call's set, from the NEGATIVE rows of the same static buffers (views: nothing is copied), in place."""
+        B, n = self.batch, self.n_steps
+        with torch.no_grad():
+            if self._split:
+                new = self.unet.precompute_context(self.ehs[:B])
+                if self.ctx_sag is None:
+                    self.ctx_sag = tuple(t.clone() for t in new)
+                else:
+                    for dst, src in zip(self.ctx_sag, new):
+                        dst.copy_(src)
+            if self._tsplit:
+                rows = self.x_in.new_empty((n * B, 1, 1, 1))
+                cond = {"text_embeds": self.text_embeds[:B].repeat(n, 1), "time_ids": self.time_ids[:B].repeat(n, 1)}
+                out = self.unet.precompute_time(rows, self.timesteps.repeat_interleave(B), cond)
+                new = tuple(o.reshape(n, B, *o.shape[1:]) for o in out)
+                if self.time_tables_sag is None:
+                    self.time_tables_sag = tuple(t.clone() for t in new)
+                else:
+                    for dst, src in zip(self.time_tables_sag, new):
+                        dst.copy_(src)
 
     def refresh_weights(self) -> int:
         """Captured graphs read derived weight buffers (fused q|k|v, LayerNorm-folded projections) by address: after an
@@ -943,8 +1019,10 @@ class DenoiseLoop:
     def _cond(self) -> Dict[str, torch.Tensor]:
         return {"text_embeds": self.text_embeds, "time_ids": self.time_ids}
 
-    def _unet(self, t, time_row=None, step=None):
+    def _unet(self, t, time_row=None, step=None, second: bool = False):
         with contextlib.ExitStack() as scopes:      # both for this loop's own calls only
+            if self._sag is not None:            # the 2B call records the negative rows' attention map; the second call records nothing
+                scopes.enter_context(self._sag.using(0 if second else self.batch, self._latent_hw))
             if self._sites is not None:          # the residual sites read this loop's scale table at `step`
                 lent = ()
                 if self.controlnet is not None:  # the branch on the UNet's own rows, then its outputs lent to the sites (no copies)
@@ -962,38 +1040,59 @@ class DenoiseLoop:
                 scopes.enter_context(self._hypertile.using(self._latent_hw, self.step_ids[0:1] if step is None else step))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
                 scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
-            return self._unet_call(t, time_row)
+            return self._unet_call(t, time_row, second)
 
-    def _unet_call(self, t, time_row=None):
+    def _unet_call(self, t, time_row=None, second: bool = False):
+        B = self.batch
+        # (the second call of a self-attention guidance step: its own input, the negative rows of the conditioning - views - and their set)
+        x, ehs, ctx = (self.x_sag, self.ehs[:B], self.ctx_sag) if second else (self.x_in, self.ehs, self.ctx)
+        cond = {"text_embeds": self.text_embeds[:B], "time_ids": self.time_ids[:B]} if second else self._cond()
         if self._split:
-            if self.ctx is None:
+            if ctx is None:
                 raise RuntimeError("set_conditioning() must be called before running the loop")
             if self._tsplit:
-                return self.unet.forward_with_context(self.x_in, t, self.ctx, self._cond(), time_cache=time_row)[0]
-            return self.unet.forward_with_context(self.x_in, t, self.ctx, self._cond())[0]
-        return self.unet(self.x_in, t, self.ehs, self._cond())[0]
+                return self.unet.forward_with_context(x, t, ctx, cond, time_cache=time_row)[0]
+            return self.unet.forward_with_context(x, t, ctx, cond)[0]
+        return self.unet(x, t, ehs, cond)[0]
+
+    def _evaluate(self, t, rows, step: torch.Tensor):
+        """The step's UNet work: (eps, e_sag).  `rows` = the time-table rows of the 2B call and of the second call.  Without
+        self-attention guidance one call and e_sag None; with it the 2B call, the degrade launch and the second call, inside ONE step
+        scope of the UNet's context so that the weight plan sees one repeating sequence of launches."""
+        if self._sag is None:
+            return self._unet(t, rows[0], step), None
+        ectx = getattr(self.unet, "exec_context", None)
+        with (ectx.step() if ectx is not None else contextlib.nullcontext()):
+            eps = self._unet(t, rows[0], step)
+            b = self._sag.bound(self.batch, self._latent_hw, self.device)
+            ops.sag_degrade(self.latent, eps[:self.batch], b.A, b.grid, self.sigma, self.in_scale, step, self._sag.params(self.device),
+                            self.x_sag, b.mask)
+            return eps, self._unet(t, rows[1], step, second=True)
+
+    def _time_rows(self, pick):
+        """(the 2B call's time-table row, the second call's), each None where there is no table; pick(table) selects the step."""
+        return tuple(None if tables is None or not self._tsplit else tuple(pick(tbl) for tbl in tables)
+                     for tables in (self.time_tables, self.time_tables_sag))
 
     def _step_const(self, i: int) -> None:
-        row = tuple(tbl[i] for tbl in self.time_tables) if self._tsplit else None      # static views: no launch
-        eps = self._unet(self.timesteps[i], row, self.step_ids[i:i + 1])
-        self._update(eps, self.step_ids[i:i + 1])
+        eps, e_sag = self._evaluate(self.timesteps[i], self._time_rows(lambda tbl: tbl[i]), self.step_ids[i:i + 1])      # static views: no launch
+        self._update(eps, self.step_ids[i:i + 1], e_sag)
 
     def _step_counted(self) -> None:
         idx = self.step.long()
         t = self.timesteps.index_select(0, idx)[0]
-        row = tuple(tbl.index_select(0, idx)[0] for tbl in self.time_tables) if self._tsplit else None
-        eps = self._unet(t, row, self.step)
-        self._update(eps, self.step)
+        eps, e_sag = self._evaluate(t, self._time_rows(lambda tbl: tbl.index_select(0, idx)[0]), self.step)
+        self._update(eps, self.step, e_sag)
         ops.step_advance(self.step, self.n_steps)
 
-    def _update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
+    def _update(self, eps: torch.Tensor, step: torch.Tensor, e_sag: Optional[torch.Tensor] = None) -> None:
         if self.tile_grid is not None:                     # the windows' predictions -> one prediction per canvas pixel
             g = self.tile_grid
             ops.tile_blend(eps, self.eps_canvas, self.tile_weights, g.ys, g.xs, g.wrap_w)
             eps = self.eps_canvas
         if self._reference is not None:                    # the sampler sees the leading row blocks (views): its kernels are unchanged
             eps = eps[:self._lead_rows]
-        self._sampler_update(eps, step)
+        self._sampler_update(eps, step, e_sag)
         if self.inpaint_mask is not None:                  # behind the update, on what it wrote: pixels to repaint are not touched
             ops.inpaint_blend(self.latent, self._x_lead, self.inpaint_init, self.inpaint_noise, self.inpaint_mask, self.sigma_next,
                               self.in_scale, step, self.inpaint_thr)
@@ -1007,8 +1106,18 @@ class DenoiseLoop:
         """What the update kernels write: `x_step`, without the reference block when there is one."""
         return self.x_step if self._reference is None else self.x_step[:self._lead_rows]
 
-    def _sampler_update(self, eps: torch.Tensor, step: torch.Tensor) -> None:
-        if self.pag is not None:
+    def _sampler_update(self, eps: torch.Tensor, step: torch.Tensor, e_sag: Optional[torch.Tensor] = None) -> None:
+        if e_sag is not None:
+            if isinstance(self.tables, SDETables):
+                ops.sag_sde_step(self.latent, eps, e_sag, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
+                                 self.sag, self.guidance, self.rescale, self.cfg_workspace)
+            elif self.coef is not None:
+                ops.sag_dpmpp2m_step(self.latent, eps, e_sag, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.sag,
+                                     self.guidance, self.rescale, self.cfg_workspace)
+            else:
+                ops.sag_euler_step(self.latent, eps, e_sag, self._x_lead, self.dsigma, self.in_scale, self.guidance, self.sag, step,
+                                   self.rescale, self.cfg_workspace)
+        elif self.pag is not None:
             if isinstance(self.tables, SDETables):
                 ops.pag_sde_step(self.latent, eps, self._x_lead, self.history, self.coef, self.in_scale, step, self.start, self.seeds,
                                  self.pag, self.guidance, self.rescale, self.cfg_workspace)
