@@ -761,6 +761,40 @@ int st_inpaint_blend(float* latent, void* next_in, const float* init, const floa
 int st_conv_stem(const void* a, long a_px, long a_img, int Na, int C0, const void* b, long b_px, long b_img, int Nb, int C1,
                  const void* w, const void* bias, void* out, int N, int H, int W, int Cout, int epi, int dtype, void* stream);
 
+/* ---- Token merging (ToMe for Stable Diffusion, Bolya & Hoffman 2023; no reference counterpart).  Added after ABI 18 without a bump: new
+ * entry points, no existing signature or contract changed.
+ *
+ * A site has N = h * w tokens on a row-major h x w grid, both sides even: D = N / 4 cells of 2 x 2 tokens, cell c = cy * (w / 2) + cx.
+ * `off` is a DEVICE table of n_steps rows of D bytes; the row read is clamp(*step, 0, n_steps - 1), row 0 when step is null; only the two
+ * low bits of a byte count.  The cell's dst token is (2 cy + (off >> 1)) * w + 2 cx + (off & 1); its src tokens are s = 3 c + k, k = 0..2,
+ * at slot k + (k >= off[c]) of the cell by the same formula.  S = 3 D.  x is (B, N, C) of `dtype` (ST_BF16 / ST_F16), token stride ldx
+ * values, batch stride N * ldx; C a multiple of 64, at most 2048.  S <= ST_TOME_MAX_SRC (select and merge_norm keep S words in LDS).
+ *
+ * st_tome_match: node_max[b][s] = max over j < D of <x_s, x_j> / (|x_s| |x_j|) (norms clamped below at 1e-12), node_idx[b][s] the
+ *   smallest j that attains it; both (B, S).  16-bit MFMA products, fp32 accumulation and fp32 sums of squares; the score matrix is
+ *   never stored.
+ * st_tome_select: rank[s] = #{t: node_max[t] > node_max[s]} + #{t < s: node_max[t] == node_max[s]}; src s is merged iff rank < r
+ *   (0 <= r <= S; a NaN node_max counts as -inf, so the ranks are a permutation for any input).  where (B, N): dst j -> j, merged src -> node_idx[s], kept src -> D + rank - r.  assign (B, S): node_idx[s] or -1.
+ *   kept (B, S): kept[b][rank - r] = s for the S - r kept src (the rest is not written).
+ * st_tome_merge_norm: y (B, N - r, C) dense.  Row m < D = (LN(x_dst m) + sum of LN(x_s) over the s with assign[s] == m, ascending s)
+ *   / (1 + their number); row m >= D = LN(x_s), s = kept[m - D].  LN is LayerNorm over C with gamma, beta (C values of `dtype`) and eps,
+ *   statistics and sums in fp32, one rounding.
+ * st_tome_unmerge_add: out[b][t] = x[b][t] + y[b][where[b][t]] for t < N, y (B, R, C) dense, out (B, N, C) dense, one rounding; stats,
+ *   when not null, takes (B * N) float2 (sum, sum of squares) of the stored rows: the LayerNorm partials st_ln_linear reads as one chunk.
+ * Indices read from node_idx, kept and where are clamped to their ranges before use.  No atomics: two launches give the same bits.
+ * Rejected before any launch: null pointers (step, stats excepted), a type other than the two 16-bit ones, odd or empty grids, C no
+ * multiple of 64 or past 2048, S past ST_TOME_MAX_SRC, r outside 0..S, R outside 1..N, misaligned pointers or strides (csrc/tome.hip). */
+#define ST_TOME_MAX_SRC 12288
+int st_tome_match(const void* x, long ldx, const unsigned char* off, const int* step, int n_steps, int B, int h, int w, int C,
+                  float* node_max, int* node_idx, int dtype, void* stream);
+int st_tome_select(const float* node_max, const int* node_idx, const unsigned char* off, const int* step, int n_steps, int B, int h,
+                   int w, int r, int* where, int* assign, int* kept, void* stream);
+int st_tome_merge_norm(const void* x, long ldx, const void* gamma, const void* beta, float eps, const unsigned char* off,
+                       const int* step, int n_steps, const int* assign, const int* kept, int B, int h, int w, int C, int r, void* y,
+                       int dtype, void* stream);
+int st_tome_unmerge_add(const void* x, long ldx, const void* y, const int* where, int B, int N, int R, int C, void* out, float* stats,
+                        int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

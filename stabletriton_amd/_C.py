@@ -87,6 +87,10 @@ SIGNATURES = {
     "st_tile_blend": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _i, _i, _p]),
     "st_inpaint_blend": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _i, _i, _p]),
     "st_conv_stem": (_i, [_p, _l, _l, _i, _i, _p, _l, _l, _i, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "st_tome_match": (_i, [_p, _l, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "st_tome_select": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "st_tome_merge_norm": (_i, [_p, _l, _p, _p, _f, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p]),
+    "st_tome_unmerge_add": (_i, [_p, _l, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p]),
 }
 
 

@@ -136,6 +136,12 @@ class _HoistedUNet(nn.Module):
             if self._hypertile_step is None:
                 raise RuntimeError("hypertile: run one call outside the capture first (the wrapper's call counter is allocated there)")
             return tiles.using(latent_hw, self._hypertile_step)
+        from . import tome
+        merge = compiled_state(self.compiled, "tome", tome.ToMe)
+        if merge is not None:      # the same call counter: a module has one of the two
+            if self._hypertile_step is None:
+                raise RuntimeError("tome: run one call outside the capture first (the wrapper's call counter is allocated there)")
+            return merge.using(latent_hw, self._hypertile_step)
         ref = compiled_state(self.compiled, "reference", reference.ReferenceRows)
         if ref is not None:
             return ref.using(chunks)
@@ -220,8 +226,8 @@ class _HoistedUNet(nn.Module):
     def _apply_hypertile(self, sample: torch.Tensor) -> None:
         """This call's draw: the wrapper's counter on this call's device (allocated outside any capture; the sites only read it),
         written before the launch.  The state's tables hold HYPERTILE_DRAWS rows unless a DenoiseLoop bound them first."""
-        from . import hypertile
-        state = compiled_state(self.compiled, "hypertile", hypertile.HyperTile)
+        from . import hypertile, tome
+        state = compiled_state(self.compiled, "hypertile", hypertile.HyperTile) or compiled_state(self.compiled, "tome", tome.ToMe)
         if state is None or torch.cuda.is_current_stream_capturing():
             return
         if state.n_steps == 0:
@@ -232,6 +238,24 @@ class _HoistedUNet(nn.Module):
         self._hypertile_step = self._hypertile_steps[key]
         self._hypertile_step.fill_(self._hypertile_calls % state.n_steps)
         self._hypertile_calls += 1
+
+    # ---- token merging (tome.py): per-grid device offset tables read at the same call counter; the captured graphs stay ----------
+    def enable_tome(self, seed: int = 0) -> None:
+        """The self-attention sites compiled in with `tome_layers` draw which token of every 2 x 2 cell is dst from (seed, token grid):
+        HYPERTILE_DRAWS table rows, call i after this one reads row i % HYPERTILE_DRAWS of the wrapper's own call counter, as
+        `enable_hypertile` counts.  Written in place: no graph is captured again.  A wrapper compiled with the sites always merges (the
+        ratio is compile-time); before this call, and after `disable_tome()`, every cell's dst is its first token.  Raises on a
+        wrapper compiled without `tome_layers`."""
+        from . import tome
+        self._set_tome(tome.state_of(self.compiled, "enable_tome"), seed)
+
+    def disable_tome(self) -> None:
+        from . import tome
+        self._set_tome(tome.state_of(self.compiled, "disable_tome"), None)
+
+    def _set_tome(self, state, seed) -> None:
+        state.set(seed)
+        self._hypertile_calls = 0
 
     # ---- smoothed energy guidance (seg.py): which rows of a call take blurred queries; sigma is a device row, written in place ----
     def enable_seg(self, chunks: int, sigma: float = float("inf")) -> None:
@@ -589,7 +613,7 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
                                  cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                                  region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
                                  controlnet: bool = False, reference_layers=None, hypertile_layers=None,
-                                 style_aligned_layers=None) -> DiffusersUNet:
+                                 style_aligned_layers=None, tome_layers=None, tome_ratio: float = 0.5) -> DiffusersUNet:
     """Build the UNet, load a Diffusers-keyed state_dict (any float dtype), compile, wrap for the pipeline.
     `dtype` None = the state_dict's own dtype (fp16 for the reference's `variant="fp16"` checkpoint).
     `freeu=True` compiles the FreeU sites in: `enable_freeu(s1, s2, b1, b2)` / `disable_freeu()` then work as on diffusers' UNet.
@@ -611,7 +635,9 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     `hypertile_layers=(".*",)` compiles the windowed self-attention sites in (hypertile.py; not with `pag_layers` / `seg_layers` /
     `reference_layers`): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()` drive them.
     `style_aligned_layers=(".*",)` compiles the StyleAligned sites in (style_aligned.py; not with any of the four before):
-    `enable_style_aligned(chunks)` / `disable_style_aligned()` then say how a call's rows divide into blocks led by a style row."""
+    `enable_style_aligned(chunks)` / `disable_style_aligned()` then say how a call's rows divide into blocks led by a style row.
+    `tome_layers=("down_blocks.1|up_blocks.1",)` compiles the token-merging sites in at the compile-time `tome_ratio` (tome.py; not
+    with any other flag of this list): `enable_tome(seed)` / `disable_tome()` draw or clear the per-call dst offsets."""
     if dtype is None:
         dtype = next(iter(state_dict.values())).dtype
     with torch.device("meta"):
@@ -620,20 +646,22 @@ def compile_unet_from_state_dict(state_dict, spec: UNetSpec = SDXL_BASE, dtype=N
     model.load_state_dict({k: v.to(device=device, dtype=dtype) for k, v in state_dict.items()})
     compiled = optimize_model(model, cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
                               ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
-                              reference_layers=reference_layers, hypertile_layers=hypertile_layers, style_aligned_layers=style_aligned_layers)
+                              reference_layers=reference_layers, hypertile_layers=hypertile_layers, style_aligned_layers=style_aligned_layers,
+                              tome_layers=tome_layers, tome_ratio=tome_ratio)
     return DiffusersUNet(compiled, spec, dtype, cuda_graph)
 
 
 def attach_to_diffusers(pipe, spec: UNetSpec = SDXL_BASE, dtype=None, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                         regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                        controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None):
+                        controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None, tome_layers=None,
+                        tome_ratio: float = 0.5):
     """`pipe.unet = compiled UNet` (same weights; the counterpart of load_sdxl_pipeline.py:24-35), returns the pipeline.
     `dtype` None = the pipeline's own UNet dtype (fp16 at the reference call site): no casts at the boundary."""
     device = next(pipe.unet.parameters()).device
     pipe.unet = compile_unet_from_state_dict(pipe.unet.state_dict(), spec, dtype, device, cuda_graph, freeu=freeu, pag_layers=pag_layers,
                                              regions=regions, region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers,
                                              t2i_adapter=t2i_adapter, controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
-                                             style_aligned_layers=style_aligned_layers)
+                                             style_aligned_layers=style_aligned_layers, tome_layers=tome_layers, tome_ratio=tome_ratio)
     return pipe
 
 
@@ -663,7 +691,8 @@ class ComfyUNet(_HoistedUNet):
 
 def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None, regions=None,
                        region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                       controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None) -> ComfyUNet:
+                       controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None, tome_layers=None,
+                       tome_ratio: float = 0.5) -> ComfyUNet:
     """Compile the `y`-vector entry of a UNet (weights shared with `unet`).  `freeu=True`: with FreeU sites, driven by
     `enable_freeu(s1, s2, b1, b2, version=2)` (the FreeU_V2 node) or version 1 (the FreeU node).  `pag_layers=("mid",)`: with
     perturbed-attention sites; the PerturbedAttentionGuidance node's extra, fully perturbed call is `enable_pag(1)`.  `regions=R`:
@@ -679,21 +708,24 @@ def compile_comfy_unet(unet: UNet2DConditionModel, cuda_graph: bool = True, free
     [generated | reference] latents is `enable_reference(2)`).  `hypertile_layers=(".*",)`: with windowed self-attention sites (the
     HyperTile node): `enable_hypertile(tile, swap, seed)` / `disable_hypertile()`.  `style_aligned_layers=(".*",)`: with StyleAligned
     sites (the StyleAligned Batch Align node with share_attn q+k, share_norm disabled): `enable_style_aligned(chunks)` - 1 for a
-    cond-only call, 2 for [uncond | cond] - / `disable_style_aligned()`."""
+    cond-only call, 2 for [uncond | cond] - / `disable_style_aligned()`.  `tome_layers=(...)`, `tome_ratio`: with token-merging sites (the
+    TomePatchModel node): `enable_tome(seed)` / `disable_tome()`."""
     dtype = next(unet.parameters()).dtype
     compiled = optimize_model(UNetWithLabelVector(unet), cuda_graph=False, freeu=freeu, pag_layers=pag_layers, regions=regions,
                               region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
                               controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
-                              style_aligned_layers=style_aligned_layers)
+                              style_aligned_layers=style_aligned_layers, tome_layers=tome_layers, tome_ratio=tome_ratio)
     return ComfyUNet(compiled, dtype, cuda_graph)
 
 
 def patch_comfy_model(model_patcher, unet: UNet2DConditionModel, cuda_graph: bool = True, freeu: bool = False, pag_layers=None,
                       regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None, t2i_adapter: bool = False,
-                      controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None) -> ComfyUNet:
+                      controlnet: bool = False, reference_layers=None, hypertile_layers=None, style_aligned_layers=None, tome_layers=None,
+                      tome_ratio: float = 0.5) -> ComfyUNet:
     """Replace `model_patcher.model.diffusion_model` (duck-typed ComfyUI ModelPatcher) with the compiled UNet."""
     adapter = compile_comfy_unet(unet, cuda_graph, freeu=freeu, pag_layers=pag_layers, regions=regions, region_tokens=region_tokens,
                                  ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter, controlnet=controlnet,
-                                 reference_layers=reference_layers, hypertile_layers=hypertile_layers, style_aligned_layers=style_aligned_layers)
+                                 reference_layers=reference_layers, hypertile_layers=hypertile_layers, style_aligned_layers=style_aligned_layers,
+                                 tome_layers=tome_layers, tome_ratio=tome_ratio)
     model_patcher.model.diffusion_model = adapter
     return adapter

@@ -2594,3 +2594,96 @@ def inpaint_blend(latent: torch.Tensor, next_in: torch.Tensor, init: torch.Tenso
     _C.check(_C.load().st_inpaint_blend(latent.data_ptr(), next_in.data_ptr(), init.data_ptr(), noise.data_ptr(), mask.data_ptr(), _ptr(thr),
                                         sigma_next.data_ptr(), in_scale.data_ptr(), step.data_ptr(), B, next_in.shape[0] // B, H * W, Cc,
                                         mask.shape[0], n, _C.dtype_code(next_in.dtype), _C.stream_ptr()), "inpaint_blend")
+
+
+# ----------------------------------------------------------------------------- token merging (ToMe): match, select, merge, unmerge
+TOME_MAX_SRC = 12288      # ST_TOME_MAX_SRC: src tokens of a site (3/4 of its tokens) whose rank and member tables fit LDS
+TOME_MAX_C = 2048         # widest row a wave of st_tome_merge_norm keeps in registers
+
+
+def _tome_site(what: str, x: torch.Tensor, grid_hw, off: torch.Tensor, step: Optional[torch.Tensor]):
+    """(B, h, w, C, row stride) of a site's (B, N, C) tensor after the checks the four launches share."""
+    _C.require_device(x, off, step)
+    h, w = int(grid_hw[0]), int(grid_hw[1])
+    if x.dim() != 3 or x.shape[1] != h * w:
+        raise BackendError(f"{what}: x must be (B, {h} * {w}, C), got {tuple(x.shape)}")
+    if x.stride(2) != 1 or x.stride(0) != x.stride(1) * x.shape[1]:
+        raise BackendError(f"{what}: x must have unit channel stride and dense batch entries")
+    if off.dtype != torch.uint8 or off.dim() != 2 or off.shape[1] * 4 != h * w or off.shape[0] < 1 or not off.is_contiguous():
+        raise BackendError(f"{what}: off must be a contiguous uint8 table (n_steps, {h * w // 4}), got {off.dtype} {tuple(off.shape)}")
+    if step is not None and (step.dtype != torch.int32 or step.numel() != 1):
+        raise BackendError(f"{what}: step must be an int32 tensor of one entry")
+    return x.shape[0], h, w, x.shape[2], x.stride(1)
+
+
+def tome_match(x: torch.Tensor, grid_hw, off: torch.Tensor, step: Optional[torch.Tensor] = None):
+    """The bipartite match of token merging (tome.py, csrc/tome.hip): x (B, N, C) bf16 / fp16 on the row-major `grid_hw` token grid,
+    `off` the uint8 device table (n_steps, N / 4) of dst slots read at `step` (int32, one entry; None: row 0).  Returns node_max
+    (B, S) fp32 - every src token's largest cosine to a dst token - and node_idx (B, S) int32, the smallest dst that attains it."""
+    B, h, w, Cc, ld = _tome_site("tome_match", x, grid_hw, off, step)
+    S = h * w // 4 * 3
+    node_max = torch.empty((B, S), dtype=torch.float32, device=x.device)
+    node_idx = torch.empty((B, S), dtype=torch.int32, device=x.device)
+    _C.check(_C.load().st_tome_match(x.data_ptr(), ld, off.data_ptr(), _ptr(step), off.shape[0], B, h, w, Cc, node_max.data_ptr(),
+                                     node_idx.data_ptr(), _C.dtype_code(x.dtype), _C.stream_ptr()), "tome_match")
+    return node_max, node_idx
+
+
+def tome_select(node_max: torch.Tensor, node_idx: torch.Tensor, grid_hw, r: int, off: torch.Tensor, step: Optional[torch.Tensor] = None):
+    """Rank the src tokens by node_max (descending, ties to the smaller index) and merge the first r.  Returns where (B, N) int32 - the
+    row of the merged (B, N - r, C) tensor every token reads back -, assign (B, S) int32 (the dst a src merges into, or -1) and kept
+    (B, S) int32 whose first S - r entries are the kept src in rank order."""
+    _C.require_device(node_max, node_idx, off, step)
+    h, w = int(grid_hw[0]), int(grid_hw[1])
+    S = h * w // 4 * 3
+    if node_max.dtype != torch.float32 or node_idx.dtype != torch.int32 or node_max.dim() != 2 or node_max.shape != node_idx.shape \
+            or node_max.shape[1] != S or not node_max.is_contiguous() or not node_idx.is_contiguous():
+        raise BackendError(f"tome_select: node_max fp32 and node_idx int32, both contiguous (B, {S}), expected")
+    if off.dtype != torch.uint8 or off.dim() != 2 or off.shape[1] * 3 != S or not off.is_contiguous():
+        raise BackendError(f"tome_select: off must be a contiguous uint8 table (n_steps, {S // 3})")
+    B = node_max.shape[0]
+    where = torch.empty((B, h * w), dtype=torch.int32, device=node_max.device)
+    assign = torch.empty((B, S), dtype=torch.int32, device=node_max.device)
+    kept = torch.empty((B, S), dtype=torch.int32, device=node_max.device)
+    _C.check(_C.load().st_tome_select(node_max.data_ptr(), node_idx.data_ptr(), off.data_ptr(), _ptr(step), off.shape[0], B, h, w, int(r),
+                                      where.data_ptr(), assign.data_ptr(), kept.data_ptr(), _C.stream_ptr()), "tome_select")
+    return where, assign, kept
+
+
+def tome_merge_norm(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, grid_hw, r: int, assign: torch.Tensor,
+                    kept: torch.Tensor, off: torch.Tensor, step: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, N - r, C): row m < N / 4 the mean of LayerNorm(x) over dst token m and the src merged into it, the later rows the LayerNorm
+    of the kept src in rank order (`assign`, `kept`: tome_select's)."""
+    B, h, w, Cc, ld = _tome_site("tome_merge_norm", x, grid_hw, off, step)
+    _C.require_device(weight, bias, assign, kept)
+    S = h * w // 4 * 3
+    for t in (assign, kept):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, S) or not t.is_contiguous():
+            raise BackendError(f"tome_merge_norm: assign and kept must be contiguous int32 ({B}, {S})")
+    if weight.numel() != Cc or bias.numel() != Cc:
+        raise BackendError("tome_merge_norm: only normalisation over the last dimension is supported")
+    wt = weight if weight.dtype == x.dtype else weight.to(x.dtype)
+    bs = bias if bias.dtype == x.dtype else bias.to(x.dtype)
+    y = torch.empty((B, h * w - int(r), Cc), dtype=x.dtype, device=x.device)
+    _C.check(_C.load().st_tome_merge_norm(x.data_ptr(), ld, wt.data_ptr(), bs.data_ptr(), float(eps), off.data_ptr(), _ptr(step), off.shape[0],
+                                          assign.data_ptr(), kept.data_ptr(), B, h, w, Cc, int(r), y.data_ptr(), _C.dtype_code(x.dtype),
+                                          _C.stream_ptr()), "tome_merge_norm")
+    return y
+
+
+def tome_unmerge_add(x: torch.Tensor, y: torch.Tensor, where: torch.Tensor, emit_stats: bool = False):
+    """x + y[where]: x (B, N, C), y (B, R, C), where (B, N) int32 rows of y.  With emit_stats the launch also writes the LayerNorm
+    partials of its output rows and the call returns (out, RowStats) as `linear(..., emit_stats=True)` does."""
+    _C.require_device(x, y, where)
+    if x.dim() != 3 or y.dim() != 3 or y.shape[0] != x.shape[0] or y.shape[2] != x.shape[2] or y.dtype != x.dtype or not y.is_contiguous():
+        raise BackendError(f"tome_unmerge_add: x (B, N, C) and a contiguous y (B, R, C) of one dtype expected, got {tuple(x.shape)} {tuple(y.shape)}")
+    if x.stride(2) != 1 or x.stride(0) != x.stride(1) * x.shape[1]:
+        raise BackendError("tome_unmerge_add: x must have unit channel stride and dense batch entries")
+    B, N, Cc = x.shape
+    if where.dtype != torch.int32 or tuple(where.shape) != (B, N) or not where.is_contiguous():
+        raise BackendError(f"tome_unmerge_add: where must be a contiguous int32 ({B}, {N})")
+    out = torch.empty((B, N, Cc), dtype=x.dtype, device=x.device)
+    stats = torch.empty((B * N, 1, 2), dtype=torch.float32, device=x.device) if emit_stats else None
+    _C.check(_C.load().st_tome_unmerge_add(x.data_ptr(), x.stride(1), y.data_ptr(), where.data_ptr(), B, N, y.shape[1], Cc, out.data_ptr(),
+                                           _ptr(stats), _C.dtype_code(x.dtype), _C.stream_ptr()), "tome_unmerge_add")
+    return (out, RowStats(stats, 1)) if emit_stats else out

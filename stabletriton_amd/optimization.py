@@ -21,7 +21,7 @@ from . import t2i_adapter as _t2i
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
-                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_sag, insert_hypertile, insert_reference, insert_style_aligned, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
+                         fuse_temb_add, fuse_timesteps, insert_controlnet, insert_freeu, insert_t2i_adapter, insert_ip_adapter, insert_pag, insert_sag, insert_hypertile, insert_reference, insert_style_aligned, insert_tome, insert_regions, insert_seg, split_context, split_region, keep_channels_last, make_dynamic_graphed_callable, plan_fp8, remove_dropout,
                          replace_conv, replace_group_norm, replace_group_norm_activation, replace_layer_norm,
                          replace_linear, replace_linear_activ)
 
@@ -29,7 +29,8 @@ from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention,
 def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8: bool = False, xattn_fusion: bool = True,
                     gn_stats: bool = True, freeu: bool = False, pag_layers=None, regions=None, region_tokens: int = 77,
                     ip_adapter=None, seg_layers=None, t2i_adapter: bool = False, controlnet: bool = False,
-                    reference_layers=None, hypertile_layers=None, style_aligned_layers=None, sag_layer=None) -> fx.GraphModule:
+                    reference_layers=None, hypertile_layers=None, style_aligned_layers=None, sag_layer=None, tome_layers=None,
+                    tome_ratio: float = 0.5) -> fx.GraphModule:
     """Pass pipeline over a traced module; an untraced nn.Module is traced here, after the flags were checked against each other
     (optimize_model relies on it: a bad combination raises before the trace).  The first eight passes and their order are the reference's
     (optimization.py:10-22); replace_linear is enabled (the MFMA GEMM is the
@@ -65,9 +66,13 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     default, likewise): True - the middle block's first self-attention - or one regular expression selecting exactly ONE
     self-attention site, which can also record the column sums of its softmax matrix for the leading rows of a call (self-attention
     guidance; optimizers/insert_sag.py, sag.py); the state, `gm.sag`, starts with rows 0 = ordinary attention; not with `pag_layers`,
-    `seg_layers`, `reference_layers`, `style_aligned_layers`, `regions`, `ip_adapter`, `t2i_adapter`, `controlnet` or `fp8`."""
+    `seg_layers`, `reference_layers`, `style_aligned_layers`, `regions`, `ip_adapter`, `t2i_adapter`, `controlnet` or `fp8`.
+    `tome_layers` (addition, off by default, likewise): regular expressions selecting the self-attention sites whose first half - norm1,
+    the q|k|v projection, the attention, to_out - runs on merged tokens at the compile-time `tome_ratio` (token merging;
+    optimizers/insert_tome.py, tome.py); the state, `gm.tome`, is the unmerged chain outside its `using`; not with any other flag
+    that is off by default (`freeu` included): none of those combinations is tested."""
     check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet, reference_layers, hypertile_layers,
-                              style_aligned_layers, sag_layer)
+                              style_aligned_layers, sag_layer, tome_layers, freeu, tome_ratio)
     if not isinstance(gm, fx.GraphModule):
         gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
@@ -81,6 +86,8 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     if fuse:
         stats["deduped_activations"] = dedupe_pure_calls(gm)
     stats["attention"] = fuse_attention(gm)
+    if tome_layers is not None:     # directly after: norm1, the projections and to_out are still module calls with their paths
+        stats["tome_sites"] = insert_tome(gm, tome_layers, tome_ratio)      # (never with another site pass: check_feature_combination)
     if pag_layers is not None:      # directly after: the query projections still carry their module paths
         stats["pag_sites"] = insert_pag(gm, pag_layers)
     if seg_layers is not None:      # likewise (never both: check_feature_combination)
@@ -126,8 +133,20 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
 
 
 def check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet=False, reference_layers=None,
-                              hypertile_layers=None, style_aligned_layers=None, sag_layer=None) -> None:
+                              hypertile_layers=None, style_aligned_layers=None, sag_layer=None, tome_layers=None, freeu=False,
+                              tome_ratio: float = 0.5) -> None:
     """The compile flags that exclude each other."""
+    if tome_layers is not None:
+        from .tome import check_ratio
+        check_ratio(tome_ratio)
+        for name, on in (("pag_layers", pag_layers is not None), ("seg_layers", seg_layers is not None),
+                         ("reference_layers", reference_layers is not None), ("hypertile_layers", hypertile_layers is not None),
+                         ("style_aligned_layers", style_aligned_layers is not None), ("sag_layer", sag_layer is not None),
+                         ("fp8", bool(fp8)), ("regions", regions is not None), ("ip_adapter", ip_adapter is not None),
+                         ("t2i_adapter", bool(t2i_adapter)), ("controlnet", bool(controlnet)), ("freeu", bool(freeu))):
+            if on:
+                raise ValueError(f"tome_layers cannot be combined with {name}: a token-merging site changes its token count between norm1 "
+                                 "and the residual add, and that feature's leaves, buffers or plan are not verified on such a site")
     if sag_layer is not None:
         for name, on in (("pag_layers", pag_layers is not None), ("seg_layers", seg_layers is not None),
                          ("reference_layers", reference_layers is not None), ("style_aligned_layers", style_aligned_layers is not None),
@@ -161,8 +180,18 @@ def run_compiler(gm: fx.GraphModule) -> fx.GraphModule:
 def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True, fp8: bool = False, freeu: bool = False,
                    pag_layers=None, regions=None, region_tokens: int = 77, ip_adapter=None, seg_layers=None,
                    t2i_adapter: bool = False, controlnet: bool = False, reference_layers=None, hypertile_layers=None,
-                   style_aligned_layers=None, sag_layer=None) -> fx.GraphModule:
-    """`sag_layer=True` (addition): self-attention guidance (sag.py).  One self-attention site - True: the first `attn1` of the middle
+                   style_aligned_layers=None, sag_layer=None, tome_layers=None, tome_ratio: float = 0.5) -> fx.GraphModule:
+    """`tome_layers=("down_blocks.1|up_blocks.1",)` (addition; that entry is the method's default on SDXL, the highest-resolution
+    attention level): token merging (tome.py).  In the selected self-attention sites r = int(N * tome_ratio) of the N tokens (rounded
+    so that N - r is a multiple of 32) are merged into their most similar dst token of a 2 x 2 cell partition before norm1 and restored
+    behind to_out: four launches (csrc/tome.hip: an MFMA cosine match with a row arg-max epilogue, a counting rank, a merge fused with
+    norm1, an unmerge fused with the residual add) around the q|k|v projection, attention and to_out, which run on N - r rows.
+    `tome_ratio` is fixed at compile time (a captured graph's shapes are static); which token of a cell is dst comes per step from
+    device tables: `gm.tome.bind(n_steps)`, `set(seed)` / `set(None)` in place, no new capture, and `using(latent_hw, step)` around
+    the caller's own calls; outside `using`, in fp32, on odd token grids and past the kernels' caps a site is the unmerged chain (so
+    with `cuda_graph=True` the module's own cached graphs never merge: DenoiseLoop captures its own over a `cuda_graph=False` module).
+    Not with any other flag of this list.
+    `sag_layer=True` (addition): self-attention guidance (sag.py).  One self-attention site - True: the first `attn1` of the middle
     block; a string: a regular expression that must select exactly one `attn1` - can also record, for the leading `rows` batch entries
     of a call, the column sums of its softmax matrix averaged over the heads (three launches behind the unchanged attention launch,
     csrc/attention_colsum.hip; the matrix is never stored).  `gm.sag.using(rows, latent_hw)` around the caller's own calls; rows 0, the
@@ -244,7 +273,7 @@ def optimize_model(model: nn.Module, cuda_graph: bool = True, fuse: bool = True,
     gm = replace_backend(model, fuse=fuse, fp8=fp8, freeu=freeu, pag_layers=pag_layers, regions=regions,
                          region_tokens=region_tokens, ip_adapter=ip_adapter, seg_layers=seg_layers, t2i_adapter=t2i_adapter,
                          controlnet=controlnet, reference_layers=reference_layers, hypertile_layers=hypertile_layers,
-                         style_aligned_layers=style_aligned_layers, sag_layer=sag_layer)
+                         style_aligned_layers=style_aligned_layers, sag_layer=sag_layer, tome_layers=tome_layers, tome_ratio=tome_ratio)
     # the compiled module owns its mutable host state (split-K workspace, next-weights plan, derived weight buffers):
     # two compiled modules, or two streams each driving their own, never share any (ops.ExecContext)
     gm.exec_context = ops.ExecContext()

@@ -21,6 +21,7 @@ from .insert_sag import insert_sag
 from .insert_reference import insert_reference
 from .insert_hypertile import insert_hypertile
 from .insert_style_aligned import insert_style_aligned
+from .insert_tome import insert_tome
 from .insert_regions import insert_regions
 from .insert_ip_adapter import insert_ip_adapter
 from .cleanup import dedupe_pure_calls, fuse_token_residual

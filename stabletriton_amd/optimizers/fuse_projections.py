@@ -60,6 +60,7 @@ def fuse_layernorm_into_linear(gm: fx.GraphModule) -> int:
     concatenated / GEGLU projection disappears: the producing GEMM also emits per-row (sum, sum of
     squares) partials of what it stores, gamma is folded into the consumer's weights and the
     consumer applies mean/rstd as a rank-1 correction in its epilogue (`ln_linear_wrapper`)."""
+    from ..tome import tome_unmerge_wrapper
     from .wrappers import linear_residual_wrapper
     count = 0
     for ln in list(gm.graph.nodes):
@@ -83,7 +84,8 @@ def fuse_layernorm_into_linear(gm: fx.GraphModule) -> int:
         mods = [gm.get_submodule(a.target) for a in linears]
         if any(m.in_features != kdim for m in mods) or kdim % 64 != 0:
             continue
-        # the producer of the LayerNorm input must be one of our GEMMs (it will emit the partials)
+        # the producer of the LayerNorm input must be one of our GEMMs (it will emit the partials), or a token-merging site's
+        # unmerge launch, which writes them beside its residual add
         prod = ln.args[0]
         if not (isinstance(prod, fx.Node) and prod.op == "call_function"):
             continue
@@ -91,11 +93,14 @@ def fuse_layernorm_into_linear(gm: fx.GraphModule) -> int:
             pass
         elif prod.target is linear_residual_wrapper and len(prod.args) == 3:
             pass
+        elif prod.target is tome_unmerge_wrapper and len(prod.args) == 3:
+            pass
         else:
             continue
-        pmod = gm.get_submodule(prod.args[1].target)
-        if pmod.in_features % 64 != 0 or pmod.out_features != kdim:
-            continue
+        if prod.target is not tome_unmerge_wrapper:
+            pmod = gm.get_submodule(prod.args[1].target)
+            if pmod.in_features % 64 != 0 or pmod.out_features != kdim:
+                continue
         prod.args = tuple(prod.args) + (True,)            # emit_stats
         with gm.graph.inserting_after(prod):
             st = gm.graph.call_function(operator.getitem, (prod, 1))

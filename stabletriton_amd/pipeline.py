@@ -234,6 +234,10 @@ class DenoiseLoop:
         # tables start all (1, 1) = the bits of ordinary attention (set_hypertile)
         from . import hypertile as _hypertile
         self._hypertile = compiled_state(unet, "hypertile", _hypertile.HyperTile)
+        # token merging: a UNet compiled with tome_layers merges at its sites under this loop's latent size and step counter; the
+        # per-grid offset tables start all 0 (set_tome)
+        from . import tome as _tome
+        self._tome = compiled_state(unet, "tome", _tome.ToMe)
         # regional prompts: the sites are part of the compiled UNet, the text context carries its R prompts side by side
         self._regions_state = compiled_state(unet, "regions", _regions.Regions)
         if self._regions_state is not None and tokens != self._regions_state.R * self._regions_state.seg_len:
@@ -378,6 +382,8 @@ class DenoiseLoop:
                 self.sigma_next = torch.tensor(self.tables.sigmas[1:], dtype=torch.float32, device=dev)
         if self._hypertile is not None:
             self._hypertile.bind(n)
+        if self._tome is not None:
+            self._tome.bind(n)
         # StyleAligned: the sites' per-step gate (all 0 = off: ordinary attention, q / k untouched) and their AdaIN scratch; read by
         # address, allocated once, outside capture
         self.style_aligned_table, self._style_live = None, False      # (live: some step of the table is on; a host value)
@@ -662,6 +668,15 @@ class DenoiseLoop:
             raise ValueError("set_hypertile: this loop's UNet was compiled without windowed self-attention sites: compile it with "
                              'hypertile_layers=(".*",)')
         self._hypertile.set(tile, swap, seed, start, end)
+
+    def set_tome(self, seed: Optional[int] = 0) -> None:
+        """Token merging (tome.py) on a UNet compiled with `tome_layers`: which token of every 2 x 2 cell is the dst token is drawn per
+        step and token grid from a generator seeded with (seed, grid); `set_tome(None)`: always the cell's first token.  Written into
+        the device tables in place, before or after `capture()`: no new capture.  (The ratio is the UNet's compile-time `tome_ratio`.)"""
+        if self._tome is None:
+            raise ValueError("set_tome: this loop's UNet was compiled without token-merging self-attention sites: compile it with "
+                             'tome_layers=("down_blocks.1|up_blocks.1",)')
+        self._tome.set(seed)
 
     def _rederive_conditioning(self) -> None:
         """Everything the loop computes once per prompt from the weights and its own static `ehs`, `text_embeds` and
@@ -1038,6 +1053,8 @@ class DenoiseLoop:
                                                        table=self.style_aligned_table))
             if self._hypertile is not None:      # the sites derive their token grids from the latent size and read their tables at `step`
                 scopes.enter_context(self._hypertile.using(self._latent_hw, self.step_ids[0:1] if step is None else step))
+            if self._tome is not None:           # likewise: the sites merge on the grids of this latent size, their offsets read at `step`
+                scopes.enter_context(self._tome.using(self._latent_hw, self.step_ids[0:1] if step is None else step))
             if self._perturbed is not None:      # the last B rows are the perturbed block; SEG's sites derive their token grids from the latent size
                 scopes.enter_context(self._perturbed.using(self._perturbed_chunks, self._latent_hw))
             return self._unet_call(t, time_row, second)
