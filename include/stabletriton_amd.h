@@ -176,7 +176,8 @@ int st_ln_linear_xattn(const void* x, const float* row_stats, int row_stats_chun
  * keep the (B, T, H*D) / (B, S, H*D) projection layout of unet_pt.py:133-142.
  * ld* are token strides in elements (>= H*D), batch strides are T*ldq etc.
  * D (head_dim) in {16, 32, 64, 128}, the reference operator's set (kernels/attention_fa2.py:118-123); 64 - every SDXL
- * head - runs on the tuned kernels, the other three on one generic kernel (csrc/attention_anyd.hip). */
+ * head - runs on the tuned kernels, the other three on one generic kernel (csrc/attention_anyd.hip).  D = 512 (the one
+ * head of the SDXL VAE decoder's middle block) is taken too, in ST_BF16 and ST_F16 only (csrc/attention_d512.hip). */
 int st_attention(const void* q, const void* k, const void* v, void* out,
                  int B, int T, int S, int H, int D,
                  long ldq, long ldk, long ldv, long ldo,

@@ -18,6 +18,7 @@ from torch import fx, nn
 from . import _C, ops
 from . import controlnet as _controlnet
 from . import t2i_adapter as _t2i
+from . import vae as _vae
 from .ip_adapter import check_combination
 from .optimizers import (dedupe_pure_calls, fuse_token_residual, fuse_attention, fuse_geglu, fuse_geglu_into_linear, fuse_groupnorm_stats, fuse_skip_cat, fuse_layernorm_into_linear, fuse_query_projection_into_attention, fuse_residual_adds,
                          fuse_shared_input_linears,
@@ -74,6 +75,8 @@ def replace_backend(gm: Union[fx.GraphModule, nn.Module], fuse: bool = True, fp8
     check_feature_combination(fp8, regions, ip_adapter, pag_layers, seg_layers, t2i_adapter, controlnet, reference_layers, hypertile_layers,
                               style_aligned_layers, sag_layer, tome_layers, freeu, tome_ratio)
     if not isinstance(gm, fx.GraphModule):
+        if isinstance(gm, _vae.DecoderXL):      # the VAE decoder: conv_out with zero filters up to Cout % 4 == 0, sliced away in forward
+            gm = gm.kernel_form()
         gm = fx.symbolic_trace(gm)
     stats: Dict[str, int] = {}
     if t2i_adapter:      # first of all: module paths are readable, and FreeU's sites then read skips that carry the residual

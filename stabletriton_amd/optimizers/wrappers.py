@@ -30,6 +30,12 @@ def attention_wrapper(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, output:
     exactly as in the reference."""
     if q.shape[-1] != num_heads * head_dim:
         raise ops.BackendError(f"attention_wrapper: C={q.shape[-1]} != num_heads*head_dim={num_heads * head_dim}")
+    if head_dim == 512 and q.dtype == torch.float32:
+        # the VAE decoder's one head in the strict mode: st_attention takes head_dim 512 in bf16 / fp16 only (csrc/attention_d512.hip),
+        # and this one site is plain torch
+        qh, kh, vh = (t.reshape(t.shape[0], t.shape[1], num_heads, head_dim).transpose(1, 2) for t in (q, k, v))
+        w = torch.softmax(torch.matmul(qh, kh.transpose(-2, -1)) * sm_scale, dim=-1)
+        return torch.matmul(w, vh).transpose(1, 2).reshape(q.shape)
     return ops.attention(q, k, v, num_heads, sm_scale)
 
 

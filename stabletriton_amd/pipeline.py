@@ -1220,3 +1220,9 @@ class DenoiseLoop:
         self.set_noise(latent_unit, seed)
         self.run_steps(self.n_steps)
         return self.latent.contiguous(memory_format=torch.contiguous_format).clone()
+
+    @staticmethod
+    def decode(latent: torch.Tensor, vae, scaling_factor: float = 0.13025) -> torch.Tensor:
+        """`denoise`'s latent -> (B, 3, 8h, 8w) image through a `vae.DecoderXL` (compiled by optimize_model, or eager): vae.decode."""
+        from .vae import decode
+        return decode(vae, latent, scaling_factor)

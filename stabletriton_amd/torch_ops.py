@@ -19,7 +19,7 @@ import torch
 from . import ops
 
 _lib = torch.library.Library("st", "DEF")
-_lib.define("attention(Tensor q, Tensor k, Tensor v, int num_heads, float scale, int head_dim=64) -> Tensor")      # head_dim: 16 / 32 / 64 / 128 (st_attention)
+_lib.define("attention(Tensor q, Tensor k, Tensor v, int num_heads, float scale, int head_dim=64) -> Tensor")      # head_dim: 16 / 32 / 64 / 128 / 512 (st_attention)
 _lib.define("group_norm_silu(Tensor x, int num_groups, Tensor weight, Tensor bias, float eps, bool silu) -> Tensor")
 _lib.define("geglu(Tensor state, Tensor gate) -> Tensor")
 _lib.define("linear_act(Tensor x, Tensor weight, Tensor? bias, bool silu, bool geglu=False, Tensor? residual=None) -> Tensor")
@@ -29,7 +29,7 @@ _lib.define("layer_norm(Tensor x, Tensor weight, Tensor bias, float eps) -> Tens
 
 
 # ---- HIP kernels: the C-ABI launchers --------------------------------------------------------------
-ATTENTION_HEAD_DIMS = (16, 32, 64, 128)      # what st_attention takes (include/stabletriton_amd.h; kernels/attention_fa2.py:118-123)
+ATTENTION_HEAD_DIMS = (16, 32, 64, 128, 512)      # what st_attention takes (include/stabletriton_amd.h; 512: 16-bit tensors only, the VAE decoder's head)
 
 
 def _check_attention(q, k, v, num_heads, head_dim):
