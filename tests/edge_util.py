@@ -1,6 +1,6 @@
 """Helpers of the edge tests (tests/test_edge_gate_host.py, tests/test_edges_gpu.py, tests/test_dma_gate_host.py,
 tests/test_dma_edges_gpu.py, tests/test_conv_gate_host.py, tests/test_conv_edges_gpu.py, tests/test_fp8_gate_host.py,
-tests/test_fp8_edges_gpu.py): a per-element float64 gate with a derived
+tests/test_fp8_edges_gpu.py, tests/test_norm_gate_host.py, tests/test_norm_edges_gpu.py): a per-element float64 gate with a derived
 budget, NaN-poisoned operands, guarded outputs, and C-ABI callers that write into an output the test owns."""
 import math
 
@@ -552,6 +552,45 @@ def geglu_into(out, state, gate):
     assert state.stride(1) == 1 and gate.stride(1) == 1 and out.is_contiguous() and tuple(out.shape) == (rows, Fh)
     _C.check(_C.load().st_geglu(state.data_ptr(), gate.data_ptr(), out.data_ptr(), rows, Fh, state.stride(0), gate.stride(0), Fh,
                                 _C.dtype_code(state.dtype), _C.stream_ptr()), "geglu")
+    return out
+
+
+def _gn_stats_args(part0, C0, rows0, part1, C1, rows1):
+    for p in (part0, part1):
+        assert p is None or (p.dtype == torch.float32 and p.stride(-1) == 1 and p.is_contiguous())
+    return part0.data_ptr(), C0, rows0, (None if part1 is None else part1.data_ptr()), C1, rows1
+
+
+def group_norm_from_stats_into(out, x, groups, weight, bias, eps, silu, part0, C0, rows0, part1=None, C1=0, rows1=0):
+    """st_group_norm_from_stats of the channels_last x into the channels_last `out`; part0 / part1: the producers' partials as
+    plain fp32 tensors (N * HW / rows, C_source, 2) = (sum, sum of squares) per tile row and channel."""
+    _C, ops = _ops()
+    lib = _C.load()
+    N, Cc = x.shape[0], x.shape[1]
+    HW = x.numel() // (N * Cc)
+    cl = torch.channels_last
+    assert x.is_contiguous(memory_format=cl) and out.shape == x.shape and out.is_contiguous(memory_format=cl)
+    ws = torch.empty(lib.st_group_norm_workspace_bytes(N, Cc, HW, groups), dtype=torch.uint8, device=x.device)
+    _C.check(lib.st_group_norm_from_stats(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), N, Cc, HW, groups, float(eps),
+                                          int(bool(silu)), _C.dtype_code(x.dtype), *_gn_stats_args(part0, C0, rows0, part1, C1, rows1),
+                                          ws.data_ptr(), _C.stream_ptr()), "group_norm_from_stats")
+    return out
+
+
+def group_norm_from_stats_cat_into(out, x0, x1, groups, weight, bias, eps, silu, part0, C0, rows0, part1, C1, rows1):
+    """st_group_norm_from_stats_cat of the two channels_last tensors x0 | x1 (never concatenated) into the channels_last `out`."""
+    _C, ops = _ops()
+    lib = _C.load()
+    N, Cc = out.shape[0], out.shape[1]
+    HW = out.numel() // (N * Cc)
+    cl = torch.channels_last
+    assert x0.is_contiguous(memory_format=cl) and x1.is_contiguous(memory_format=cl) and out.is_contiguous(memory_format=cl)
+    assert x0.shape[0] == x1.shape[0] == N and x0.shape[2:] == x1.shape[2:] == out.shape[2:] and x0.dtype == x1.dtype == out.dtype
+    ws = torch.empty(lib.st_group_norm_workspace_bytes(N, Cc, HW, groups), dtype=torch.uint8, device=out.device)
+    _C.check(lib.st_group_norm_from_stats_cat(x0.data_ptr(), x1.data_ptr(), weight.data_ptr(), bias.data_ptr(), out.data_ptr(), N, Cc, HW,
+                                              groups, float(eps), int(bool(silu)), _C.dtype_code(out.dtype),
+                                              *_gn_stats_args(part0, C0, rows0, part1, C1, rows1), ws.data_ptr(), _C.stream_ptr()),
+             "group_norm_from_stats_cat")
     return out
 
 
@@ -1419,3 +1458,268 @@ def fp8_ln_reference(x_stored, q, scale, wq, ws, c, d, eps, geglu):
     ref, mag, extra = ln_linear_ref64(x_stored.float(), None, c, d, torch.bfloat16, eps, geglu=geglu,
                                       products=((xd @ wd.T) * unit, (xd.abs() @ wd.abs().T) * unit))
     return ref, mag, extra, fp8_n_terms(K, ln=True, act=geglu)
+
+
+# ------------------------------------------------------------------------------------------------ norms: geometry, references, budgets, cases
+# (tests/test_norm_gate_host.py proves the gate on a CPU emulation of csrc/norms.hip and measures the four constants below;
+#  tests/test_norm_edges_gpu.py applies it to st_group_norm, st_group_norm_from_stats(_cat), st_layer_norm and st_geglu)
+GN_THREADS, GN_MAX_BLOCKS = 1024, 256
+NORM_EPS = 1e-5
+
+
+def vec_of(dtype) -> int:
+    """Elements of a 16-byte vector (Elem<T>::VEC)."""
+    return 4 if dtype == torch.float32 else 8
+
+
+def gn_geometry_nhwc(dtype, C, HW):
+    """(VC, RP, NB, P) of gn_geom<T>: vectors per pixel, pixel rows a block covers per pass, blocks per image, pixels per block."""
+    VC = C // vec_of(dtype)
+    RP = max(GN_THREADS // VC, 1)
+    NB = min(_cdiv(HW, RP), GN_MAX_BLOCKS)
+    P = _cdiv(HW, NB)
+    return VC, RP, _cdiv(HW, P), P
+
+
+def gn_geometry_nchw(N, C, HW, G):
+    """(NB, chunk, bx) of gn_launch's NCHW branch: statistics blocks per group, elements per block, apply blocks per channel."""
+    total = (C // G) * HW
+    NB = min(_cdiv(total, 8192), GN_MAX_BLOCKS)
+    want = _cdiv(1024, N * G)
+    if NB > want and want >= 1:
+        NB = max(want, 1)
+    chunk = _cdiv(total, NB)
+    return _cdiv(total, chunk), chunk, max(_cdiv(HW, 256 * 4), 1)
+
+
+def ln_vectors(dtype, C):
+    """NV of ln_kernel<T, NV>: 16-byte vectors a lane holds."""
+    return _cdiv(C // vec_of(dtype), 64)
+
+
+def geglu_grid(dtype, rows, F):
+    """(nvec, grid) of geglu_launch: 16-byte vectors of the output, blocks of 256 threads (capped: threads then stride)."""
+    nvec = rows * (F // vec_of(dtype))
+    return nvec, min(_cdiv(nvec, 256), 4096)
+
+
+# What the kernels are documented to compute (csrc/norms.hip):
+#   three-launch GroupNorm   per block (mean_b, m2_b, cnt_b) with mean_b = S / cnt and m2_b = max(SS - S * mean_b, 0) from fp32
+#                            sums S, SS; gn_finalize Chan-merges the blocks (64 lanes fold, ordered butterfly);
+#                            rstd = rsqrtf(m2 / cnt + eps)
+#   from producer statistics fp32 (sum, sum of squares) partials added in double; mean, var = Q / n - mean^2 and
+#                            1 / sqrt(var + eps) in double, rounded once to fp32
+#   apply (both)             a = rstd * gamma;  y = (x - mean) * a + beta in fp32;  SiLU;  one rounding at the store
+#   LayerNorm                mean = sum / C, var = sum (x - mean)^2 / C (two passes over registers), rsqrtf;
+#                            y = (x - mean) * rstd * gamma + beta
+# With mu, rho the exact statistics of a group (row), m1 = mean |x|, q = mean x^2, var = q - mu^2, per element:
+#   d_mean   the fp32 sums and the merges: MEASURED on the emulation in units of U_ACC * m1 (GN_MEAN_ULPS, LNK_MEAN_ULPS)
+#   d_var    three-launch: SS - S * mean_b CANCELS inside every block - both terms are about cnt * q and each carries its own
+#            rounding, so the variance is off by a multiple of U_ACC * q, NOT of U_ACC * var: q / var times worse relative to
+#            the variance (65 times on the `offset` family, 1.2 on `normal`).  d_var = GN_VAR_ULPS * U_ACC * q + 2 |mu| d_mean.
+#            LayerNorm: a sum of C squared differences, no cancellation: LNK_VAR_ULPS * U_ACC * var + d_mean^2 (a mean that is
+#            off by e adds exactly e^2 to the mean squared difference).
+#            from statistics: every partial is a float64 sum rounded once to fp32, U_ACC |partial| each:
+#            d_mean = U_ACC * m1 + U_ACC |mu| (the fp32 store of the mean) <= 2 U_ACC m1, d_var = U_ACC * q + 2 |mu| d_mean;
+#            nothing is measured, nothing cancels beyond the partials' own rounding (the rest is double).
+#   d_rstd   rho * (d_var / (2 (var + eps)) + RSQRT_ULPS * U_ACC); the double 1 / sqrt rounds once: 1 ulp there
+#   element  rho |gamma| d_mean + d_rstd |x - mu| |gamma| joins the magnitude through as_magnitude(., 0); the three (LayerNorm:
+#            four) fp32 operations of the apply pass are among the EPI_OPS on (|x| + |mu|) rho |gamma| + |beta|; SiLU brings
+#            ACT_SLOPE and SILU_ABS_ERR (|pre-activation| < ACT_RANGE asserted); the store U_OUT |ref|.
+# The four measured constants (tests/test_norm_gate_host.py::test_measured_constants prints them over every case, type and
+# family of the GPU file and holds each to "covers the measured value, at most twice it"; never from GPU output):
+GN_MEAN_ULPS = 5.5        # measured 2.95: x 2, rounded down
+GN_VAR_ULPS = 8.5         # measured 4.29 (in units of U_ACC * q, beyond the mean's share)
+LNK_MEAN_ULPS = 4.0       # measured 2.13
+LNK_VAR_ULPS = 16.0       # measured 8.42 (in units of U_ACC * var: the longest lanes add 64 squares in a row)
+GN_COLS_MEAN_ULPS, GN_COLS_VAR_ULPS, GN_COLS_RSQRT_ULPS = 2.0, 1.0, 1.0      # derived above
+
+
+def gn_stat_bounds(xg64, eps, mean_ulps=None, var_ulps=None, rsqrt_ulps=RSQRT_ULPS):
+    """(mu, rho, d_mean, d_rstd) over the last axis of xg64 (one group's values each) for the three-launch kernels."""
+    mean_ulps = GN_MEAN_ULPS if mean_ulps is None else mean_ulps
+    var_ulps = GN_VAR_ULPS if var_ulps is None else var_ulps
+    mu, q, m1 = xg64.mean(-1), (xg64 * xg64).mean(-1), xg64.abs().mean(-1)
+    var = ((xg64 - mu[..., None]) ** 2).mean(-1)
+    rho = (var + eps).rsqrt()
+    d_mean = mean_ulps * U_ACC * m1
+    d_var = var_ulps * U_ACC * q + 2.0 * mu.abs() * d_mean
+    d_rstd = rho * (0.5 * d_var / (var + eps) + rsqrt_ulps * U_ACC)
+    return mu, rho, d_mean, d_rstd
+
+
+def _gn_ref64(x, gamma, beta, G, eps, dtype, silu, consts):
+    xd = r64(x, dtype)
+    N, C = xd.shape[:2]
+    tail = (1,) * (xd.dim() - 2)
+    per_channel = lambda t: t.repeat_interleave(C // G, 1).view(N, C, *tail)
+    mu, rho, d_mean, d_rstd = (per_channel(t) for t in gn_stat_bounds(xd.reshape(N, G, -1), eps, *consts))
+    gd, bd = r64(gamma, dtype).view(1, C, *tail), r64(beta, dtype).view(1, C, *tail)
+    pre = (xd - mu) * rho * gd + bd
+    mag = (xd.abs() + mu.abs()) * rho * gd.abs() + bd.abs()
+    mag = mag + as_magnitude(rho * gd.abs() * d_mean + d_rstd * (xd - mu).abs() * gd.abs(), 0)
+    return _epilogue64(pre, mag, 0, dtype, silu=silu)
+
+
+def group_norm_ref64(x, gamma, beta, G, eps, dtype, silu):
+    """(ref64, mag64, extra64) of st_group_norm (both layouts) on the rounded operands; x (N, C, ...): n_terms = 0 in the gate."""
+    return _gn_ref64(x, gamma, beta, G, eps, dtype, silu, (GN_MEAN_ULPS, GN_VAR_ULPS, RSQRT_ULPS))
+
+
+def group_norm_from_stats_ref64(x, gamma, beta, G, eps, dtype, silu):
+    """The same for st_group_norm_from_stats(_cat) where the partials are the float64 sums of the stored values rounded to
+    fp32 (gn_partials): the apply budget is the three-launch one, the statistics' bounds are the derived ones above."""
+    return _gn_ref64(x, gamma, beta, G, eps, dtype, silu, (GN_COLS_MEAN_ULPS, GN_COLS_VAR_ULPS, GN_COLS_RSQRT_ULPS))
+
+
+def gn_partials(stored, rows):
+    """What a producer leaves beside the channels_last / (N, C, H, W) tensor `stored` (any device, the element type): per tile
+    row of `rows` pixels and per channel (sum, sum of squares) of the stored values - float64 sums rounded once to fp32,
+    (N * HW / rows, C, 2) on the CPU."""
+    N, C = stored.shape[:2]
+    v = stored.detach().double().cpu().reshape(N, C, -1).transpose(1, 2)          # (N, HW, C)
+    HW = v.shape[1]
+    assert HW % rows == 0
+    v = v.reshape(N * (HW // rows), rows, C)
+    return torch.stack([v.sum(1), (v * v).sum(1)], -1).float().contiguous()
+
+
+def ln_kernel_bounds(x64, eps):
+    """(mu, rho, d_mean, d_rstd) per row for ln_kernel's two-pass statistics."""
+    mu, m1 = x64.mean(-1), x64.abs().mean(-1)
+    var = ((x64 - mu[..., None]) ** 2).mean(-1)
+    rho = (var + eps).rsqrt()
+    d_mean = LNK_MEAN_ULPS * U_ACC * m1
+    d_var = LNK_VAR_ULPS * U_ACC * var + d_mean * d_mean
+    d_rstd = rho * (0.5 * d_var / (var + eps) + RSQRT_ULPS * U_ACC)
+    return mu, rho, d_mean, d_rstd
+
+
+def layer_norm_ref64(x, gamma, beta, eps, dtype):
+    """(ref64, mag64, None) of st_layer_norm on the rounded operands, x (rows, C)."""
+    xd, gd, bd = r64(x, dtype), r64(gamma, dtype), r64(beta, dtype)
+    mu, rho, d_mean, d_rstd = (t[:, None] for t in ln_kernel_bounds(xd, eps))
+    ref = (xd - mu) * rho * gd + bd
+    mag = (xd.abs() + mu.abs()) * rho * gd.abs() + bd.abs()
+    mag = mag + as_magnitude(rho * gd.abs() * d_mean + d_rstd * (xd - mu).abs() * gd.abs(), 0)
+    return ref, mag, None
+
+
+def geglu_ref64(state, gate, dtype):
+    """(ref64, mag64, extra64) of st_geglu: _epilogue64's GEGLU branch with exact operands (n_terms = 0, no accumulation error
+    in front): the GELU's own absolute error times |state|, and the product's one fp32 rounding among the EPI_OPS.  Gates
+    down to -7.5 give products under 2^-14, which fp16 stores as subnormals: an ABSOLUTE rounding error of half their spacing,
+    2^-25, that U_OUT |ref| does not hold (ATT_SUBNORMAL_P is the same fact for a stored P); bf16 and fp32 have fp32's exponent
+    range."""
+    v, g = r64(state, dtype), r64(gate, dtype)
+    assert float(g.abs().max()) < ACT_RANGE
+    ge = gelu_abs_err(dtype)
+    gl = gelu64(g)
+    return v * gl, (gl.abs() + ge) * v.abs(), v.abs() * ge + (2.0 ** -25 if dtype == torch.float16 else 0.0)
+
+
+# ---- input families -------------------------------------------------------------------------------------------------------------
+# normal    x * 1.5 + 0.7
+# offset    mean 8, deviation 1 in every group: q / var = 65, so the cancellation term of d_var is visible while the budget
+#           still means something.  |mu| / sigma = 8 is a CHOICE that makes the term show, not a measurement of what SDXL's
+#           groups reach.
+# gradient  unit normal plus 3 * p / HW along the pixel index p: block means differ, the Chan cross term carries weight
+# quiet     `normal`, but one group (G // 2) is unit normal scaled to a deviation of 1e-2: eps = 1e-5 is a tenth of its variance
+NORM_FAMILIES = ("normal", "offset", "gradient", "quiet")
+
+
+def gn_operands(shape, family="normal"):
+    """(x (N, C, H, W), gamma, beta) of a GroupNorm case (N, C, H, W, G), fp32 on the CPU."""
+    N, C, H, W, G = shape
+    z = normal(f"n.x{N}.{C}.{H}.{W}", (N, C, H, W))
+    if family == "normal":
+        x = z * 1.5 + 0.7
+    elif family == "offset":
+        x = z + 8.0
+    elif family == "gradient":
+        x = z + 3.0 * torch.arange(H * W, dtype=torch.float32).view(1, 1, H, W) / (H * W)
+    else:
+        assert family == "quiet"
+        x = z * 1.5 + 0.7
+        cpg, g = C // G, G // 2
+        x[:, g * cpg:(g + 1) * cpg] = z[:, g * cpg:(g + 1) * cpg] * 1e-2
+    return x, normal(f"n.g{C}", (C,), 0.2) + 1.0, normal(f"n.b{C}", (C,), 0.2)
+
+
+# (N, C, H, W, G).  NHWC: cpg = 3 with idle threads in one block | N * G = 9: the last gn_finalize block has one live wave |
+# several blocks (16 bits: four of 20 pixels, the last ragged with 17; fp32: seven whole ones of 11) | cpg = 15 | the block cap:
+# VC = 320, RP = 3, 225 blocks of P = 4 > RP pixels (the last with 3), gn_finalize lanes fold three or four partials |
+# G = 1 | one pixel | G = C
+GN_NHWC = [(1, 96, 5, 7, 32), (3, 24, 3, 3, 3), (1, 320, 7, 11, 32), (2, 120, 4, 3, 8), None, (1, 64, 4, 4, 1), (1, 40, 1, 1, 8),
+           (2, 32, 3, 3, 32)]
+GN_NHWC_CAP = {torch.float32: (1, 1280, 31, 29, 32), torch.bfloat16: (1, 2560, 31, 29, 32), torch.float16: (1, 2560, 31, 29, 32)}
+# NCHW: two statistics blocks per group with a chunk that is no multiple of 256, three apply blocks | one statistics block |
+# N * G = 9 | one pixel
+GN_NCHW = [(1, 8, 33, 63, 2), (1, 8, 33, 31, 2), (3, 24, 3, 3, 3), (1, 40, 1, 1, 8)]
+
+
+def gn_nhwc_shapes(dtype):
+    return [GN_NHWC_CAP[dtype] if s is None else s for s in GN_NHWC]
+
+
+def gn_cases(dtype):
+    """(nhwc, shape, family): `normal` everywhere, the other families on the first case of each layout."""
+    out = []
+    for nhwc, shapes in ((True, gn_nhwc_shapes(dtype)), (False, GN_NCHW)):
+        out += [(nhwc, s, "normal") for s in shapes] + [(nhwc, shapes[0], f) for f in NORM_FAMILIES[1:]]
+    return out
+
+
+# GroupNorm from producer statistics: (N, C0, C1, HW, G, rows0, rows1), family.  cpg = 15, the group over channels 60..74
+# straddles the sources, 3 and 2 tile rows | cpg = 60: 480 and 240 (channel, tile) pairs a group (more than the 256 threads),
+# group 21 straddles | one source, one tile | the first again with a quiet group
+GN_STATS = [((2, 64, 56, 12, 8, 4, 6), "normal"), ((2, 1280, 640, 64, 32, 8, 16), "normal"), ((1, 64, 0, 16, 4, 16, 0), "normal"),
+            ((2, 64, 56, 12, 8, 4, 6), "quiet")]
+
+
+def gn_stats_shape(case):
+    """The (N, C, H, W, G) of a from-statistics case: rows of four pixels."""
+    N, C0, C1, HW, G, _, _ = case
+    return (N, C0 + C1, HW // 4, 4, G)
+
+
+# LayerNorm (rows, C): per type every NV from 1 to 8 at a ragged width (23 live lanes in the last vector row; 1, 3, 5, 6, 7 rows:
+# a last block with idle waves), the shapes of test_edges_gpu.py::test_layer_norm_edges, the full-width NV = 8, the UNet's widths
+def ln_cases(dtype):
+    vec = vec_of(dtype)
+    shapes = [((5, 6, 7, 1, 3)[k % 5], (64 * k + 23) * vec) for k in range(8)]
+    shapes += [(5, 1432), (6, 1720), (1, 8), (7, 512 * vec), (9, 640), (3, 1280)]
+    if dtype != torch.float32:
+        shapes += [(5, 2864), (6, 3440)]
+    return shapes
+
+
+LN_FAMILIES = ("normal", "offset")
+
+
+def ln_operands(shape, family="normal"):
+    rows, C = shape
+    z = normal(f"n.ln{rows}.{C}", (rows, C))
+    return (z * 1.5 + 0.7 if family == "normal" else z + 8.0), normal(f"n.lg{C}", (C,), 0.2) + 1.0, normal(f"n.lb{C}", (C,), 0.2)
+
+
+# GEGLU (rows, F): smallest strided halves | rows no multiple of 4 | just over 4096 * 256 vectors: the first 16,384 (16 bits) /
+# 17,424 (fp32) threads take a second grid-stride pass
+GEGLU_SMALL = [(3, 8), (5, 40)]
+GEGLU_STRIDE2 = {torch.float32: (520, 8200), torch.bfloat16: (1040, 8192), torch.float16: (1040, 8192)}
+# halves: the two column halves of one NaN-separated buffer (equal row strides); dense: two contiguous tensors; mixed: a dense
+# state and a gate that is the second half of such a buffer (the row strides differ)
+GEGLU_LAYOUTS = ("halves", "dense", "mixed")
+GEGLU_GATE_SPAN = 7.5
+
+
+def geglu_cases(dtype):
+    """(shape, layout): every layout at the small shapes, the two of the issue at the large one."""
+    return [(s, l) for s in GEGLU_SMALL for l in GEGLU_LAYOUTS] + [(GEGLU_STRIDE2[dtype], l) for l in GEGLU_LAYOUTS[:2]]
+
+
+def geglu_operands(shape):
+    """(state, gate) fp32 on the CPU; the gate's arguments scaled to span [-7.5, 7.5]."""
+    rows, Fh = shape
+    g = normal(f"n.gg{rows}.{Fh}", (rows, Fh))
+    return normal(f"n.gs{rows}.{Fh}", (rows, Fh)) * 2.0, g * (GEGLU_GATE_SPAN / float(g.abs().max()))
